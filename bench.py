@@ -20,6 +20,24 @@ scaling) and the only collective is the RCCL all-reduce of the class sums.
 
 `--gpus N` without a torch.distributed launcher re-launches itself under one (N child processes) before any GPU call;
 a launcher whose world size differs from N is an error.  It never silently runs a single rank.
+
+    python bench.py --steps 6 --warmup 1 --dump-outputs bench_outputs     # also write what the last timed step computed
+
+`--dump-outputs DIR` writes, after the timed steps, what a caller of the timed path receives from its last step, one
+DIR/<name>.npy per array (float32, or float64 for integer fields): the per-particle parameters `param_<field>` (the fields of
+api.RESULT_DTYPE) and `shift_state`, then `references` + `class_sizes` (multi-reference) or `average` + `criterion`
+(reference-free).  Rank 0's shard only.  The inputs are seeded, so the same arguments give the same inputs on every run and two
+builds can be compared array for array.  Above 64 MB in all, a fixed seeded sample of rows is written instead, with the
+chosen row indices in `particle_rows.npy` / `<name>_rows.npy`.
+
+The result line (one JSON line on stdout, printed last): `ms_per_step` is the wall time of one timed step (host clock around
+`--steps` steps that end in a device synchronisation).  In `roofline`, `frac` / `achieved` are of the dominant kernel on
+ALGORITHMIC work; `mfma_busy_frac` is that kernel's matrix-pipe utilisation in the committed PMC passes
+(SQ_VALU_MFMA_BUSY_CYCLES / (kernel cycles x 1024 SIMDs)); `traffic` is HBM bytes per launch (PMC FETCH_SIZE x 2 + WRITE_SIZE
+per particle x particles per launch, x live_shift_fraction for kernels that evaluate in-window offsets only: the PMC passes run
+full windows), and `hbm_bus_gbps` / `hbm_bus_frac` are those bytes over the live launch time and 8 TB/s -- bus utilisation, not
+a roofline fraction of useful work.  `other_workloads` holds each side workload's rate, step time, dominant kernel, roofline
+fraction and parity summary.
 """
 import argparse
 import json
@@ -78,7 +96,12 @@ def parse_args(argv=None):
     ap.add_argument("--no-pcie", action="store_true")
     ap.add_argument("--no-others", action="store_true", help="headline workload only (the default run appends short runs of "
                     "reffree, mref50 and largebox under \"other_workloads\")")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     cfg, nx, ou, xr, nref, n, steps, warm = WORKLOADS[args.workload]
     args.config_name = cfg
     args.custom_geometry = any(v is not None for v in (args.particles, args.nref, args.nx, args.ou, args.xr)) or args.chunk != 0
@@ -309,6 +332,58 @@ def committed_traffic(kernel_substr, workload, geometry=None):
     return None, None, None
 
 
+DUMP_BUDGET = 64 << 20      # bytes of .npy data --dump-outputs writes at most
+DUMP_SEED = 20261015        # the row sample it writes when the outputs are larger
+
+
+def step_outputs(al, reffree, last):
+    """what a caller of the timed path receives from its last step (mref_ali2d_gpu / ali2d_base_gpu return the same):
+    name -> float32 / float64 numpy array.  `last` is what that step's iterate() returned."""
+    import numpy as np
+    r = al.params()
+    out = {"param_" + f: r[f].astype(np.float32 if r.dtype[f].kind == "f" else np.float64) for f in r.dtype.names}
+    out["shift_state"] = al.state.cpu().numpy().astype(np.float32)
+    if reffree:
+        out["average"] = al.tavg[0].cpu().numpy().astype(np.float32)
+        out["criterion"] = np.array([last], np.float64)
+    else:
+        out["references"] = al.refs.cpu().numpy().astype(np.float32)
+        out["class_sizes"] = np.asarray(last, np.float64)
+    return out
+
+
+def write_outputs(dirname, arrays, n, budget=DUMP_BUDGET):
+    """DIR/<name>.npy for every array; arrays whose first axis is the n particles are per particle.  Above `budget` bytes in
+    all, a seeded sample of rows: of any other array larger than half the budget (its row indices in <name>_rows.npy), then of
+    the particles (particle_rows.npy), the same rows for every per-particle array."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+
+    def sample(rows, k):
+        return np.sort(np.random.default_rng(DUMP_SEED).choice(rows, k, replace=False))
+
+    files = {}
+    per = {k: a for k, a in arrays.items() if a.ndim and a.shape[0] == n}
+    for name, a in arrays.items():
+        if name in per:
+            continue
+        if a.nbytes > budget // 2 and a.shape[0] > 1:
+            idx = sample(a.shape[0], max(1, (budget // 2) // (a.nbytes // a.shape[0] + 8)))
+            a = a[idx]
+            files[name + "_rows"] = idx.astype(np.float64)
+        files[name] = a
+    left = budget - sum(a.nbytes for a in files.values())
+    row = sum(a.nbytes // n for a in per.values()) if n else 0
+    if per and n * row > left:
+        idx = sample(n, max(1, left // (row + 8)))
+        per = {k: a[idx] for k, a in per.items()}
+        files["particle_rows"] = idx.astype(np.float64)
+    files.update(per)
+    for name, a in files.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+    return sorted(files)
+
+
 def run_workload(args, rank, local, world, dev):
     """one workload: generate the shard, warm up, time `args.steps` steps; returns the JSON line (rank 0) or None"""
     import numpy as np
@@ -355,11 +430,13 @@ def run_workload(args, rank, local, world, dev):
     for _ in range(args.steps):
         if solo:          # a few small device-side operations per step, no synchronisation: the windows of the coming search
             live += live_offsets(al.state, nx, ou, xr, xr, 1.0, reffree)
-        step()
+        last = step()
     rdist.barrier(); torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     dt = rdist.max_over_ranks(dt, dev)
     ms_a, n_a, ms_b, n_b = al.engine.kernel_time(False)
+    if rank == 0 and args.dump_outputs:
+        write_outputs(args.dump_outputs, step_outputs(al, reffree, last), n)
     path = al.engine.search_path
     tiled = al.engine.search_tiled
     opp = al.engine.search_offsets_per_pass
@@ -438,14 +515,8 @@ def run_workload(args, rank, local, world, dev):
                          "frac": hbm_alg_frac if hbm_bound else kernels[dom]["frac"],
                          "mfma_frac": kernels[dom]["frac"], "hbm_algorithmic_gbps": hbm_alg_gbps, "hbm_algorithmic_frac": hbm_alg_frac,
                          "mfma_busy_frac": mfma_busy,
-                         "mfma_busy_what": "matrix-pipe utilisation of this kernel in the committed PMC passes: SQ_VALU_MFMA_BUSY_CYCLES / "
-                                           "(kernel cycles x 1024 SIMDs)",
                          "hbm_bus_gbps": hbm_gbps, "hbm_bus_frac": hbm_frac,
-                         "hbm_bus_what": "measured bytes through the L2 <-> fabric boundary (traffic) / live launch time / 8 TB/s: bus "
-                                         "utilisation, not a roofline fraction of useful work",
                          "traffic": traffic_pp * per_launch if traffic_pp is not None else None,
-                         "traffic_unit": "HBM bytes per launch (PMC FETCH_SIZE x 2 + WRITE_SIZE per particle x particles per launch; x live_shift_fraction "
-                                         "for kernels that evaluate in-window offsets only: the PMC passes run full windows)",
                          "traffic_per_particle": traffic_pp, "traffic_per_particle_full_windows": traffic_full, "traffic_source": traffic_src,
                          "algorithmic_bytes_per_particle": alg_bytes,
                          "kernel": dom, "flops_per_particle": kernels[dom]["flops_per_particle"],
@@ -471,6 +542,20 @@ def run_workload(args, rank, local, world, dev):
 
 # what the default run adds to the headline line: the other BASELINE configs at one GPU's share, a few steps each
 OTHER_WORKLOADS = ("reffree", "mref50", "largebox", "nb00", "box128", "box100", "box256")
+
+
+def side_summary(line):
+    """the numbers of a side workload's line that go under "other_workloads" (the whole line of every workload would make
+    the one result line too long to be read back)"""
+    rf = line["roofline"]
+    out = {k: line[k] for k in ("metric", "value", "steps", "warmup", "ms_per_step")}
+    out.update(kernel=rf["kernel"], bound=rf["bound"], frac=rf["frac"], whole_path_frac=rf["whole_path"]["frac"])
+    sig = [v for k, v in line.get("parity", {}).items() if k.startswith("sigma_")]
+    if sig:
+        out["parity"] = {"exact_match_rate": min(v["exact_match_rate"] for v in sig), "tie_flips": sum(v["tie_flips"] for v in sig),
+                         "max_rel_peak": max(v["max_rel_peak"] for v in sig),
+                         "alpha_outliers_gt_2e-3_deg": sum(v["alpha_outliers_gt_2e-3_deg"] for v in sig)}
+    return out
 
 
 def main():
@@ -508,9 +593,7 @@ def main():
             sub = parse_args(["--workload", w, "--no-cpu-baseline", "--no-pcie", "--sigma", str(args.sigma)] +
                              (["--no-parity"] if args.no_parity else []))
             t0 = time.perf_counter()
-            o = run_workload(sub, rank, local, world, dev)
-            o = {k: o[k] for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "dtype", "config", "roofline", "parity") if k in o}
-            o["roofline"] = {k: v for k, v in o["roofline"].items() if k != "kernels"}
+            o = side_summary(run_workload(sub, rank, local, world, dev))
             o["wall_s"] = time.perf_counter() - t0
             others[w] = o
         line["other_workloads"] = others
