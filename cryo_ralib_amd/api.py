@@ -69,7 +69,7 @@ EXPORTED_SYMBOLS = [
     "ra_debug_spectra", "ra_transform_accumulate", "ra_update_references", "ra_normalize_particles", "ra_sync", "ra_kernel_time",
     "ra_fsc_len", "ra_class_fsc", "ra_last_class_fsc", "ra_fit_tanh", "ra_class_averages", "ra_filter_references",
     "ra_state_from_params_dev", "ra_class_fsc_fit", "ra_filter_references_dev", "ra_last_refine_count",
-    "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets",
+    "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
 ]
 
 _lib = None
@@ -167,6 +167,7 @@ def load_library(path=None):
     L.ref_free_alignment_2D_filter_references.restype = None
     L.ref_free_alignment_2D_filter_references.argtypes = [ctypes.c_float, ctypes.c_float]
     L.ra_isac_get_references.argtypes = [float_ptr]
+    L.ra_phase_flip.argtypes = [vp, ctypes.c_int, ctypes.c_int, float_ptr, ctypes.c_int, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -193,6 +194,27 @@ def fit_tanh(dres, low=0.1):
     _check(load_library().ra_fit_tanh(fr, fs, n, ctypes.byref(fl), ctypes.byref(aa)), "ra_fit_tanh")
     dres[1][:] = [float(v) for v in fs]
     return fl.value, aa.value
+
+
+def phase_flip(images, ctf, pad=True):
+    """CTF phase flip of images [n][nx][nx] (contiguous float32 CUDA tensor), in place, on the current stream (ra_phase_flip).
+    ctf: [n][9] table in the utils_ralib.parse_ctf_star layout (numpy or tensor; it is checked on the host before the launch).
+    pad=True embeds every image in a 2nx x 2nx zero image (SPHIRE filt_ctf's default padding), pad=False flips at nx.
+    Returns `images`."""
+    import torch
+    assert images.is_cuda and images.is_contiguous() and images.dtype == torch.float32, "images: contiguous float32 CUDA tensor"
+    assert images.dim() == 3 and images.shape[1] == images.shape[2], "images: [n][nx][nx]"
+    n, nx = int(images.shape[0]), int(images.shape[-1])
+    if isinstance(ctf, torch.Tensor):
+        ctf = ctf.detach().cpu().numpy()
+    tab = np.ascontiguousarray(ctf, np.float32)
+    if tab.shape != (n, 9):
+        raise EngineError("phase_flip: the CTF table is [%d][9], got %s" % (n, tab.shape))
+    stream = torch.cuda.current_stream(images.device)
+    with torch.cuda.device(images.device):
+        _check(load_library().ra_phase_flip(ctypes.c_void_p(images.data_ptr()), n, nx, tab.ctypes.data_as(float_ptr),
+                                            int(bool(pad)), ctypes.c_void_p(stream.cuda_stream)), "ra_phase_flip")
+    return images
 
 
 def _check(rc, what):

@@ -16,6 +16,12 @@ centring on the device; any other name is rejected.  An optional mask file repla
 outdir by default, of the input stack itself with --header_writeback (the reference's behaviour).
 Options that would change the result and are not implemented (--CTF, --center 2..5, --random_method, --Fourvar,
 --dst != 0, --mode other than F, --randomize, --orient) end the run with an error; --MPI / --EQ select paths with the same results and are only noted.
+
+--phase_flip TABLE is what the reference's --CTF does on its GPU path (test_mref_gpu_align.py:303-308, 341-345;
+test_reffree_gpu_align.py:252-257, 279-281): every particle is phase-flipped once at setup, after the masked-mean
+subtraction, and the CTF-free alignment follows.  TABLE is a [N][9] .npy or a RELION .star (cryo_ralib_amd.ctf); --apix
+gives the pixel size where the .star has none, --phase_flip_nopad flips without the 2x zero padding.  --CTF itself, which
+reads the parameters from the stack's EMAN.ctf headers, stays rejected.
 """
 import argparse
 import os
@@ -38,6 +44,11 @@ def _common(p):
     p.add_argument("--gpu_info", action="store_true")
     p.add_argument("--MPI", action="store_true")
     p.add_argument("--EQ", action="store_true")
+    p.add_argument("--phase_flip", default="", metavar="TABLE",
+                   help="phase-flip every particle at setup with the CTF table TABLE ([N][9] .npy or RELION .star): what the "
+                        "reference's --CTF does on its GPU path")
+    p.add_argument("--apix", type=float, default=None, help="pixel size (A) for a --phase_flip .star file that gives none")
+    p.add_argument("--phase_flip_nopad", action="store_true", help="flip at the box size instead of in a 2x zero-padded image")
     p.add_argument("--ext", default="hdf", help="format of the written stacks: hdf (EMAN2 MDF, as the reference) | mrcs | npy")
     p.add_argument("--header_writeback", action="store_true",
                    help="write xform.align2d / assign / ID into the headers of the HDF INPUT stack itself, as the reference does "
@@ -121,6 +132,17 @@ def _write_headers(mdfio, args, params, assign=None, ids=None):
               file=sys.stderr)
 
 
+def _ctf_shard(args, total, nx, lo, hi):
+    """rows lo:hi of the --phase_flip table (the rank's particles), or None"""
+    if not args.phase_flip:
+        return None
+    from . import ctf
+    try:
+        return ctf.load_table(args.phase_flip, total, nx, args.apix, lo, hi)
+    except (ctf.CtfTableError, OSError) as e:
+        raise SystemExit("--phase_flip: %s" % e)
+
+
 def _setup(args):
     import torch
     from . import dist as rdist
@@ -163,7 +185,8 @@ def main_mref(argv=None):
     mask = stackio.read_stack(args.maskfile)[0] if args.maskfile else None      # get_image(maskfile) (:317-319)
     xr, yr, ts = _first(args.xr), _first(args.yr), _first(args.ts)
     al = MrefAligner(data, refs, ou, xr, yr, ts, int(args.ir), int(args.rs), device=local, index0=lo,
-                     total_nima=total, rand_seed=args.rand_seed, preprocess=True, mask=mask)
+                     total_nima=total, rand_seed=args.rand_seed, preprocess=True, mask=mask,
+                     ctf=_ctf_shard(args, total, nx, lo, hi), ctf_pad=not args.phase_flip_nopad)
     if rank == 0:
         os.makedirs(args.outdir, exist_ok=True)
     maxit = int(args.maxit) if int(args.maxit) > 0 else 10
@@ -246,7 +269,8 @@ def main_reffree(argv=None):
     mask = stackio.read_stack(args.maskfile)[0] if args.maskfile else None
     # "--xr '4 2 1 1' --ts '2 1 0.5 0.25'": one stage per entry, --maxit iterations each; --maxit 0 = 10 with auto-stop
     al = RefFreeAligner(data, ou, args.xr, args.yr, args.ts, int(args.ir), int(args.rs), device=local, index0=lo,
-                        total_nima=total, nomirror=args.nomirror, mask=mask)
+                        total_nima=total, nomirror=args.nomirror, mask=mask,
+                        ctf=_ctf_shard(args, total, nx, lo, hi), ctf_pad=not args.phase_flip_nopad)
     max_iter = 10 if int(args.maxit) == 0 else int(args.maxit)
     auto_stop = args.auto_stop and int(args.maxit) == 0
     al.track_pixel_error = True

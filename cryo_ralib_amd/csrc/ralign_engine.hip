@@ -23,6 +23,7 @@
 #include "ralign_pair.h"
 #include "ralign_exact.h"
 #include "ralign_refine.h"
+#include "ralign_ctf.h"
 
 using namespace ralign;
 
@@ -2745,4 +2746,72 @@ extern "C" int ra_isac_get_references(float *h_out)
 extern "C" size_t ra_legacy_bytes(const unsigned int num_particles, const AlignConfig *cfg)
 {
     return cfg ? legacy_bytes(num_particles, cfg) : (size_t)-1;
+}
+
+// ---- CTF phase flip (ralign_ctf.h)
+
+#define PF_GBLK_BYTES ((size_t)512 << 20)      // global scratch of the large-box route: the grid is sized to stay within it
+
+extern "C" int ra_phase_flip(float *d_images, int n, int nx, const float *ctf, int pad, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 0 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1)) {
+        g_last_error = "ra_phase_flip: need n >= 0, 2 <= nx <= 1024 and pad 0 or 1";
+        return RA_ERR_ARG;
+    }
+    if (n == 0) return RA_OK;
+    if (!d_images || !ctf) { g_last_error = "ra_phase_flip: null argument"; return RA_ERR_ARG; }
+    for (int i = 0; i < n; i++) {
+        const float *c = ctf + (size_t)i * 9;
+        bool finite = true;
+        for (int j = 0; j < 9; j++) finite = finite && std::isfinite(c[j]);
+        if (!finite || c[0] <= 0.f || c[1] <= 0.f || c[5] <= 0.f || c[7] < 0.f || c[7] >= 1.f) {
+            char buf[256];
+            snprintf(buf, sizeof(buf), "ra_phase_flip: CTF row %d out of range (needs finite values, D > 0, Apix > 0, "
+                     "voltage > 0, 0 <= w < 1)", i);
+            g_last_error = buf;
+            return RA_ERR_ARG;
+        }
+    }
+    const PfPlan pl = pf_make_plan(nx, pad);
+    if (pl.nb < 1) { g_last_error = "ra_phase_flip: no plan for this box"; return RA_ERR_ARG; }
+    // the common boxes run a kernel specialised for their plan; any other box the kernel that takes the plan as an argument
+    const void *fk = nullptr;
+    switch (nx * 2 + pad) {
+    case 90 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<90, 1>; break;
+    case 90 * 2: fk = (const void *)phase_flip_fixed_kernel<90, 0>; break;
+    case 100 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<100, 1>; break;
+    case 128 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<128, 1>; break;
+    case 130 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<130, 1>; break;
+    case 256 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<256, 1>; break;
+    default: break;
+    }
+    const bool fixed = fk != nullptr;
+    if (!fixed) fk = pl.gblk ? (const void *)phase_flip_kernel<true> : (const void *)phase_flip_kernel<false>;
+    RA_HIP(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
+    // the global-block route: as many workgroups as fit on the chip at this LDS size (256 CUs), within PF_GBLK_BYTES of scratch
+    const size_t blk_bytes = (size_t)nx * pl.H * sizeof(float2);
+    const size_t resident = (size_t)256 * std::max(1, std::min(4, (int)((size_t)160 * 1024 / pl.lds)));     // <= 32 waves per CU
+    const int grid = pl.gblk ? (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(resident, PF_GBLK_BYTES / blk_bytes))) : n;
+    float *d_ctf = nullptr;
+    float2 *d_scr = nullptr;
+    RA_HIP(hipMallocAsync((void **)&d_ctf, (size_t)n * 9 * sizeof(float), stream));
+    // the table is pageable host memory of the caller: hipMemcpyAsync stages such a copy before it returns, so the caller may free
+    // it as soon as this call returns (a caller passing PINNED memory must keep it alive until the stream has run the copy)
+    hipError_t he = hipMemcpyAsync(d_ctf, ctf, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_scr, (size_t)grid * blk_bytes, stream);
+    if (he == hipSuccess) {
+        void *args_fixed[] = {&d_images, &n, &d_ctf, &d_scr};
+        PfPlan pl_arg = pl;
+        void *args_plan[] = {&d_images, &n, &d_ctf, &pl_arg, &d_scr};
+        he = hipLaunchKernel(fk, dim3(grid), dim3(PF_THREADS), fixed ? args_fixed : args_plan, pl.lds, stream);
+        if (he == hipSuccess) he = hipGetLastError();
+    }
+    if (d_scr) (void)hipFreeAsync(d_scr, stream);
+    (void)hipFreeAsync(d_ctf, stream);
+    if (he != hipSuccess) {
+        g_last_error = std::string("ra_phase_flip: ") + hipGetErrorString(he);
+        return RA_ERR_HIP;
+    }
+    return RA_OK;
 }

@@ -65,14 +65,18 @@ class _Lagged:
 
 class MrefAligner:
     def __init__(self, particles, refs, ou, xr, yr, ts=1.0, ir=1, rs=1, device=0, index0=0, total_nima=None,
-                 rand_seed=1000, preprocess=True, chunk=0, myid=0, main_node=0, mask=None, state_roundtrip=True, refine=None):
+                 rand_seed=1000, preprocess=True, chunk=0, myid=0, main_node=0, mask=None, state_roundtrip=True, refine=None,
+                 ctf=None, ctf_pad=True):
         """particles: [n][nx][nx] float32 numpy array or CUDA tensor holding THIS rank's shard;
         refs: [R][nx][nx]; index0 = global index of particles[0] (even/odd split).
         state_roundtrip: rebuild the shift every search starts from out of the float32 (alpha, sx, sy) of the previous
         iteration with inverse_transform2, as the reference's loop does (test_mref_gpu_align.py:1024-1026); False carries
         the exact accumulated shift instead (algebraically the same; differs by rounding at edge-limited windows).
         refine: threshold of the sub-bin angle refinement (api.Engine.set_refine; None = the engine's default, -1 = every
-        particle: alpha / sx / sy then equal the CPU path's to the last bit wherever the integer winner agrees)."""
+        particle: alpha / sx / sy then equal the CPU path's to the last bit wherever the integer winner agrees).
+        ctf: [n][9] CTF table of this shard (ctf.load_table): the particles are phase-flipped once, right after the masked-mean
+        subtraction (api.phase_flip, pad 2x unless ctf_pad=False), as the reference's GPU driver does with --CTF
+        (test_mref_gpu_align.py:303-308, 341-345); everything after it is unchanged."""
         self.state_roundtrip = bool(state_roundtrip)
         self._have_params = False
         self.dev = torch.device("cuda", device)
@@ -111,6 +115,8 @@ class MrefAligner:
         if preprocess:
             self._normalize_refs_all()
             self.engine.normalize_particles(self.particles)    # :342
+        if ctf is not None:
+            api.phase_flip(self.particles, ctf, ctf_pad)       # filt_ctf(img, ctf, binary = True) (:345)
 
     def _to_dev(self, a):
         if isinstance(a, np.ndarray):
@@ -237,11 +243,13 @@ class MrefAligner:
 
 
 def mref_ali2d_gpu(stack, refim, ou, xrng, yrng, step=1.0, ir=1, rs=1, maxit=10, rand_seed=1000, device=0,
-                   index0=0, total_nima=None, user_func=None, chunk=0, on_iteration=None, center=1):
+                   index0=0, total_nima=None, user_func=None, chunk=0, on_iteration=None, center=1, ctf=None, ctf_pad=True):
     """Multi-reference alignment of this rank's shard `stack` against `refim`
     (mirror of mref_ali2d_gpu, test_mref_gpu_align.py:222).  Returns
-    (params records, class averages [R][nx][nx] numpy, list of class-size arrays)."""
-    al = MrefAligner(stack, refim, ou, xrng, yrng, step, ir, rs, device, index0, total_nima, rand_seed, True, chunk)
+    (params records, class averages [R][nx][nx] numpy, list of class-size arrays).  ctf: [n][9] table of the shard: the
+    particles are phase-flipped at setup (MrefAligner)."""
+    al = MrefAligner(stack, refim, ou, xrng, yrng, step, ir, rs, device, index0, total_nima, rand_seed, True, chunk,
+                     ctf=ctf, ctf_pad=ctf_pad)
     max_iter = int(maxit) if int(maxit) > 0 else 10
     for it in range(max_iter):
         counts = al.iterate(user_func, center)
@@ -269,10 +277,12 @@ class RefFreeAligner:
 
     xr / yr / ts may be lists ("--xr '4 2 1 1' --ts '2 1 0.5 0.25'"): one search window per stage
     (test_reffree_gpu_align.py:215-216); `set_stage(i)` switches the engine to stage i (reset_shifts, :355-357).
-    The engine is sized once for the stage with the most search offsets and the widest range."""
+    The engine is sized once for the stage with the most search offsets and the widest range.
+    ctf / ctf_pad: phase flip of the particles at setup as in MrefAligner, after the masked-mean subtraction, which then runs
+    even with preprocess=False."""
 
     def __init__(self, particles, ou, xr, yr, ts=1.0, ir=1, rs=1, device=0, index0=0, total_nima=None,
-                 preprocess=False, chunk=0, nomirror=False, mask=None, refine=None):
+                 preprocess=False, chunk=0, nomirror=False, mask=None, refine=None, ctf=None, ctf_pad=True):
         self.dev = torch.device("cuda", device)
         if isinstance(particles, np.ndarray):
             particles = torch.from_numpy(np.ascontiguousarray(particles, np.float32))
@@ -308,8 +318,12 @@ class RefFreeAligner:
                 mask = torch.from_numpy(np.ascontiguousarray(mask, np.float32))
             self.mask = mask.to(self.dev, dtype=torch.float32).reshape(self.nx, self.nx).contiguous()
             self.engine.set_mask(self.mask)
-        if preprocess:
+        if preprocess or ctf is not None:
+            # with a CTF table the masked mean goes first whatever `preprocess` says: the reference subtracts it right before the
+            # flip (test_reffree_gpu_align.py:279-281), and a padded flip of an image with a mean is not the flip of the mean-free one
             self.engine.normalize_particles(self.particles)
+        if ctf is not None:
+            api.phase_flip(self.particles, ctf, ctf_pad)
         self.state = self.engine.new_state(self.n)
         self.result = self.engine.new_result(self.n)
         self.buf = dist.ClassSumBuffer(1, self.nx, self.dev, extra=2)
@@ -429,7 +443,8 @@ class RefFreeAligner:
 
 
 def ali2d_base_gpu(stack, ou, xrng, yrng, step=1.0, ir=1, rs=1, maxit=10, device=0, index0=0, total_nima=None,
-                   center=0, chunk=0, user_func=None, nomirror=False, on_iteration=None, all_stages=False, auto_stop=False):
+                   center=0, chunk=0, user_func=None, nomirror=False, on_iteration=None, all_stages=False, auto_stop=False,
+                   ctf=None, ctf_pad=True):
     """mirror of ali2d_base_gpu_isac_CLEAN; returns (params records, final average, criteria).
     Rows of initial2Dparams.txt are (alpha, sx, sy, mirror) (test_reffree_gpu_align.py:561-569).
 
@@ -437,9 +452,9 @@ def ali2d_base_gpu(stack, ou, xrng, yrng, step=1.0, ir=1, rs=1, maxit=10, device
     (N_step = 0, test_reffree_gpu_align.py:355-357), and maxit = 0 means 10 iterations -- the driver computes and
     broadcasts the auto-stop flag `again` (:422-433) and never tests it.
     all_stages=True runs every stage, `maxit` iterations each (SPHIRE's ali2d_base schedule, "--xr '4 2 1 1' --ts '2 1
-    0.5 0.25'"); auto_stop=True (with maxit = 0) ends a stage with the iteration whose average scored below the best so
+    0.5 0.25'"); ctf: [n][9] table of the shard (phase flip at setup, RefFreeAligner); auto_stop=True (with maxit = 0) ends a stage with the iteration whose average scored below the best so
     far -- the rule the reference's comments state ("a0 should increase; stop algorithm when it decreases", :392-396)."""
-    al = RefFreeAligner(stack, ou, xrng, yrng, step, ir, rs, device, index0, total_nima, False, chunk, nomirror)
+    al = RefFreeAligner(stack, ou, xrng, yrng, step, ir, rs, device, index0, total_nima, False, chunk, nomirror, ctf=ctf, ctf_pad=ctf_pad)
     max_iter = 10 if int(maxit) == 0 else int(maxit)
     auto_stop = bool(auto_stop) and int(maxit) == 0
     a0 = -1.0e22

@@ -297,6 +297,15 @@ int  ra_isac_get_references(float *h_out);
 /* diagnostic: the device-memory estimate (bytes) behind pre_align_size_check; (size_t)-1 for a bad geometry */
 size_t ra_legacy_bytes(const unsigned int num_particles, const AlignConfig *cfg);
 
+/* CTF phase flip of a stack, in place, without an engine: d_images [n][nx][nx] (device); h_ctf [n][9] (HOST, checked before
+ * anything is launched) in the utils_ralib.parse_ctf_star layout (D, Apix, DefocusU, DefocusV, DefocusAngle, Voltage, Cs, w,
+ * PhaseShift; A, A, A, A, degrees, kV, mm, -, degrees).  Per particle: embed in a P x P zero image (P = 2 nx with pad != 0,
+ * nx otherwise) at (P - nx) / 2, real 2-D DFT, multiply by -sign(ctf) (+1 where ctf == 0) with apix_eff = Apix D / nx,
+ * inverse DFT, keep the nx x nx window.  RA_ERR_ARG for nx outside 2 .. 1024, pad not 0 / 1, or a
+ * row with a non-finite value, D <= 0, Apix <= 0, voltage <= 0 or w outside [0, 1).  Asynchronous on hip_stream (a
+ * hipStream_t; NULL = default stream); bitwise reproducible; every particle is independent of the others. */
+int  ra_phase_flip(float *d_images, int n, int nx, const float *h_ctf, int pad, void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
