@@ -7,9 +7,9 @@ reference update (test_mref_gpu_align.py:408-575; test_reffree_gpu_align.py:361-
 Particles are already resident in HBM when the timed region starts.  For N>1 every rank holds its own shard (weak
 scaling) and the only collective is the RCCL all-reduce of the class sums.
 
-    python bench.py --gpus 1 --steps 6 --warmup 1                       # BASELINE configs[1] (the metric's config); at one GPU
-                                                                        # the line also carries short runs of the three workloads
-                                                                        # below under "other_workloads" (--no-others: headline only)
+    python bench.py --gpus 1 --steps 6 --warmup 1                       # BASELINE configs[1] (the metric's config): the headline only
+    python bench.py --gpus 1 --steps 6 --warmup 1 --full                # the same headline, then everything else the benchmark
+                                                                        # measures or checks (see below)
     python bench.py --workload reffree                                  # BASELINE configs[2]
     python bench.py --workload largebox                                 # BASELINE configs[4] geometry, one GPU's share
     python bench.py --workload mref50                                   # BASELINE configs[3], one GPU's share (125k particles, nref=50)
@@ -17,6 +17,13 @@ scaling) and the only collective is the RCCL all-reduce of the class sums.
                                                                         # nref 50, 128 x 128 / ou 60, 100 x 100 / ou 40
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the steps, writes `--dump-outputs` if asked and prints the result line; its `roofline`
+comes from the HIP-event kernel times of those same timed steps and the committed profiles.  `--full` adds what needs runs of
+its own: `pcie_inclusive` (one pinned H2D copy of the shard), `parity` (the engine against the CPU oracle on two subsamples) and
+`cpu_baseline` (the oracle timed on this host's cores) at one GPU, and -- at one GPU with the default mref geometry -- short runs
+of the other workloads under "other_workloads".  `--no-pcie`, `--no-parity`, `--no-cpu-baseline` and `--no-others` leave
+single parts of that out of a `--full` run.
 
 `--gpus N` without a torch.distributed launcher re-launches itself under one (N child processes) before any GPU call;
 a launcher whose world size differs from N is an error.  It never silently runs a single rank.
@@ -91,11 +98,13 @@ def parse_args(argv=None):
     ap.add_argument("--chunk", type=int, default=0)
     ap.add_argument("--function", default="ref_ali2d", help="reference preparation per iteration: ref_ali2d (the "
                     "reference's default --function: FSC-fitted tangent filter + centring, on the device) | none")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-parity", action="store_true")
-    ap.add_argument("--no-pcie", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="headline workload only (the default run appends short runs of "
-                    "reffree, mref50 and largebox under \"other_workloads\")")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check what it does not need: "
+                    "PCIe-inclusive rate, parity against the CPU oracle, CPU baseline, short runs of the other workloads")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
+    ap.add_argument("--no-parity", action="store_true", help="with --full: no parity block")
+    ap.add_argument("--no-pcie", action="store_true", help="with --full: no PCIe-inclusive rate")
+    ap.add_argument("--no-others", action="store_true", help="with --full: headline workload only (no short runs of the "
+                    "other workloads under \"other_workloads\")")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy")
     args = ap.parse_args(argv)
     if args.steps is not None and args.steps < 1:
@@ -109,6 +118,11 @@ def parse_args(argv=None):
     args.nref = args.nref or nref; args.particles = args.particles or n
     args.steps = steps if args.steps is None else args.steps
     args.warmup = warm if args.warmup is None else args.warmup
+    # the parts of a --full run; a plain run does none of them
+    args.pcie = args.full and not args.no_pcie
+    args.parity = args.full and not args.no_parity
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.others = args.full and not args.no_others and args.workload == "mref" and not args.custom_geometry
     return args
 
 
@@ -398,7 +412,7 @@ def run_workload(args, rank, local, world, dev):
     refs_np = synth.make_references(max(nref, 1), nx, ou)
     particles, _ = generate_shard(dev, refs_np, n, xr, xr, args.sigma, rank, nx, ou)
     pcie = None
-    if rank == 0 and not args.no_pcie:
+    if rank == 0 and args.pcie:
         # the boundary hands over host buffers (pre_align_fetch): one pinned H2D copy of the shard, measured once
         host = torch.empty(particles.shape, dtype=torch.float32, pin_memory=True)
         host.copy_(particles)
@@ -530,9 +544,9 @@ def run_workload(args, rank, local, world, dev):
             line["pcie_inclusive"] = {"value": total / world / (pcie + dt), "unit": "particles/s per GPU",
                                       "h2d_seconds": pcie, "h2d_gb_per_s": particles.numel() * 4 / pcie / 1e9,
                                       "note": "one pinned H2D copy of the shard + the %d timed steps" % args.steps}
-        if world == 1 and not args.no_parity:
+        if world == 1 and args.parity:
             line["parity"] = parity_block(refs_np, nx, ou, xr, nref, reffree, dev)
-        if not args.no_cpu_baseline and world == 1:
+        if world == 1 and args.cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(refs_np, nx, ou, xr, xr, nref, reffree)
     al.close()
     del al, particles
@@ -540,7 +554,7 @@ def run_workload(args, rank, local, world, dev):
     return line if rank == 0 else None
 
 
-# what the default run adds to the headline line: the other BASELINE configs at one GPU's share, a few steps each
+# what a --full run adds to the headline line: the other BASELINE configs at one GPU's share, a few steps each
 OTHER_WORKLOADS = ("reffree", "mref50", "largebox", "nb00", "box128", "box100", "box256")
 
 
@@ -585,12 +599,12 @@ def main():
             props.total_memory / 2.0 ** 30, torch.cuda.device_count(), tdist.get_backend() if tdist.is_initialized() else "none"),
             file=sys.stderr, flush=True)
     line = run_workload(args, rank, local, world, dev)
-    if world == 1 and args.workload == "mref" and not args.no_others and not args.custom_geometry:
+    if world == 1 and args.others:
         # the other workloads, measured in the same process right after the headline (short runs, their own parity block, no
         # CPU baseline); the headline keys above are untouched
         others = {}
         for w in OTHER_WORKLOADS:
-            sub = parse_args(["--workload", w, "--no-cpu-baseline", "--no-pcie", "--sigma", str(args.sigma)] +
+            sub = parse_args(["--workload", w, "--full", "--no-cpu-baseline", "--no-pcie", "--sigma", str(args.sigma)] +
                              (["--no-parity"] if args.no_parity else []))
             t0 = time.perf_counter()
             o = side_summary(run_workload(sub, rank, local, world, dev))

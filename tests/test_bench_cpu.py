@@ -1,5 +1,5 @@
-"""bench.py's host-side pieces: the step count it is given, what --dump-outputs writes, the size of the result line's
-side-workload entries (no GPU)."""
+"""bench.py's host-side pieces: the step count it is given, what a plain run does besides its steps, what --dump-outputs
+writes, the size of the result line's side-workload entries (no GPU)."""
 import json
 import os
 
@@ -17,6 +17,22 @@ def test_steps_and_warmup_are_what_was_asked():
     for bad in (["--steps", "0"], ["--warmup", "-1"]):
         with pytest.raises(SystemExit):
             bench.parse_args(bad)
+
+
+def test_plain_run_is_the_headline_alone():
+    parts = ("pcie", "parity", "cpu_baseline", "others")
+    for argv in ([], ["--gpus", "1", "--steps", "6", "--warmup", "1"], ["--no-parity", "--no-others"], ["--workload", "reffree"]):
+        a = bench.parse_args(argv)
+        assert not a.full and not any(getattr(a, p) for p in parts), argv
+    a = bench.parse_args(["--full"])
+    assert all(getattr(a, p) for p in parts)
+    a = bench.parse_args(["--full", "--no-parity", "--no-pcie"])
+    assert (a.pcie, a.parity, a.cpu_baseline, a.others) == (False, False, True, True)
+    a = bench.parse_args(["--full", "--no-cpu-baseline", "--no-others"])
+    assert (a.pcie, a.parity, a.cpu_baseline, a.others) == (True, True, False, False)
+    # the side workloads follow the default mref geometry only
+    assert not bench.parse_args(["--full", "--workload", "reffree"]).others
+    assert not bench.parse_args(["--full", "--particles", "2048"]).others
 
 
 def _outputs(n, nref, nx):
