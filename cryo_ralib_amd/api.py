@@ -70,6 +70,7 @@ EXPORTED_SYMBOLS = [
     "ra_fsc_len", "ra_class_fsc", "ra_last_class_fsc", "ra_fit_tanh", "ra_class_averages", "ra_filter_references",
     "ra_state_from_params_dev", "ra_class_fsc_fit", "ra_filter_references_dev", "ra_last_refine_count",
     "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
+    "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
 ]
 
 _lib = None
@@ -168,6 +169,12 @@ def load_library(path=None):
     L.ref_free_alignment_2D_filter_references.argtypes = [ctypes.c_float, ctypes.c_float]
     L.ra_isac_get_references.argtypes = [float_ptr]
     L.ra_phase_flip.argtypes = [vp, ctypes.c_int, ctypes.c_int, float_ptr, ctypes.c_int, vp]
+    ci = ctypes.c_int
+    L.ra_sdr_mean.argtypes = [vp, ci, ci, ci, vp, vp]
+    L.ra_sdr_gram.argtypes = [vp, ci, ci, ci, vp, ci, vp, ci, vp, vp]
+    L.ra_sdr_project.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
+    L.ra_sdr_factors.argtypes = [vp, ci, ci, vp, ci, vp, vp]
+    L.ra_rot_shift2d.argtypes = [vp, ci, ci, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -215,6 +222,44 @@ def phase_flip(images, ctf, pad=True):
         _check(load_library().ra_phase_flip(ctypes.c_void_p(images.data_ptr()), n, nx, tab.ctypes.data_as(float_ptr),
                                             int(bool(pad)), ctypes.c_void_p(stream.cuda_stream)), "ra_phase_flip")
     return images
+
+
+def rot_shift2d(images, params, out=None):
+    """rot_shift2D of images [n][nx][nx] (contiguous float32 CUDA tensor) by params [n][4] (alpha, sx, sy, mirror), on the current
+    stream (ra_rot_shift2d): the transform of Engine.transform_accumulate, without an engine. Returns out ([n][nx][nx])."""
+    import torch
+    assert images.is_cuda and images.is_contiguous() and images.dtype == torch.float32, "images: contiguous float32 CUDA tensor"
+    assert images.dim() == 3 and images.shape[1] == images.shape[2], "images: [n][nx][nx]"
+    n, nx = int(images.shape[0]), int(images.shape[-1])
+    if isinstance(params, torch.Tensor):
+        params = params.detach().cpu().numpy()
+    prm = np.asarray(params, np.float64)
+    if prm.shape != (n, 4):
+        raise EngineError("rot_shift2d: params is [%d][4] (alpha, sx, sy, mirror), got %s" % (n, prm.shape))
+    rec = np.zeros(n, RESULT_DTYPE)
+    rec["alpha"], rec["sx"], rec["sy"] = prm[:, 0], prm[:, 1], prm[:, 2]
+    rec["mirror"] = (prm[:, 3] != 0).astype(np.int32)
+    if out is None:
+        out = torch.empty_like(images)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == images.shape, "out: like images"
+    d_rec = torch.from_numpy(rec.view(np.uint8)).to(images.device)
+    stream = torch.cuda.current_stream(images.device)
+    with torch.cuda.device(images.device):
+        _check(load_library().ra_rot_shift2d(ctypes.c_void_p(images.data_ptr()), n, nx, ctypes.c_void_p(d_rec.data_ptr()),
+                                             ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream.cuda_stream)), "ra_rot_shift2d")
+    return out
+
+
+def two_sdr(images, p0, q0, r, **kw):
+    """Two-stage dimension reduction of images [n][p][q] (sdr.two_sdr)."""
+    from . import sdr
+    return sdr.two_sdr(images, p0, q0, r, **kw)
+
+
+def mpca(images, p0, q0, **kw):
+    """MPCA of images [n][p][q] (sdr.mpca)."""
+    from . import sdr
+    return sdr.mpca(images, p0, q0, **kw)
 
 
 def _check(rc, what):

@@ -306,6 +306,29 @@ size_t ra_legacy_bytes(const unsigned int num_particles, const AlignConfig *cfg)
  * hipStream_t; NULL = default stream); bitwise reproducible; every particle is independent of the others. */
 int  ra_phase_flip(float *d_images, int n, int nx, const float *h_ctf, int pad, void *hip_stream);
 
+/* Two-stage dimension reduction (utils_ralib.py MPCA / TwoSDR) of a stack in device memory, without an engine (DESIGN.md
+ * section 4.6).  All pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL = default stream)
+ * and allocates and frees its scratch on that stream, as ra_phase_flip does.  Images are [n][p][q] float32, centred on load
+ * (x - mean in fp32) where a mean is given.  Results are bitwise reproducible call to call.  RA_ERR_ARG for anything outside the
+ * documented domain; nothing is launched then.
+ *   ra_sdr_mean     d_mean[p q] = per-pixel mean (double sums in a fixed order, rounded once); 1 <= p, q <= 256, n >= 1.
+ *   ra_sdr_gram     d_gram (double, exactly symmetric):  form 0: sum X_i^T X_i (q x q);  form 1: sum (X_i P)(X_i P)^T (p x p),
+ *                   d_proj P [q][k];  form 2: sum (P^T X_i)^T (P^T X_i) (q x q), d_proj P [p][k].  d_mean NULL: no centring.
+ *                   1 <= p, q <= 256 (form 0 with p == 1: q <= 2048, the second stage's n x m matrix); forms 1 / 2: 1 <= k <= 64
+ *                   and k <= q (form 1) or k <= p (form 2).
+ *   ra_sdr_project  d_U [n][p0 q0] = A^T X_i B, row-major (a, b) -> a q0 + b; d_A [p][p0], d_B [q][q0];
+ *                   1 <= p0 <= min(p, 64), 1 <= q0 <= min(q, 64), p0 q0 <= 2048.
+ *   ra_sdr_factors  d_F [n][r] = U G; d_U [n][m], d_G [m][r]; 1 <= m <= 2048, 1 <= r <= min(256, m).
+ *   ra_rot_shift2d  d_out [n][nx][nx] = rot_shift2D of d_in by d_params[i] (alpha, sx, sy, mirror; the other fields unused): the
+ *                   kernel and grid of ra_transform_accumulate without sums, so bitwise equal to its aligned images; 2 <= nx <= 1024. */
+int  ra_sdr_mean(const float *d_images, int n, int p, int q, float *d_mean, void *hip_stream);
+int  ra_sdr_gram(const float *d_images, int n, int p, int q, const float *d_mean, int form, const float *d_proj, int k,
+                 double *d_gram, void *hip_stream);
+int  ra_sdr_project(const float *d_images, int n, int p, int q, const float *d_mean, const float *d_A, int p0, const float *d_B,
+                    int q0, float *d_U, void *hip_stream);
+int  ra_sdr_factors(const float *d_U, int n, int m, const float *d_G, int r, float *d_F, void *hip_stream);
+int  ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result *d_params, float *d_out, void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
