@@ -71,6 +71,7 @@ EXPORTED_SYMBOLS = [
     "ra_state_from_params_dev", "ra_class_fsc_fit", "ra_filter_references_dev", "ra_last_refine_count",
     "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
+    "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
 ]
 
 _lib = None
@@ -175,6 +176,11 @@ def load_library(path=None):
     L.ra_sdr_project.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
     L.ra_sdr_factors.argtypes = [vp, ci, ci, vp, ci, vp, vp]
     L.ra_rot_shift2d.argtypes = [vp, ci, ci, vp, vp, vp]
+    cf = ctypes.c_float
+    L.ra_tsne_knn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
+    L.ra_tsne_affinity.argtypes = [vp, ci, ci, cf, vp, vp]
+    L.ra_tsne_step.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, vp, vp]
+    L.ra_tsne_error.argtypes = [vp, ci, vp, vp, vp, ci, cf, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -260,6 +266,12 @@ def mpca(images, p0, q0, **kw):
     """MPCA of images [n][p][q] (sdr.mpca)."""
     from . import sdr
     return sdr.mpca(images, p0, q0, **kw)
+
+
+def tsne(X, **kw):
+    """t-SNE embedding [n][2] of X [n][d] (tsne.tsne)."""
+    from . import tsne as _tsne
+    return _tsne.tsne(X, **kw)
 
 
 def _check(rc, what):

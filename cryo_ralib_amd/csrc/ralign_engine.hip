@@ -25,6 +25,7 @@
 #include "ralign_refine.h"
 #include "ralign_ctf.h"
 #include "ralign_sdr.h"
+#include "ralign_tsne.h"
 
 using namespace ralign;
 
@@ -2828,8 +2829,8 @@ static int sdr_launch_error(const char *what, hipError_t he)
 extern "C" int ra_sdr_mean(const float *d_images, int n, int p, int q, float *d_mean, void *hip_stream)
 {
     hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 1 || p < 1 || p > 256 || q < 1 || q > 256) {
-        g_last_error = "ra_sdr_mean: need n >= 1 and 1 <= p, q <= 256";
+    if (n < 1 || p < 1 || p > 256 || q < 1 || q > (p == 1 ? 2048 : 256)) {
+        g_last_error = "ra_sdr_mean: need n >= 1 and 1 <= p, q <= 256 (p == 1: q <= 2048)";
         return RA_ERR_ARG;
     }
     if (!d_images || !d_mean) { g_last_error = "ra_sdr_mean: null argument"; return RA_ERR_ARG; }
@@ -2941,4 +2942,121 @@ extern "C" int ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result 
     }
     if (he == hipSuccess) he = hipGetLastError();
     return he == hipSuccess ? RA_OK : sdr_launch_error("ra_rot_shift2d", he);
+}
+
+// ---- t-SNE (ralign_tsne.h)
+
+extern "C" int ra_tsne_knn(const float *d_x, int n, int d, int k, int *d_idx, double *d_dist2, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 2 || n > TSNE_MAX_N || d < 1 || d > TSNE_MAX_D || k < 1 || k > std::min(n - 1, TSNE_MAX_K)) {
+        g_last_error = "ra_tsne_knn: need 2 <= n <= 262144, 1 <= d <= 2048 and 1 <= k <= min(n - 1, 301)";
+        return RA_ERR_ARG;
+    }
+    if (!d_x || !d_idx || !d_dist2) { g_last_error = "ra_tsne_knn: null argument"; return RA_ERR_ARG; }
+    TsneKnnArgs a;
+    a.x = d_x; a.n = n; a.d = d; a.k = k;
+    a.C = std::min(n - 1, k + TSNE_KNN_MARGIN);
+    a.cap = a.C + TSNE_KNN_SLACK;
+    a.idx = d_idx; a.dist2 = d_dist2;
+    const size_t lds = (size_t)16 * a.C * sizeof(double) + (size_t)16 * TSNE_KNN_TILE * sizeof(float) + (size_t)16 * a.cap * 8;
+    hipError_t he = hipFuncSetAttribute((const void *)tsne_knn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (he != hipSuccess) return sdr_launch_error("ra_tsne_knn", he);
+    float *d_nrm = nullptr;
+    he = hipMallocAsync((void **)&d_nrm, (size_t)n * sizeof(float), stream);
+    if (he != hipSuccess) return sdr_launch_error("ra_tsne_knn", he);
+    a.nrm = d_nrm;
+    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, d_nrm);
+    he = hipGetLastError();
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(tsne_knn_kernel, dim3((n + 15) / 16), dim3(TSNE_KNN_THREADS), lds, stream, a);
+        he = hipGetLastError();
+    }
+    (void)hipFreeAsync(d_nrm, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_tsne_knn", he);
+}
+
+extern "C" int ra_tsne_affinity(const double *d_dist2, int n, int k, float perplexity, double *d_pcond, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 2 || n > TSNE_MAX_N || k < 1 || k > std::min(n - 1, TSNE_MAX_K) || !(perplexity > 0.f && perplexity <= 100.f)) {
+        g_last_error = "ra_tsne_affinity: need 2 <= n <= 262144, 1 <= k <= min(n - 1, 301) and 0 < perplexity <= 100";
+        return RA_ERR_ARG;
+    }
+    if (!d_dist2 || !d_pcond) { g_last_error = "ra_tsne_affinity: null argument"; return RA_ERR_ARG; }
+    hipLaunchKernelGGL(tsne_affinity_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, d_dist2, n, k, log((double)perplexity), d_pcond);
+    hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_tsne_affinity", he);
+}
+
+// repulsion partials, then the update kernel in the given mode, then (if d_stats) the statistics
+static int tsne_run(const char *what, const float *d_y, float *d_y_out, float *d_update, float *d_gains, float *d_grad, int n,
+                    const int *d_indptr, const int *d_indices, const float *d_p, int nnz, float exaggeration, float momentum,
+                    float learning_rate, int mode, double *d_stats, hipStream_t stream)
+{
+    const int seg = tsne_segment(n), nseg = (n + seg - 1) / seg, nrb = (n + TSNE_REP_ROWS - 1) / TSNE_REP_ROWS;
+    const int nub = (n + TSNE_UPD_THREADS - 1) / TSNE_UPD_THREADS, nz = nseg * nrb;
+    const size_t part_bytes = (size_t)nseg * n * sizeof(float2), z_bytes = (size_t)nz * sizeof(double);
+    const size_t st_bytes = d_stats ? (size_t)nub * 2 * sizeof(double) : 0;
+    unsigned char *scratch = nullptr;
+    hipError_t he = hipMallocAsync((void **)&scratch, part_bytes + z_bytes + st_bytes, stream);
+    if (he != hipSuccess) return sdr_launch_error(what, he);
+    float2 *part = (float2 *)scratch;
+    double *zpart = (double *)(scratch + part_bytes), *st = d_stats ? (double *)(scratch + part_bytes + z_bytes) : nullptr;
+    hipLaunchKernelGGL(tsne_repulsion_kernel, dim3(nrb, nseg), dim3(TSNE_REP_THREADS), 0, stream, (const float2 *)d_y, n, seg, part, zpart);
+    he = hipGetLastError();
+    if (he == hipSuccess) {
+        TsneUpdateArgs u;
+        u.y = (const float2 *)d_y; u.y_out = (float2 *)d_y_out; u.update = (float2 *)d_update; u.gains = (float2 *)d_gains;
+        u.grad = (float2 *)d_grad; u.part = part; u.zpart = zpart; u.indptr = d_indptr; u.indices = d_indices; u.p = d_p;
+        u.n = n; u.nseg = nseg; u.nz = nz; u.nnz = nnz; u.mode = mode;
+        u.exaggeration = exaggeration; u.momentum = momentum; u.learning_rate = learning_rate; u.stats_part = st;
+        hipLaunchKernelGGL(tsne_update_kernel, dim3(nub), dim3(TSNE_UPD_THREADS), 0, stream, u);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess && d_stats) {
+        hipLaunchKernelGGL(tsne_stats_kernel, dim3(1), dim3(256), 0, stream, st, nub, d_stats);
+        he = hipGetLastError();
+    }
+    (void)hipFreeAsync(scratch, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error(what, he);
+}
+
+static bool tsne_csr_ok(const char *what, int n, int nnz, const int *d_indptr, const int *d_indices, const float *d_p)
+{
+    if (n < 2 || n > TSNE_MAX_N || nnz < 0 || (long long)nnz > 2LL * n * TSNE_MAX_K) {
+        g_last_error = std::string(what) + ": need 2 <= n <= 262144 and 0 <= nnz <= 2 n 301";
+        return false;
+    }
+    if (!d_indptr || (nnz > 0 && (!d_indices || !d_p))) { g_last_error = std::string(what) + ": null argument"; return false; }
+    return true;
+}
+
+extern "C" int ra_tsne_step(const float *d_y, float *d_y_out, float *d_update, float *d_gains, int n, const int *d_indptr,
+                            const int *d_indices, const float *d_p, int nnz, float exaggeration, float momentum, float learning_rate,
+                            double *d_stats, void *hip_stream)
+{
+    if (!tsne_csr_ok("ra_tsne_step", n, nnz, d_indptr, d_indices, d_p)) return RA_ERR_ARG;
+    if (!d_y || !d_y_out || !d_update || !d_gains || d_y_out == d_y) {
+        g_last_error = "ra_tsne_step: null argument, or d_y_out == d_y (the step reads every y_j while it writes)";
+        return RA_ERR_ARG;
+    }
+    if (!std::isfinite(exaggeration) || !std::isfinite(momentum) || !std::isfinite(learning_rate) || !(learning_rate > 0.f)) {
+        g_last_error = "ra_tsne_step: need finite exaggeration and momentum and a finite learning rate > 0";
+        return RA_ERR_ARG;
+    }
+    return tsne_run("ra_tsne_step", d_y, d_y_out, d_update, d_gains, nullptr, n, d_indptr, d_indices, d_p, nnz, exaggeration, momentum,
+                    learning_rate, 0, d_stats, (hipStream_t)hip_stream);
+}
+
+extern "C" int ra_tsne_error(const float *d_y, int n, const int *d_indptr, const int *d_indices, const float *d_p, int nnz,
+                             float exaggeration, float *d_grad, double *d_stats, void *hip_stream)
+{
+    if (!tsne_csr_ok("ra_tsne_error", n, nnz, d_indptr, d_indices, d_p)) return RA_ERR_ARG;
+    if (!d_y || (!d_grad && !d_stats) || !std::isfinite(exaggeration)) {
+        g_last_error = "ra_tsne_error: null embedding, neither gradient nor statistics asked for, or a non-finite exaggeration";
+        return RA_ERR_ARG;
+    }
+    return tsne_run("ra_tsne_error", d_y, nullptr, nullptr, nullptr, d_grad, n, d_indptr, d_indices, d_p, nnz, exaggeration, 0.f, 0.f, 1,
+                    d_stats, (hipStream_t)hip_stream);
 }

@@ -1,0 +1,409 @@
+// t-SNE of factors X [n][d] (scikit-learn 1.7 TSNE, method="barnes_hut", angle=0: sparse kNN affinities, exact repulsion).
+//
+//   tsne_sqnorm_kernel      |x_i|^2 per row (double sum, rounded once), for the Gram distances of the kNN.
+//   tsne_knn_kernel         exact kNN: Gram distance tiles |x_i|^2 + |x_j|^2 - 2 x_i.x_j on v_mfma_f32_16x16x4_f32, a streaming
+//                           per-row top-C selection in LDS (C = min(n - 1, k + TSNE_KNN_MARGIN)), then the C survivors re-ranked
+//                           by squared distances computed in double from x_i - x_j; writes the k best by (distance, index).
+//   tsne_affinity_kernel    sklearn's _binary_search_perplexity on the k neighbours of a row (one wave per row, double).
+//   tsne_repulsion_kernel   all-pairs partials over one block of rows x one segment of columns: sum_j w_ij^2 (y_i - y_j) per row
+//                           and sum w_ij over the block (self pairs included, removed exactly by the update), w = 1 / (1 + d^2).
+//   tsne_update_kernel      Z from the block partials, the row's repulsion from its segment partials, the sparse attraction over
+//                           its CSR row, the gradient, then sklearn's gains / momentum update (or the gradient alone).
+//   tsne_stats_kernel       KL error and squared gradient norm from the update's per-workgroup partials.
+//
+// Determinism: no atomics on floating-point data. Every sum has an order fixed by n alone: the segment length, the row blocks
+// and the reduction trees depend on n only, never on the device or on how the grid is scheduled. The kNN list's append order
+// varies (an LDS integer counter), but only its set is used: every cut is by the total order (distance, index).
+// Indices read from data (CSR columns, row pointers) are clamped before they address anything.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+namespace ralign {
+
+#define TSNE_KNN_THREADS 256        // 4 waves; the workgroup owns 16 query rows, a wave 16 candidate columns of each tile
+#define TSNE_KNN_TILE 64            // candidate columns per tile
+#define TSNE_KNN_MARGIN 32          // survivors kept beyond k for the double re-rank
+#define TSNE_KNN_SLACK 256          // list capacity beyond C: a compaction every >= 192 accepted candidates
+#define TSNE_MAX_K 301              // k = int(3 perplexity + 1) at perplexity 100
+#define TSNE_MAX_N 262144
+#define TSNE_MAX_D 2048
+
+#define TSNE_REP_THREADS 256
+#define TSNE_REP_R 4                                   // rows per lane
+#define TSNE_REP_ROWS (TSNE_REP_THREADS * TSNE_REP_R)  // rows per workgroup
+#define TSNE_REP_CHUNK 512                             // columns staged in LDS at a time
+#define TSNE_REP_MAXSEG 64                             // segments per row at most (bounds the partial buffer)
+#define TSNE_UPD_THREADS 256
+
+// the column segment length of the repulsion for n points: a multiple of TSNE_REP_ROWS, at most TSNE_REP_MAXSEG segments
+__host__ __device__ inline int tsne_segment(int n)
+{
+    const int per = (n + TSNE_REP_MAXSEG * TSNE_REP_ROWS - 1) / (TSNE_REP_MAXSEG * TSNE_REP_ROWS);
+    return TSNE_REP_ROWS * (per > 0 ? per : 1);
+}
+
+__device__ __forceinline__ const float *x_row_or_null(const float *x, int i, int n, int d)
+{
+    return i < n ? x + (size_t)i * d : nullptr;
+}
+
+__device__ __forceinline__ float tsne_not_nan(float v) { return v != v ? __builtin_inff() : v; }
+
+__device__ __forceinline__ bool tsne_key_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
+
+__device__ __forceinline__ bool tsne_key_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
+
+// fixed-order sum of v over the workgroup (blockDim.x = NT, a power of two); every thread gets the result
+template <int NT>
+__device__ __forceinline__ double tsne_block_sum(double v, double *red)
+{
+    red[threadIdx.x] = v;
+    __syncthreads();
+#pragma unroll
+    for (int s = NT / 2; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+__global__ __launch_bounds__(256) void tsne_sqnorm_kernel(const float *__restrict__ x, int n, int d, float *__restrict__ nrm)
+{
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float *xi = x + (size_t)i * d;
+    double s = 0.0;
+    for (int t = 0; t < d; t++) s += (double)xi[t] * (double)xi[t];
+    nrm[i] = (float)s;
+}
+
+struct TsneKnnArgs {
+    const float *x, *nrm;
+    int n, d, k, C, cap;            // C survivors per row, cap list capacity (C + TSNE_KNN_SLACK)
+    int *idx;                       // [n][k]
+    double *dist2;                  // [n][k]
+};
+
+// LDS: tile [16][64] float, list distances [16][cap] float, list indices [16][cap] int, exact distances [16][C] double
+__global__ __launch_bounds__(TSNE_KNN_THREADS) void tsne_knn_kernel(TsneKnnArgs a)
+{
+    extern __shared__ __align__(16) unsigned char tsne_smem[];
+    double *ex = (double *)tsne_smem;
+    float *tile = (float *)(ex + 16 * a.C);
+    float *ld = tile + 16 * TSNE_KNN_TILE;
+    int *li = (int *)(ld + 16 * a.cap);
+    __shared__ int cnt[16], full[16], thr_i[16];
+    __shared__ float thr_d[16];
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
+    const int i0 = blockIdx.x * 16;
+    const int row = tid >> 4, sub = tid & 15, gi = i0 + row;   // selection: 16 lanes per query row
+    if (tid < 16) { cnt[tid] = 0; full[tid] = 0; thr_d[tid] = __builtin_inff(); thr_i[tid] = 0; }
+    __syncthreads();
+
+    // keep the C smallest (distance, index) of the rows whose list holds more than `limit`; workgroup-uniform
+    auto compact = [&](int limit) {
+        const int c = cnt[row];
+        const bool act = gi < a.n && c > limit;
+        float *rd = ld + row * a.cap;
+        int *ri = li + row * a.cap;
+        if (act) {
+            for (int e = sub; e < c; e += 16) {
+                const float de = rd[e];
+                const int ie = ri[e];
+                int rank = 0;
+                for (int f = 0; f < c; f++) rank += tsne_key_less(rd[f], ri[f], de, ie) ? 1 : 0;
+                if (rank == a.C - 1) { thr_d[row] = de; thr_i[row] = ie; }
+            }
+        }
+        __syncthreads();
+        if (act) {
+            const float td = thr_d[row];
+            const int ti = thr_i[row];
+            int base = 0;
+            // in-place stream compaction, 16 entries at a time: all lanes of the row read their entry before any write, and
+            // every write lands below the next chunk
+            for (int c0 = 0; c0 < c; c0 += 16) {
+                const int e = c0 + sub;
+                float dv = 0.f;
+                int iv = 0;
+                bool keep = false;
+                if (e < c) { dv = rd[e]; iv = ri[e]; keep = !tsne_key_less(td, ti, dv, iv); }
+                const unsigned long long b = __ballot(keep);
+                const unsigned grp = (unsigned)(b >> (lane & 48)) & 0xffffu;
+                const int pre = __popc(grp & ((1u << sub) - 1u));
+                if (keep) { rd[base + pre] = dv; ri[base + pre] = iv; }
+                base += __popc(grp);
+            }
+            if (sub == 0) { cnt[row] = base; full[row] = 1; }
+        }
+        __syncthreads();
+    };
+
+    const int qi = i0 + lr;
+    const float *xq = x_row_or_null(a.x, qi, a.n, a.d);
+    for (int j0 = 0; j0 < a.n; j0 += TSNE_KNN_TILE) {
+        // Gram tile: rows i0 .. i0 + 15 x columns j0 + 16 wave .. + 15
+        const int cj = j0 + wave * 16 + lr;
+        const float *xc = x_row_or_null(a.x, cj, a.n, a.d);
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int k0 = 0; k0 < a.d; k0 += 4) {
+            const int kk = k0 + lk;
+            const float av = (xq && kk < a.d) ? xq[kk] : 0.f;
+            const float bv = (xc && kk < a.d) ? xc[kk] : 0.f;
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+        }
+        const float nc = cj < a.n ? a.nrm[cj] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int orow = lk * 4 + r;
+            const float nq = i0 + orow < a.n ? a.nrm[i0 + orow] : 0.f;
+            tile[orow * TSNE_KNN_TILE + wave * 16 + lr] = tsne_not_nan(nq + nc - 2.f * acc[r]);
+        }
+        __syncthreads();
+        if (gi < a.n) {
+            const bool fl = full[row] != 0;
+            const float td = thr_d[row];
+#pragma unroll
+            for (int m = 0; m < TSNE_KNN_TILE / 16; m++) {
+                const int col = sub + 16 * m, j = j0 + col;
+                if (j >= a.n || j == gi) continue;
+                const float dv = tile[row * TSNE_KNN_TILE + col];
+                // columns arrive in increasing index order, so a distance equal to the cut loses to the kept entry
+                if (!fl || dv < td) {
+                    const int pos = atomicAdd(&cnt[row], 1);
+                    ld[row * a.cap + pos] = dv;
+                    li[row * a.cap + pos] = j;
+                }
+            }
+        }
+        __syncthreads();
+        bool over = false;
+#pragma unroll
+        for (int r = 0; r < 16; r++) over |= cnt[r] > a.cap - TSNE_KNN_TILE;
+        if (over) compact(a.cap - TSNE_KNN_TILE);
+    }
+    compact(a.C);
+
+    // re-rank the survivors by the exact squared distance (double, from x_i - x_j)
+    const int c = gi < a.n ? cnt[row] : 0;
+    const float *xi = a.x + (size_t)min(gi, a.n - 1) * a.d;
+    double *rx = ex + row * a.C;
+    const int *ri = li + row * a.cap;
+    for (int e = sub; e < c; e += 16) {
+        const float *xj = a.x + (size_t)ri[e] * a.d;
+        double s = 0.0;
+        for (int t = 0; t < a.d; t++) {
+            const double df = (double)xi[t] - (double)xj[t];
+            s += df * df;
+        }
+        rx[e] = s != s ? __builtin_inf() : s;
+    }
+    __syncthreads();
+    for (int e = sub; e < c; e += 16) {
+        const double de = rx[e];
+        const int ie = ri[e];
+        int rank = 0;
+        for (int f = 0; f < c; f++) rank += tsne_key_less(rx[f], ri[f], de, ie) ? 1 : 0;
+        if (rank < a.k) {
+            a.idx[(size_t)gi * a.k + rank] = ie;
+            a.dist2[(size_t)gi * a.k + rank] = de;
+        }
+    }
+}
+
+// one wave per row: sklearn _binary_search_perplexity (_utils.pyx) with the row's k squared distances rounded to float, as
+// sklearn hands them over; sums by a fixed butterfly, so every lane holds the same bits
+__device__ __forceinline__ double tsne_wave_sum(double v)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void tsne_affinity_kernel(const double *__restrict__ dist2, int n, int k, double desired_entropy,
+                                                            double *__restrict__ pcond)
+{
+    const int lane = threadIdx.x & 63, i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= n) return;
+    constexpr int M = (TSNE_MAX_K + 63) / 64;
+    double dd[M], pp[M];
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        const int j = lane + 64 * m;
+        dd[m] = j < k ? (double)(float)dist2[(size_t)i * k + j] : 0.0;
+        pp[m] = 0.0;
+    }
+    double beta = 1.0, beta_min = -__builtin_inf(), beta_max = __builtin_inf();
+    const double tol = (double)1e-5f, floor_sum = (double)1e-8f;
+    for (int step = 0; step < 100; step++) {
+        double s = 0.0;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            pp[m] = lane + 64 * m < k ? exp(-dd[m] * beta) : 0.0;
+            s += pp[m];
+        }
+        double sum_p = tsne_wave_sum(s);
+        if (sum_p == 0.0) sum_p = floor_sum;
+        double sd = 0.0;
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            pp[m] /= sum_p;
+            sd += dd[m] * pp[m];
+        }
+        const double sum_dp = tsne_wave_sum(sd);
+        const double diff = log(sum_p) + beta * sum_dp - desired_entropy;
+        if (fabs(diff) <= tol) break;       // NaN distances make diff NaN: the search runs its 100 steps and ends
+        if (diff > 0.0) {
+            beta_min = beta;
+            beta = beta_max == __builtin_inf() ? beta * 2.0 : (beta + beta_max) / 2.0;
+        } else {
+            beta_max = beta;
+            beta = beta_min == -__builtin_inf() ? beta / 2.0 : (beta + beta_min) / 2.0;
+        }
+    }
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        const int j = lane + 64 * m;
+        if (j < k) pcond[(size_t)i * k + j] = pp[m];
+    }
+}
+
+// grid (row blocks, segments). Partials part[s][i] = sum over segment s of w^2 (y_i - y_j); zpart[s * nrb + rb] = sum of w over
+// the block's rows and the segment's columns (self pairs included: one each, 1.0 exactly).
+__global__ __launch_bounds__(TSNE_REP_THREADS) void tsne_repulsion_kernel(const float2 *__restrict__ y, int n, int seg,
+                                                                          float2 *__restrict__ part, double *__restrict__ zpart)
+{
+    __shared__ float2 ys[TSNE_REP_CHUNK];
+    __shared__ double red[TSNE_REP_THREADS];
+    const int rb = blockIdx.x, s = blockIdx.y, nrb = gridDim.x, tid = threadIdx.x;
+    float yx[TSNE_REP_R], yy[TSNE_REP_R], fx[TSNE_REP_R], fy[TSNE_REP_R], z[TSNE_REP_R];
+#pragma unroll
+    for (int r = 0; r < TSNE_REP_R; r++) {
+        const int i = rb * TSNE_REP_ROWS + r * TSNE_REP_THREADS + tid;
+        const float2 v = i < n ? y[i] : float2{0.f, 0.f};
+        yx[r] = v.x; yy[r] = v.y; fx[r] = 0.f; fy[r] = 0.f; z[r] = 0.f;
+    }
+    const int j0 = s * seg, j1 = min(n, j0 + seg);
+    for (int jt = j0; jt < j1; jt += TSNE_REP_CHUNK) {
+        const int c = min(TSNE_REP_CHUNK, j1 - jt);
+        __syncthreads();
+        for (int t = tid; t < c; t += TSNE_REP_THREADS) ys[t] = y[jt + t];
+        __syncthreads();
+#pragma unroll 4
+        for (int j = 0; j < c; j++) {
+            const float2 v = ys[j];
+#pragma unroll
+            for (int r = 0; r < TSNE_REP_R; r++) {
+                const float dx = yx[r] - v.x, dy = yy[r] - v.y;
+                const float w = __builtin_amdgcn_rcpf(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, 1.f)));
+                const float w2 = w * w;
+                z[r] += w;
+                fx[r] = __builtin_fmaf(w2, dx, fx[r]);
+                fy[r] = __builtin_fmaf(w2, dy, fy[r]);
+            }
+        }
+    }
+    double zs = 0.0;
+#pragma unroll
+    for (int r = 0; r < TSNE_REP_R; r++) {
+        const int i = rb * TSNE_REP_ROWS + r * TSNE_REP_THREADS + tid;
+        if (i < n) {
+            part[(size_t)s * n + i] = float2{fx[r], fy[r]};
+            zs += (double)z[r];
+        }
+    }
+    zs = tsne_block_sum<TSNE_REP_THREADS>(zs, red);
+    if (tid == 0) zpart[s * nrb + rb] = zs;
+}
+
+struct TsneUpdateArgs {
+    const float2 *y;                // current embedding [n]
+    float2 *y_out, *update, *gains; // mode 0: next embedding, sklearn's update and gains (in place)
+    float2 *grad;                   // mode 1: the gradient (may be null)
+    const float2 *part;             // [nseg][n]
+    const double *zpart;            // [nz]
+    const int *indptr, *indices;    // CSR of P, nnz entries
+    const float *p;
+    int n, nseg, nz, nnz, mode;
+    float exaggeration, momentum, learning_rate;
+    double *stats_part;             // [gridDim.x][2]: KL error, squared gradient norm (null: not computed)
+};
+
+__global__ __launch_bounds__(TSNE_UPD_THREADS) void tsne_update_kernel(TsneUpdateArgs a)
+{
+    __shared__ double red[TSNE_UPD_THREADS];
+    const int tid = threadIdx.x, i = blockIdx.x * TSNE_UPD_THREADS + tid;
+    double zs = 0.0;
+    for (int t = tid; t < a.nz; t += TSNE_UPD_THREADS) zs += a.zpart[t];
+    // every workgroup forms the same Z; the n self pairs come out exactly (each added 1.0); sklearn floors sum_Q at eps
+    const double Z = fmax(tsne_block_sum<TSNE_UPD_THREADS>(zs, red) - (double)a.n, 2.220446049250313e-16);
+    double err = 0.0, gn = 0.0;
+    if (i < a.n) {
+        double rx = 0.0, ry = 0.0;
+        for (int s = 0; s < a.nseg; s++) {
+            const float2 v = a.part[(size_t)s * a.n + i];
+            rx += (double)v.x;
+            ry += (double)v.y;
+        }
+        const float2 yi = a.y[i];
+        const int e0 = min(max(a.indptr[i], 0), a.nnz), e1 = min(max(a.indptr[i + 1], e0), a.nnz);
+        float ax = 0.f, ay = 0.f;
+        const bool want = a.stats_part != nullptr;
+        const float tiny = 1.17549435e-38f;
+        for (int e = e0; e < e1; e++) {
+            const int j = a.indices[e];
+            if ((unsigned)j >= (unsigned)a.n) continue;
+            const float2 yj = a.y[j];
+            const float dx = yi.x - yj.x, dy = yi.y - yj.y;
+            const float w = 1.f / (1.f + (dx * dx + dy * dy));
+            const float pij = a.p[e] * a.exaggeration;
+            const float f = pij * w;
+            ax += f * dx;
+            ay += f * dy;
+            if (want) {
+                const double q = (double)w / Z;
+                err += (double)pij * log(fmax((double)pij, (double)tiny) / fmax(q, (double)tiny));
+            }
+        }
+        float gx = (float)((double)ax - rx / Z) * 4.f, gy = (float)((double)ay - ry / Z) * 4.f;
+        if (a.mode == 0) {
+            float2 u = a.update[i], g = a.gains[i];
+            g.x = u.x * gx < 0.f ? g.x + 0.2f : g.x * 0.8f;
+            g.y = u.y * gy < 0.f ? g.y + 0.2f : g.y * 0.8f;
+            g.x = fmaxf(g.x, 0.01f);
+            g.y = fmaxf(g.y, 0.01f);
+            gx *= g.x;
+            gy *= g.y;
+            u.x = a.momentum * u.x - a.learning_rate * gx;
+            u.y = a.momentum * u.y - a.learning_rate * gy;
+            a.gains[i] = g;
+            a.update[i] = u;
+            a.y_out[i] = float2{yi.x + u.x, yi.y + u.y};
+        } else if (a.grad) {
+            a.grad[i] = float2{gx, gy};
+        }
+        gn = (double)gx * gx + (double)gy * gy;
+    }
+    if (a.stats_part) {
+        err = tsne_block_sum<TSNE_UPD_THREADS>(err, red);
+        gn = tsne_block_sum<TSNE_UPD_THREADS>(gn, red);
+        if (tid == 0) { a.stats_part[2 * blockIdx.x] = err; a.stats_part[2 * blockIdx.x + 1] = gn; }
+    }
+}
+
+__global__ __launch_bounds__(256) void tsne_stats_kernel(const double *__restrict__ part, int nb, double *__restrict__ stats)
+{
+    __shared__ double red[256];
+    double e = 0.0, g = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 256) { e += part[2 * b]; g += part[2 * b + 1]; }
+    e = tsne_block_sum<256>(e, red);
+    g = tsne_block_sum<256>(g, red);
+    if (threadIdx.x == 0) { stats[0] = e; stats[1] = g; }
+}
+
+}  // namespace ralign

@@ -311,7 +311,8 @@ int  ra_phase_flip(float *d_images, int n, int nx, const float *h_ctf, int pad, 
  * and allocates and frees its scratch on that stream, as ra_phase_flip does.  Images are [n][p][q] float32, centred on load
  * (x - mean in fp32) where a mean is given.  Results are bitwise reproducible call to call.  RA_ERR_ARG for anything outside the
  * documented domain; nothing is launched then.
- *   ra_sdr_mean     d_mean[p q] = per-pixel mean (double sums in a fixed order, rounded once); 1 <= p, q <= 256, n >= 1.
+ *   ra_sdr_mean     d_mean[p q] = per-pixel mean (double sums in a fixed order, rounded once); 1 <= p, q <= 256, n >= 1
+ *                   (p == 1: q <= 2048, the mean of [n][q] factors).
  *   ra_sdr_gram     d_gram (double, exactly symmetric):  form 0: sum X_i^T X_i (q x q);  form 1: sum (X_i P)(X_i P)^T (p x p),
  *                   d_proj P [q][k];  form 2: sum (P^T X_i)^T (P^T X_i) (q x q), d_proj P [p][k].  d_mean NULL: no centring.
  *                   1 <= p, q <= 256 (form 0 with p == 1: q <= 2048, the second stage's n x m matrix); forms 1 / 2: 1 <= k <= 64
@@ -328,6 +329,31 @@ int  ra_sdr_project(const float *d_images, int n, int p, int q, const float *d_m
                     int q0, float *d_U, void *hip_stream);
 int  ra_sdr_factors(const float *d_U, int n, int m, const float *d_G, int r, float *d_F, void *hip_stream);
 int  ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result *d_params, float *d_out, void *hip_stream);
+
+/* t-SNE (scikit-learn 1.7 TSNE with method="barnes_hut", angle=0, two output dimensions) of X [n][d] in device memory, without an
+ * engine.  Pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL =
+ * default stream) and allocates and frees its scratch on that stream, as ra_phase_flip does.  Results are bitwise reproducible
+ * call to call and across streams (no floating-point atomics; every sum in an order fixed by n).  RA_ERR_ARG for anything outside
+ * the documented domain; nothing is launched then.  The optimisation loop around ra_tsne_step is cryo_ralib_amd/tsne.py.
+ *   ra_tsne_knn       d_idx [n][k], d_dist2 [n][k]: the k nearest neighbours of every row of d_x [n][d] (float32), itself
+ *                     excluded, ordered by (squared euclidean distance, index); distances computed in double from x_i - x_j.
+ *                     2 <= n <= 262144, 1 <= d <= 2048, 1 <= k <= min(n - 1, 301).
+ *   ra_tsne_affinity  d_pcond [n][k] (double): sklearn's _binary_search_perplexity of each row of d_dist2 (rounded to float as
+ *                     sklearn does) for the given perplexity, 0 < perplexity <= 100.
+ *   ra_tsne_step      one iteration of sklearn's _gradient_descent: gradient of the KL divergence at d_y [n][2] with the CSR
+ *                     affinities (d_indptr [n + 1], d_indices, d_p [nnz], float32) times exaggeration and the exact all-pairs
+ *                     repulsion, then gains (d_gains [n][2]), update (d_update [n][2]) and d_y_out = d_y + update
+ *                     (d_y_out != d_y).  d_stats (may be NULL): [0] the KL error at d_y, [1] the squared norm of the gradient
+ *                     times the gains, as sklearn checks them.  0 <= nnz <= 2 n 301; column indices outside 0 .. n - 1 are skipped.
+ *   ra_tsne_error     the same gradient at d_y without an update: d_grad [n][2] (may be NULL), d_stats [0] KL error, [1] squared
+ *                     gradient norm (may be NULL; not both). */
+int  ra_tsne_knn(const float *d_x, int n, int d, int k, int *d_idx, double *d_dist2, void *hip_stream);
+int  ra_tsne_affinity(const double *d_dist2, int n, int k, float perplexity, double *d_pcond, void *hip_stream);
+int  ra_tsne_step(const float *d_y, float *d_y_out, float *d_update, float *d_gains, int n, const int *d_indptr, const int *d_indices,
+                  const float *d_p, int nnz, float exaggeration, float momentum, float learning_rate, double *d_stats,
+                  void *hip_stream);
+int  ra_tsne_error(const float *d_y, int n, const int *d_indptr, const int *d_indices, const float *d_p, int nnz, float exaggeration,
+                   float *d_grad, double *d_stats, void *hip_stream);
 
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
