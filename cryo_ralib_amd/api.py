@@ -72,6 +72,7 @@ EXPORTED_SYMBOLS = [
     "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
+    "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
 ]
 
 _lib = None
@@ -181,6 +182,11 @@ def load_library(path=None):
     L.ra_tsne_affinity.argtypes = [vp, ci, ci, cf, vp, vp]
     L.ra_tsne_step.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, vp, vp]
     L.ra_tsne_error.argtypes = [vp, ci, vp, vp, vp, ci, cf, vp, vp, vp]
+    L.ra_kmeans_sqnorm.argtypes = [vp, ci, ci, vp, vp]
+    L.ra_kmeans_labels.argtypes = [vp, ci, ci, vp, vp, ci, vp, ci, vp, vp]
+    L.ra_kmeans_lloyd.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, vp]
+    L.ra_kmeans_search.argtypes = [vp, ci, vp, ci, vp, vp]
+    L.ra_kmeans_seed.argtypes = [vp, ci, ci, vp, ci, vp, ci, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -272,6 +278,12 @@ def tsne(X, **kw):
     """t-SNE embedding [n][2] of X [n][d] (tsne.tsne)."""
     from . import tsne as _tsne
     return _tsne.tsne(X, **kw)
+
+
+def kmeans(X, n_clusters, **kw):
+    """k-means of X [n][d] (kmeans.kmeans): KMeansResult with labels, centers, inertia, n_iter, init_indices."""
+    from . import kmeans as _kmeans
+    return _kmeans.kmeans(X, n_clusters, **kw)
 
 
 def _check(rc, what):

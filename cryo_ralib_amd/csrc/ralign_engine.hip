@@ -26,6 +26,7 @@
 #include "ralign_ctf.h"
 #include "ralign_sdr.h"
 #include "ralign_tsne.h"
+#include "ralign_kmeans.h"
 
 using namespace ralign;
 
@@ -3059,4 +3060,205 @@ extern "C" int ra_tsne_error(const float *d_y, int n, const int *d_indptr, const
     }
     return tsne_run("ra_tsne_error", d_y, nullptr, nullptr, nullptr, d_grad, n, d_indptr, d_indices, d_p, nnz, exaggeration, 0.f, 0.f, 1,
                     d_stats, (hipStream_t)hip_stream);
+}
+
+// ---- k-means (ralign_kmeans.h)
+
+static bool km_shape_ok(const char *what, int n, int d, int k)
+{
+    if (n < 1 || n > KM_MAX_N || d < 1 || d > KM_MAX_D || k < 1 || k > std::min(n, KM_MAX_K)) {
+        g_last_error = std::string(what) + ": need 1 <= n <= 4194304, 1 <= d <= 2048 and 1 <= k <= min(n, 256)";
+        return false;
+    }
+    return true;
+}
+
+// carves aligned pieces out of one stream-ordered allocation
+struct KmScratch {
+    size_t off = 0;
+    unsigned char *base = nullptr;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+    template <class T> T *at(size_t o) { return (T *)(base + o); }
+};
+
+extern "C" int ra_kmeans_sqnorm(const float *d_x, int n, int d, float *d_nrm, void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_sqnorm", n, d, 1)) return RA_ERR_ARG;
+    if (!d_x || !d_nrm) { g_last_error = "ra_kmeans_sqnorm: null argument"; return RA_ERR_ARG; }
+    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, d_x, n, d, d_nrm);
+    hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_sqnorm", he);
+}
+
+// the E-step: labels (in place, changed counted into d_changed if non-null) and the double distance of each point to its centre.
+// cf [k][d] / cnrm [k]: scratch of the f32 copy (d > KM_SMALL_D only)
+static hipError_t km_assign(const float *x, int n, int d, const float *nrm, const double *c, int k, int *labels, double *dist,
+                            int *changed, float *cf, float *cnrm, hipStream_t stream)
+{
+    if (d <= KM_SMALL_D) {
+        hipLaunchKernelGGL(km_assign_small_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, n, d, c, k, labels, dist, changed);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(km_prep_kernel, dim3(k), dim3(256), 0, stream, c, d, cf, cnrm);
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return he;
+    KmAssignArgs a;
+    a.x = x; a.nrm = nrm; a.c = c; a.cf = cf; a.cnrm = cnrm; a.n = n; a.d = d; a.k = k;
+    a.labels = labels; a.dist = dist; a.changed = changed;
+    const dim3 grid((n + KM_ROWS - 1) / KM_ROWS), block(64 * KM_WAVES);
+    const int nt = (k + 15) / 16;
+    if (nt <= 1) hipLaunchKernelGGL(km_assign_mfma_kernel<1>, grid, block, 0, stream, a);
+    else if (nt <= 2) hipLaunchKernelGGL(km_assign_mfma_kernel<2>, grid, block, 0, stream, a);
+    else if (nt <= 4) hipLaunchKernelGGL(km_assign_mfma_kernel<4>, grid, block, 0, stream, a);
+    else if (nt <= 8) hipLaunchKernelGGL(km_assign_mfma_kernel<8>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(km_assign_mfma_kernel<16>, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+extern "C" int ra_kmeans_labels(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, int *d_labels,
+                                int assign, double *d_inertia, void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_labels", n, d, k)) return RA_ERR_ARG;
+    if (!d_x || !d_centers || !d_labels || (!assign && !d_inertia)) {
+        g_last_error = "ra_kmeans_labels: null argument, or neither assignment nor inertia asked for";
+        return RA_ERR_ARG;
+    }
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + 255) / 256;
+    KmScratch S;
+    const size_t o_dist = S.take((size_t)n * 8), o_part = S.take((size_t)nb * 8);
+    const bool big = d > KM_SMALL_D;
+    const size_t o_cf = S.take(big ? (size_t)k * d * 4 : 0), o_cn = S.take(big ? (size_t)k * 4 : 0);
+    const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
+    hipError_t he = hipMallocAsync((void **)&S.base, S.off, stream);
+    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_labels", he);
+    double *dist = S.at<double>(o_dist);
+    const float *nrm = d_nrm;
+    if (big && !d_nrm) {
+        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
+        he = hipGetLastError();
+        nrm = S.at<float>(o_nrm);
+    }
+    if (he == hipSuccess) {
+        if (assign) {
+            he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, nullptr, S.at<float>(o_cf), S.at<float>(o_cn), stream);
+        } else {
+            hipLaunchKernelGGL(km_point_dist_kernel, dim3(big ? (n + 3) / 4 : nb), dim3(256), 0, stream, d_x, n, d, d_centers, k, d_labels, dist);
+            he = hipGetLastError();
+        }
+    }
+    if (he == hipSuccess && d_inertia) {
+        hipLaunchKernelGGL(km_block_sum_kernel, dim3(nb), dim3(256), 0, stream, dist, n, S.at<double>(o_part));
+        he = hipGetLastError();
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(km_final_sum_kernel, dim3(1), dim3(256), 0, stream, S.at<double>(o_part), nb, d_inertia);
+            he = hipGetLastError();
+        }
+    }
+    (void)hipFreeAsync(S.base, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_labels", he);
+}
+
+extern "C" int ra_kmeans_lloyd(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, double *d_centers_new,
+                               int *d_labels, double *d_stats, void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_lloyd", n, d, k)) return RA_ERR_ARG;
+    if (!d_x || !d_centers || !d_centers_new || !d_labels || !d_stats || d_centers_new == d_centers) {
+        g_last_error = "ra_kmeans_lloyd: null argument, or d_centers_new == d_centers";
+        return RA_ERR_ARG;
+    }
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, L = km_run_len(n), rmax = (n + L - 1) / L + k;
+    const bool big = d > KM_SMALL_D;
+    KmScratch S;
+    const size_t o_dist = S.take((size_t)n * 8), o_ints = S.take(2 * 4), o_bcnt = S.take((size_t)nb * k * 4);
+    const size_t o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4), o_run0 = S.take((size_t)(k + 1) * 4);
+    const size_t o_mem = S.take((size_t)n * 4), o_part = S.take((size_t)rmax * d * 8), o_sums = S.take((size_t)k * d * 8);
+    const size_t o_wt = S.take((size_t)k * 8), o_shift = S.take((size_t)k * 8);
+    const size_t o_cf = S.take(big ? (size_t)k * d * 4 : 0), o_cn = S.take(big ? (size_t)k * 4 : 0);
+    const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
+    hipError_t he = hipMallocAsync((void **)&S.base, S.off, stream);
+    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_lloyd", he);
+    int *ints = S.at<int>(o_ints), *bcnt = S.at<int>(o_bcnt), *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start);
+    int *run0 = S.at<int>(o_run0), *mem = S.at<int>(o_mem);
+    double *dist = S.at<double>(o_dist), *part = S.at<double>(o_part), *sums = S.at<double>(o_sums), *wt = S.at<double>(o_wt);
+    double *shift = S.at<double>(o_shift);
+    const float *nrm = d_nrm;
+    he = hipMemsetAsync(ints, 0, 2 * sizeof(int), stream);
+    if (he == hipSuccess && big && !d_nrm) {
+        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
+        he = hipGetLastError();
+        nrm = S.at<float>(o_nrm);
+    }
+    if (he == hipSuccess) he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, ints, S.at<float>(o_cf), S.at<float>(o_cn), stream);
+#define KM_LAUNCH(...) if (he == hipSuccess) { hipLaunchKernelGGL(__VA_ARGS__); he = hipGetLastError(); }
+    KM_LAUNCH(km_hist_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, bcnt)
+    KM_LAUNCH(km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt)
+    KM_LAUNCH(km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, run0)
+    KM_LAUNCH(km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, (const int *)bcnt, (const int *)start, mem)
+    KM_LAUNCH(km_runsum_kernel, dim3(rmax), dim3(256), 0, stream, d_x, n, d, k, L, (const int *)mem, (const int *)cnt, (const int *)start,
+              (const int *)run0, part)
+    KM_LAUNCH(km_combine_kernel, dim3(k), dim3(256), 0, stream, (const double *)part, d, (const int *)cnt, (const int *)run0, sums, wt)
+    KM_LAUNCH(km_relocate_kernel, dim3(1), dim3(1024), 0, stream, d_x, n, d, k, (const int *)d_labels, (const double *)dist, (const int *)cnt,
+              sums, wt, ints + 1)
+    KM_LAUNCH(km_update_kernel, dim3(k), dim3(256), 0, stream, (const double *)sums, (const double *)wt, d_centers, d, k, d_centers_new, shift)
+    KM_LAUNCH(km_stats_kernel, dim3(1), dim3(256), 0, stream, (const double *)shift, k, (const int *)ints, d_stats)
+#undef KM_LAUNCH
+    (void)hipFreeAsync(S.base, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_lloyd", he);
+}
+
+extern "C" int ra_kmeans_search(const double *d_w, int n, const double *d_vals, int m, int *d_idx, void *hip_stream)
+{
+    if (n < 1 || n > KM_MAX_N || m < 1 || m > KM_MAX_M) {
+        g_last_error = "ra_kmeans_search: need 1 <= n <= 4194304 and 1 <= m <= 16";
+        return RA_ERR_ARG;
+    }
+    if (!d_w || !d_vals || !d_idx) { g_last_error = "ra_kmeans_search: null argument"; return RA_ERR_ARG; }
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nseg = (n + KM_SEG - 1) / KM_SEG;
+    double *buf = nullptr;
+    hipError_t he = hipMallocAsync((void **)&buf, (size_t)3 * nseg * sizeof(double), stream);
+    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_search", he);
+    double *segsum = buf, *base = buf + nseg, *end = buf + 2 * nseg;
+    hipLaunchKernelGGL(km_segsum_kernel, dim3((nseg + 255) / 256), dim3(256), 0, stream, d_w, n, segsum);
+    he = hipGetLastError();
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(km_segscan_kernel, dim3(1), dim3(256), 0, stream, (const double *)segsum, nseg, base, end);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(km_search_kernel, dim3(m), dim3(256), 0, stream, d_w, n, (const double *)base, (const double *)end, nseg, d_vals, d_idx);
+        he = hipGetLastError();
+    }
+    (void)hipFreeAsync(buf, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_search", he);
+}
+
+extern "C" int ra_kmeans_seed(const float *d_x, int n, int d, const int *d_cand, int m, double *d_closest, int first, double *d_out,
+                              void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_seed", n, d, 1)) return RA_ERR_ARG;
+    if (m < 1 || m > KM_MAX_M || (first && m != 1)) {
+        g_last_error = "ra_kmeans_seed: need 1 <= m <= 16 candidates (first centre: m = 1)";
+        return RA_ERR_ARG;
+    }
+    if (!d_x || !d_cand || !d_closest || !d_out) { g_last_error = "ra_kmeans_seed: null argument"; return RA_ERR_ARG; }
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + 255) / 256;
+    double *part = nullptr;
+    hipError_t he = hipMallocAsync((void **)&part, (size_t)m * nb * sizeof(double), stream);
+    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_seed", he);
+    hipLaunchKernelGGL(km_cand_dist_kernel, dim3(nb, m), dim3(256), 0, stream, d_x, n, d, d_cand, first ? (const double *)nullptr : d_closest, part);
+    he = hipGetLastError();
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(km_pick_kernel, dim3(1), dim3(256), 0, stream, (const double *)part, nb, d_cand, m, n, d_out);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(km_commit_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, (const double *)d_out, first, d_closest);
+        he = hipGetLastError();
+    }
+    (void)hipFreeAsync(part, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_seed", he);
 }

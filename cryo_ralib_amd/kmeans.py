@@ -1,0 +1,609 @@
+"""k-means of factors X [n][d] on the GPU, with class averages (scikit-learn 1.7 KMeans(algorithm="lloyd"), uniform weights).
+
+    python -m cryo_ralib_amd.kmeans IN OUT.npz --k K [--key factors] [--init k-means++|random|FILE.npy] [--n_init auto|N]
+                                    [--max_iter 300] [--tol 1e-4] [--seed S] [--backend device|numpy] [--truth FILE]
+                                    [--stack STACK --params PARAMS --ou R --averages REFS.{hdf,mrcs,npy}]
+
+IN is the OUT.npz of the sdr tool (--key factors) or of the tsne tool (--key embedding), or an [n][d] .npy.  --truth takes an int
+.npy or a params.txt (its class column); OUT.npz then also holds purity, c_purity and contingency.  --averages writes the k class
+averages of the stack (rot_shift2D by PARAMS, then the multi-reference loop's reference update): a refstack for the
+multi-reference command line.
+
+The contract is sklearn's KMeans(algorithm="lloyd") with uniform sample weights:
+  Seeding: init="k-means++" is _kmeans_plusplus with n_local_trials = 2 + int(log(k)): the first centre
+  random_state.choice(n, p=ones/n); every later one draws random_state.uniform(size=n_local_trials) * current_pot, takes the
+  candidates np.searchsorted(cumsum(closest_dist_sq), rand_vals) clipped to n - 1, and keeps the first one of least potential
+  sum_i min(closest_i, d^2(x_i, cand)).  init="random" is random_state.choice(n, size=k, replace=False, p=ones/n); init may be a
+  [k][d] array.  random_state as sklearn's check_random_state.  The draws happen on the host in sklearn's order; the potentials,
+  the cumulative sum and the search run on the device.
+  n_init: "auto" is 1 for k-means++ or an array, 10 for random; the runs draw from one RandomState in turn, and a run replaces
+  the best only if inertia < best and the clustering differs (_is_same_clustering).
+  Lloyd (_kmeans_single_lloyd): E-step label = argmin_c |x - c|^2 (first index on ties), M-step member means, empty clusters
+  relocated as _relocate_empty_clusters_dense (farthest points in decreasing distance, ties by lower index; none when every
+  point sits on its centre), a cluster still empty placed on the heaviest one as _average_centers does, stop on strict
+  convergence (labels unchanged) or when sum_c |c_new - c_old|^2 <= mean(var(X, axis=0)) * tol; without strict convergence one
+  more E-step.  inertia = sum_i |x_i - c_label|^2; n_iter is sklearn's n_iter_.
+Not built: sample_weight, algorithm="elkan", sparse input; sklearn's internal mean-centring (it changes rounding only).
+
+Every distance, sum and update runs in the HIP kernels behind ra_kmeans_* (csrc/ralign_kmeans.h); the host reads the changed-label
+count and the centre shift once per iteration and the potential once per seeded centre.  backend="numpy" runs the same loop in
+float64 numpy: it is the CPU checker.  contingency_matrix, purity_score and c_purity_score restate the reference's utils_ralib
+(sklearn is not a run-time dependency).
+
+Domain: 1 <= k <= min(256, n), 1 <= n <= 4194304, 1 <= d <= 2048, max_iter >= 1, tol >= 0, finite input.  Anything else raises
+KMeansError before anything is launched.
+"""
+import argparse
+import ctypes
+import math
+import numbers
+import sys
+import warnings
+
+import numpy as np
+
+MAX_N, MAX_D, MAX_K = 4194304, 2048, 256
+
+
+class KMeansError(ValueError):
+    """an input outside the supported domain"""
+
+
+class ConvergenceWarning(UserWarning):
+    """sklearn's warning class for fewer distinct clusters than asked for"""
+
+
+class KMeansResult:
+    """labels int32 [n], centers float64 [k][d], inertia, n_iter (sklearn's n_iter_), init_indices (the rows of X the kept run
+    started from; None for an init array)"""
+
+    def __init__(self, labels, centers, inertia, n_iter, init_indices):
+        self.labels, self.centers, self.inertia, self.n_iter, self.init_indices = labels, centers, inertia, n_iter, init_indices
+
+
+def _is_int(v):
+    return isinstance(v, (numbers.Integral, np.integer)) and not isinstance(v, bool)
+
+
+def check_domain(n, d, n_clusters, max_iter=300, tol=1e-4, n_init="auto"):
+    """raise KMeansError unless the shape and parameters are inside the supported domain"""
+    def need(ok, msg):
+        if not ok:
+            raise KMeansError(msg)
+    for name, v in (("n", n), ("d", d), ("n_clusters", n_clusters), ("max_iter", max_iter)):
+        need(_is_int(v), "%s must be an integer, got %r" % (name, v))
+    need(1 <= n <= MAX_N, "need 1 <= n <= %d points, got %d" % (MAX_N, n))
+    need(1 <= d <= MAX_D, "need 1 <= d <= %d features, got %d" % (MAX_D, d))
+    need(1 <= n_clusters <= min(MAX_K, n), "need 1 <= n_clusters <= min(%d, n = %d), got %d" % (MAX_K, n, n_clusters))
+    need(max_iter >= 1, "need max_iter >= 1, got %d" % max_iter)
+    need(isinstance(tol, (numbers.Real, np.number)) and not isinstance(tol, bool) and math.isfinite(tol) and tol >= 0,
+         "need a finite tol >= 0, got %r" % (tol,))
+    need(n_init == "auto" or (_is_int(n_init) and n_init >= 1), "n_init is 'auto' or an integer >= 1, got %r" % (n_init,))
+
+
+def check_random_state(seed):
+    """sklearn.utils.check_random_state"""
+    if seed is None or seed is np.random:
+        return np.random.mtrand._rand
+    if _is_int(seed):
+        return np.random.RandomState(seed)
+    if isinstance(seed, np.random.RandomState):
+        return seed
+    raise KMeansError("random_state is None, an integer or a numpy RandomState, got %r" % (seed,))
+
+
+def n_local_trials(k):
+    """sklearn's k-means++ candidates per centre"""
+    return 2 + int(np.log(k))
+
+
+def tolerance(X, tol):
+    """sklearn's _tolerance: mean(var(X, axis=0)) * tol, in float64"""
+    if tol == 0:
+        return 0.0
+    return float(np.mean(np.var(np.asarray(X, np.float64), axis=0)) * tol)
+
+
+def is_same_clustering(labels1, labels2, k):
+    """sklearn's _is_same_clustering: equal up to a permutation of the labels"""
+    mapping = np.full(k, -1, np.int64)
+    for a, b in zip(np.asarray(labels1).tolist(), np.asarray(labels2).tolist()):
+        if mapping[a] == -1:
+            mapping[a] = b
+        elif mapping[a] != b:
+            return False
+    return True
+
+
+# ---- CPU checker (float64 numpy)
+
+class _Numpy:
+    """the backend operations in float64 numpy"""
+
+    def __init__(self, X):
+        self.X = np.asarray(X, np.float64)
+        self.n, self.d = self.X.shape
+        self.reset_labels()
+
+    def reset_labels(self):
+        self.labels = np.full(self.n, -1, np.int64)
+
+    def gather(self, idx):
+        return self.X[np.asarray(idx, np.int64)].copy()
+
+    def centers_from(self, C):
+        return np.array(C, np.float64)
+
+    def to_numpy(self, C):
+        return np.array(C, np.float64)
+
+    def _dist(self, x):
+        return np.sum((self.X - x) ** 2, axis=1)
+
+    def seed(self, cand, first):
+        D = np.stack([self._dist(self.X[c]) for c in cand])
+        if not first:
+            D = np.minimum(self.closest[None, :], D)
+        pots = D.sum(axis=1)
+        best = int(np.argmin(pots))
+        self.closest = D[best]
+        return int(cand[best]), float(pots[best])
+
+    def search(self, vals):
+        idx = np.searchsorted(np.cumsum(self.closest, dtype=np.float64), vals)
+        return np.minimum(idx, self.n - 1)
+
+    def assign(self, C):
+        k = C.shape[0]
+        lab = np.empty(self.n, np.int64)
+        dist = np.empty(self.n)
+        ch = max(1, (1 << 22) // max(1, k * self.d))
+        for s in range(0, self.n, ch):
+            D = np.sum((self.X[s:s + ch, None, :] - C[None, :, :]) ** 2, axis=2)
+            lab[s:s + ch] = np.argmin(D, axis=1)
+            dist[s:s + ch] = D[np.arange(D.shape[0]), lab[s:s + ch]]
+        return lab, dist
+
+    def lloyd(self, C):
+        k = C.shape[0]
+        lab, dist = self.assign(C)
+        changed = int(np.count_nonzero(lab != self.labels))
+        self.labels = lab
+        sums = np.zeros((k, self.d))
+        np.add.at(sums, lab, self.X)
+        wt = np.bincount(lab, minlength=k).astype(np.float64)
+        empty = np.nonzero(wt == 0)[0]
+        if len(empty) and dist.max() != 0:
+            far = np.lexsort((np.arange(self.n), -dist))[:len(empty)]
+            for nw, f in zip(empty, far):
+                old = lab[f]
+                sums[old] -= self.X[f]
+                sums[nw] = self.X[f]
+                wt[nw] = 1.0
+                wt[old] -= 1.0
+        Cn = sums.copy()
+        heavy = int(np.argmax(wt))
+        for j in range(k):          # sklearn's _average_centers, in its order
+            if wt[j] > 0:
+                Cn[j] *= 1.0 / wt[j]
+            else:
+                Cn[j] = Cn[heavy]
+        return Cn, float(np.sum((Cn - C) ** 2)), changed
+
+    def finish(self, C, assign):
+        if assign:
+            self.labels, dist = self.assign(C)
+        else:
+            dist = np.sum((self.X - C[self.labels]) ** 2, axis=1)
+        return float(np.sum(dist))
+
+    def labels_numpy(self):
+        return self.labels.astype(np.int32)
+
+
+# ---- device
+
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class _Device:
+    """thin launcher of the ra_kmeans_* entries on the current stream of X's device"""
+
+    def __init__(self, X):
+        import torch
+        from . import api
+        self.torch, self.api, self.lib, self.dev = torch, api, api.load_library(), X.device
+        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        self.X = X
+        self.n, self.d = (int(s) for s in X.shape)
+        self.nrm = torch.empty(self.n, dtype=torch.float32, device=self.dev)
+        self.api._check(self.lib.ra_kmeans_sqnorm(_ptr(X), self.n, self.d, _ptr(self.nrm), self.stream), "ra_kmeans_sqnorm")
+        self.labels = torch.empty(self.n, dtype=torch.int32, device=self.dev)
+        self.stats = torch.empty(3, dtype=torch.float64, device=self.dev)
+        self.closest = None
+        self.reset_labels()
+
+    def reset_labels(self):
+        self.labels.fill_(-1)
+
+    def gather(self, idx):
+        i = self.torch.as_tensor(np.asarray(idx, np.int64), device=self.dev)
+        return self.X.index_select(0, i).to(self.torch.float64).contiguous()
+
+    def centers_from(self, C):
+        return self.torch.from_numpy(np.ascontiguousarray(C, np.float64)).to(self.dev)
+
+    def to_numpy(self, C):
+        return C.cpu().numpy()
+
+    def seed(self, cand, first):
+        torch = self.torch
+        if not isinstance(cand, torch.Tensor):
+            cand = torch.as_tensor(np.asarray(cand, np.int32), device=self.dev)
+        m = int(cand.numel())
+        if self.closest is None:
+            self.closest = torch.empty(self.n, dtype=torch.float64, device=self.dev)
+        out = torch.empty(m + 2, dtype=torch.float64, device=self.dev)
+        self.api._check(self.lib.ra_kmeans_seed(_ptr(self.X), self.n, self.d, _ptr(cand), m, _ptr(self.closest), int(bool(first)),
+                                                _ptr(out), self.stream), "ra_kmeans_seed")
+        o = out[:2].cpu().numpy()
+        return int(o[0]), float(o[1])
+
+    def search(self, vals):
+        torch = self.torch
+        v = torch.from_numpy(np.ascontiguousarray(vals, np.float64)).to(self.dev)
+        idx = torch.empty(int(v.numel()), dtype=torch.int32, device=self.dev)
+        self.api._check(self.lib.ra_kmeans_search(_ptr(self.closest), self.n, _ptr(v), int(v.numel()), _ptr(idx), self.stream),
+                        "ra_kmeans_search")
+        return idx
+
+    def lloyd(self, C):
+        k = int(C.shape[0])
+        Cn = self.torch.empty_like(C)
+        self.api._check(self.lib.ra_kmeans_lloyd(_ptr(self.X), self.n, self.d, _ptr(self.nrm), _ptr(C), k, _ptr(Cn), _ptr(self.labels),
+                                                 _ptr(self.stats), self.stream), "ra_kmeans_lloyd")
+        s = self.stats.cpu().numpy()
+        return Cn, float(s[0]), int(s[1])
+
+    def finish(self, C, assign):
+        out = self.torch.empty(1, dtype=self.torch.float64, device=self.dev)
+        self.api._check(self.lib.ra_kmeans_labels(_ptr(self.X), self.n, self.d, _ptr(self.nrm), _ptr(C), int(C.shape[0]), _ptr(self.labels),
+                                                  int(bool(assign)), _ptr(out), self.stream), "ra_kmeans_labels")
+        return float(out.item())
+
+    def labels_numpy(self):
+        return self.labels.cpu().numpy().astype(np.int32)
+
+    def tolerance(self, tol):
+        """mean(var(X, axis=0)) * tol in float64, two passes over row chunks (torch plumbing, once per fit)"""
+        if tol == 0:
+            return 0.0
+        torch = self.torch
+        ch = max(1, (1 << 24) // self.d)
+        s = torch.zeros(self.d, dtype=torch.float64, device=self.dev)
+        for i in range(0, self.n, ch):
+            s += self.X[i:i + ch].to(torch.float64).sum(0)
+        mean = s / self.n
+        q = torch.zeros(self.d, dtype=torch.float64, device=self.dev)
+        for i in range(0, self.n, ch):
+            q += ((self.X[i:i + ch].to(torch.float64) - mean) ** 2).sum(0)
+        return float((q / self.n).mean().item()) * tol
+
+
+# ---- the loop (sklearn KMeans.fit / _kmeans_single_lloyd / _kmeans_plusplus)
+
+def _plusplus(B, k, rs):
+    n = B.n
+    m = n_local_trials(k)
+    c0 = int(rs.choice(n, p=np.ones(n) / n))
+    idx = [c0]
+    _, pot = B.seed([c0], True)
+    for _ in range(1, k):
+        vals = rs.uniform(size=m) * pot
+        chosen, pot = B.seed(B.search(vals), False)
+        idx.append(chosen)
+    return np.asarray(idx, np.int64)
+
+
+def _single(B, C, max_iter, tol_abs):
+    B.reset_labels()
+    strict = False
+    i = 0
+    for i in range(max_iter):
+        C, shift, changed = B.lloyd(C)
+        if changed == 0:
+            strict = True
+            break
+        if shift <= tol_abs:
+            break
+    inertia = B.finish(C, not strict)
+    return B.labels_numpy(), inertia, C, i + 1
+
+
+def _fit(B, k, init, n_init, max_iter, tol_abs, random_state):
+    rs = check_random_state(random_state)
+    best = None
+    for _ in range(n_init):
+        if isinstance(init, str) and init == "k-means++":
+            idx = _plusplus(B, k, rs)
+            C = B.gather(idx)
+        elif isinstance(init, str) and init == "random":
+            idx = np.asarray(rs.choice(B.n, size=k, replace=False, p=np.ones(B.n) / B.n), np.int64)
+            C = B.gather(idx)
+        else:
+            idx = None
+            C = B.centers_from(init)
+        labels, inertia, C, n_iter = _single(B, C, max_iter, tol_abs)
+        if best is None or (inertia < best[1] and not is_same_clustering(labels, best[0], k)):
+            best = (labels, inertia, C, n_iter, idx)
+    labels, inertia, C, n_iter, idx = best
+    distinct = len(np.unique(labels))
+    if distinct < k:
+        warnings.warn("Number of distinct clusters ({}) found smaller than n_clusters ({}). Possibly due to duplicate points "
+                      "in X.".format(distinct, k), ConvergenceWarning, stacklevel=3)
+    return KMeansResult(labels, B.to_numpy(C), float(inertia), int(n_iter), idx)
+
+
+def _as_input(X, backend):
+    if backend == "device":
+        import torch
+        if isinstance(X, np.ndarray):
+            X = torch.from_numpy(np.ascontiguousarray(X, np.float32)).to(torch.device("cuda", torch.cuda.current_device()))
+        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
+            raise KMeansError("backend 'device' takes a contiguous float32 CUDA tensor [n][d] (or a numpy array, copied)")
+        if X.ndim != 2:
+            raise KMeansError("X is [n][d], got shape %s" % (tuple(X.shape),))
+        return X
+    if backend != "numpy":
+        raise KMeansError("backend is 'device' or 'numpy', got %r" % (backend,))
+    if not isinstance(X, np.ndarray) and hasattr(X, "detach"):
+        X = X.detach().cpu().numpy()
+    X = np.asarray(X)
+    if X.ndim != 2:
+        raise KMeansError("X is [n][d], got shape %s" % (X.shape,))
+    return X
+
+
+def _check_finite(X, backend):
+    ok = bool(X.isfinite().all().item()) if backend == "device" else bool(np.all(np.isfinite(X)))
+    if not ok:
+        raise KMeansError("X holds NaN or infinite values")
+
+
+def _resolve_init(init, k, d):
+    if isinstance(init, str):
+        if init not in ("k-means++", "random"):
+            raise KMeansError("init is 'k-means++', 'random' or a [k][d] array, got %r" % (init,))
+        return init
+    C = np.array(init.detach().cpu().numpy() if hasattr(init, "detach") else init, np.float64)
+    if C.shape != (k, d):
+        raise KMeansError("an init array is [n_clusters][d] = [%d][%d], got %s" % (k, d, C.shape))
+    if not np.all(np.isfinite(C)):
+        raise KMeansError("the init array holds NaN or infinite values")
+    return C
+
+
+def kmeans(X, n_clusters, init="k-means++", n_init="auto", max_iter=300, tol=1e-4, random_state=None, backend="device"):
+    """k-means of X [n][d]: KMeansResult(labels int32 [n], centers float64 [k][d], inertia, n_iter, init_indices)"""
+    X = _as_input(X, backend)
+    n, d = (int(s) for s in X.shape)
+    check_domain(n, d, n_clusters, max_iter, tol, n_init)
+    init = _resolve_init(init, n_clusters, d)
+    check_random_state(random_state)
+    _check_finite(X, backend)
+    if n_init == "auto":
+        n_init = 10 if isinstance(init, str) and init == "random" else 1
+    if not isinstance(init, str) and n_init != 1:
+        warnings.warn("Explicit initial center position passed: performing only one init in KMeans instead of n_init=%d." % n_init,
+                      RuntimeWarning, stacklevel=2)
+        n_init = 1
+    if backend == "numpy":
+        return _fit(_Numpy(X), n_clusters, init, n_init, max_iter, tolerance(X, tol), random_state)
+    import torch
+    with torch.cuda.device(X.device):
+        B = _Device(X)
+        return _fit(B, n_clusters, init, n_init, max_iter, B.tolerance(tol), random_state)
+
+
+def labels_for(X, centers, backend="device"):
+    """(labels int32 [n], inertia) of the given centers [k][d]: the E-step alone"""
+    X = _as_input(X, backend)
+    n, d = (int(s) for s in X.shape)
+    C = np.asarray(centers, np.float64)
+    check_domain(n, d, int(C.shape[0]) if C.ndim == 2 else 0)
+    C = _resolve_init(C, C.shape[0], d)
+    _check_finite(X, backend)
+    if backend == "numpy":
+        B = _Numpy(X)
+        inertia = B.finish(C, True)
+        return B.labels_numpy(), inertia
+    import torch
+    with torch.cuda.device(X.device):
+        B = _Device(X)
+        inertia = B.finish(B.centers_from(C), True)
+        return B.labels_numpy(), inertia
+
+
+# ---- scores (utils_ralib.purity_score / c_purity_score over sklearn.metrics.cluster.contingency_matrix)
+
+def contingency_matrix(y_true, y_pred):
+    """[classes of y_true][classes of y_pred] counts, both in sorted order of their distinct values"""
+    y_true, y_pred = np.asarray(y_true).ravel(), np.asarray(y_pred).ravel()
+    if y_true.shape != y_pred.shape:
+        raise KMeansError("y_true and y_pred differ in length: %d, %d" % (y_true.size, y_pred.size))
+    classes, ci = np.unique(y_true, return_inverse=True)
+    clusters, ki = np.unique(y_pred, return_inverse=True)
+    M = np.zeros((classes.size, clusters.size), np.int64)
+    np.add.at(M, (ci, ki), 1)
+    return M
+
+
+def purity_score(y_true, y_pred):
+    """sum over clusters of the largest class count / n"""
+    M = contingency_matrix(y_true, y_pred)
+    return float(np.sum(np.amax(M, axis=0)) / np.sum(M))
+
+
+def c_purity_score(y_true, y_pred):
+    """sum over classes of the largest cluster count / n"""
+    M = contingency_matrix(y_true, y_pred)
+    return float(np.sum(np.amax(M, axis=1)) / np.sum(M))
+
+
+# ---- class averages through the engine
+
+def class_averages(images, params, labels, k, ou, min_count=1, preprocess=True, device=0):
+    """[k][nx][nx] float32 averages of the stack's clusters, as the multi-reference loop updates its references: the particles
+    preprocessed (masked mean subtracted) unless preprocess=False, rot_shift2D by params [n][4] (alpha, sx, sy, mirror) with the
+    cluster as ref_id (Engine.transform_accumulate), then (even + odd) / count normalised under model_circle(ou)
+    (Engine.update_references).  Clusters with fewer than min_count members stay zero."""
+    import torch
+    from . import api
+    dev = torch.device("cuda", device)
+    if isinstance(images, np.ndarray):
+        images = torch.from_numpy(np.ascontiguousarray(images, np.float32))
+    x = images.to(dev, dtype=torch.float32).contiguous().clone()
+    if x.ndim != 3 or x.shape[1] != x.shape[2]:
+        raise KMeansError("images are [n][nx][nx], got %s" % (tuple(x.shape),))
+    n, nx = int(x.shape[0]), int(x.shape[-1])
+    prm = np.asarray(params.detach().cpu().numpy() if hasattr(params, "detach") else params, np.float64)
+    lab = np.asarray(labels.detach().cpu().numpy() if hasattr(labels, "detach") else labels).astype(np.int64)
+    if prm.shape != (n, 4):
+        raise KMeansError("params is [%d][4] (alpha, sx, sy, mirror), got %s" % (n, prm.shape))
+    if lab.shape != (n,) or not (_is_int(k) and 1 <= k <= MAX_K) or lab.min() < 0 or lab.max() >= k:
+        raise KMeansError("labels are [%d] integers in 0 .. k - 1 with 1 <= k <= %d" % (n, MAX_K))
+    rec = np.zeros(n, api.RESULT_DTYPE)
+    rec["alpha"], rec["sx"], rec["sy"] = prm[:, 0], prm[:, 1], prm[:, 2]
+    rec["mirror"] = (prm[:, 3] != 0).astype(np.int32)
+    rec["ref_id"] = lab.astype(np.int32)
+    with torch.cuda.device(dev):
+        eng = api.Engine(nx, int(ou), 0.0, 0.0, 1.0, int(k), api.RA_MODE_MREF, device=dev.index)
+        try:
+            eng.use_current_stream()
+            if preprocess:
+                eng.normalize_particles(x)
+            res = torch.from_numpy(rec.view(np.int32).reshape(n, 8).copy()).to(dev)
+            sums = torch.zeros((k, 2, nx, nx), dtype=torch.float32, device=dev)
+            counts = torch.zeros(k, dtype=torch.int32, device=dev)
+            eng.transform_accumulate(x, res, 0, None, sums, counts)
+            refs = torch.zeros((k, nx, nx), dtype=torch.float32, device=dev)
+            eng.update_references(sums, counts, refs, int(min_count))
+            eng.sync()
+            return refs.cpu().numpy()
+        finally:
+            eng.close()
+
+
+# ---- command line
+
+def read_input(path, key="factors"):
+    """[n][d] float32 from an .npz (key) or an .npy"""
+    try:
+        if path.endswith(".npz"):
+            with np.load(path) as z:
+                if key not in z.files:
+                    raise KMeansError("%s has no array %r (it holds %s)" % (path, key, ", ".join(z.files)))
+                X = z[key]
+        else:
+            X = np.load(path)
+    except (OSError, ValueError) as e:
+        raise KMeansError("%s: %s" % (path, e))
+    X = np.ascontiguousarray(X, np.float32)
+    if X.ndim != 2:
+        raise KMeansError("%s: need an [n][d] array, got shape %s" % (path, X.shape))
+    return X
+
+
+def read_truth(path, n):
+    """[n] int classes from an int .npy or a params.txt (idx angle_psi shift_x shift_y mirror class, rows in any order)"""
+    try:
+        if path.endswith(".npy"):
+            y = np.load(path)
+            if y.shape != (n,) or not np.issubdtype(y.dtype, np.integer):
+                raise KMeansError("%s: need [%d] integers, got %s %s" % (path, n, y.dtype, y.shape))
+            return y.astype(np.int64)
+        rows = np.loadtxt(path, ndmin=2, dtype=np.float64)
+    except (OSError, ValueError) as e:
+        raise KMeansError("%s: %s" % (path, e))
+    if rows.shape != (n, 6):
+        raise KMeansError("%s: need %d rows of 6 columns (params.txt), got %s" % (path, n, rows.shape))
+    idx = rows[:, 0].astype(np.int64)
+    if not np.array_equal(np.sort(idx), np.arange(n)):
+        raise KMeansError("%s: the idx column is not a permutation of 0 .. %d" % (path, n - 1))
+    y = np.empty(n, np.int64)
+    y[idx] = rows[:, 5].astype(np.int64)
+    return y
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m cryo_ralib_amd.kmeans")
+    ap.add_argument("input", help="OUT.npz of the sdr or tsne tool, or an [n][d] .npy")
+    ap.add_argument("output", help="OUT.npz")
+    ap.add_argument("--k", type=int, required=True, help="number of clusters")
+    ap.add_argument("--key", default="factors", help="array of an .npz input (default factors; embedding for the tsne tool)")
+    ap.add_argument("--init", default="k-means++", help="k-means++, random or a [k][d] .npy")
+    ap.add_argument("--n_init", default="auto", help="'auto' or an integer")
+    ap.add_argument("--max_iter", type=int, default=300)
+    ap.add_argument("--tol", type=float, default=1e-4)
+    ap.add_argument("--seed", type=int, default=None, help="random_state")
+    ap.add_argument("--backend", default="device", choices=("device", "numpy"))
+    ap.add_argument("--truth", default=None, help="int .npy or params.txt: purity, c_purity and contingency in OUT.npz")
+    ap.add_argument("--stack", default=None, help="stack for --averages (.hdf, .mrcs or .npy)")
+    ap.add_argument("--params", default=None, help="params.txt or initial2Dparams.txt of the stack")
+    ap.add_argument("--ou", type=int, default=None, help="outer radius of the averages' mask")
+    ap.add_argument("--averages", default=None, help="REFS.{hdf,mrcs,npy}: the k class averages")
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    try:
+        X = read_input(args.input, args.key)
+        n, d = X.shape
+        n_init = args.n_init if args.n_init == "auto" else int(args.n_init)
+        init = args.init if args.init in ("k-means++", "random") else np.load(args.init)
+        check_domain(n, d, args.k, args.max_iter, args.tol, n_init)
+        truth = read_truth(args.truth, n) if args.truth else None
+        if args.averages and not (args.stack and args.params and args.ou):
+            raise KMeansError("--averages needs --stack, --params and --ou")
+    except (KMeansError, OSError, ValueError) as e:
+        raise SystemExit("error: %s" % e)
+    if args.backend == "device" or args.averages:
+        import torch
+        if not torch.cuda.is_available():
+            raise SystemExit("no GPU visible: use --backend numpy for the CPU checker (--averages needs the GPU)")
+    try:
+        if args.backend == "device":
+            import torch
+            dev = torch.device("cuda", args.device)
+            with torch.cuda.device(dev):
+                res = kmeans(torch.from_numpy(X).to(dev), args.k, init, n_init, args.max_iter, args.tol, args.seed)
+        else:
+            res = kmeans(X, args.k, init, n_init, args.max_iter, args.tol, args.seed, backend="numpy")
+    except KMeansError as e:
+        raise SystemExit("error: %s" % e)
+    out = dict(labels=res.labels, centers=res.centers, inertia=np.float64(res.inertia), n_iter=np.int64(res.n_iter),
+               init_indices=res.init_indices if res.init_indices is not None else np.zeros(0, np.int64), k=np.int64(args.k),
+               init=np.str_(args.init), seed=np.int64(-1 if args.seed is None else args.seed), backend=np.str_(args.backend))
+    msg = "%s: %d points x %d, k = %d, %d iterations, inertia %.6g" % (args.output, n, d, args.k, res.n_iter, res.inertia)
+    if truth is not None:
+        out["purity"], out["c_purity"] = np.float64(purity_score(truth, res.labels)), np.float64(c_purity_score(truth, res.labels))
+        out["contingency"] = contingency_matrix(truth, res.labels)
+        msg += ", purity %.4f, c_purity %.4f" % (out["purity"], out["c_purity"])
+    if args.averages:
+        from . import sdr, stackio
+        try:
+            stack = np.ascontiguousarray(stackio.read_stack(args.stack), np.float32)
+            if stack.ndim != 3 or stack.shape[0] != n:
+                raise KMeansError("%s: need a stack of %d images, got shape %s" % (args.stack, n, stack.shape))
+            prm = sdr.read_params(args.params, n)
+            refs = class_averages(stack, prm, res.labels, args.k, args.ou, device=args.device)
+        except (KMeansError, sdr.SdrError, OSError, ValueError) as e:
+            raise SystemExit("error: %s" % e)
+        stackio.write_stack(args.averages, refs)
+        msg += ", averages -> %s" % args.averages
+    np.savez(args.output, **out)
+    print(msg)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

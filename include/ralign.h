@@ -355,6 +355,37 @@ int  ra_tsne_step(const float *d_y, float *d_y_out, float *d_update, float *d_ga
 int  ra_tsne_error(const float *d_y, int n, const int *d_indptr, const int *d_indices, const float *d_p, int nnz, float exaggeration,
                    float *d_grad, double *d_stats, void *hip_stream);
 
+/* k-means (scikit-learn 1.7 KMeans(algorithm="lloyd") with uniform weights) of X [n][d] in device memory, without an engine
+ * (DESIGN.md section 4.8).  Pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL = default
+ * stream) and allocates and frees its scratch on that stream, as ra_phase_flip does.  Results are bitwise reproducible call to
+ * call and across streams (no floating-point atomics; every sum in an order fixed by n, d, k and the labels).  Distances are
+ * squared euclidean, decided in double from x - c; labels are the first index of least distance.  The shape domain is
+ * 1 <= n <= 4194304, 1 <= d <= 2048, 1 <= k <= min(n, 256); RA_ERR_ARG for anything outside the documented domain, and nothing
+ * is launched then.  The seeding draws and the loop around these entries are cryo_ralib_amd/kmeans.py.
+ *   ra_kmeans_sqnorm  d_nrm [n] = |x_i|^2 of d_x [n][d] (float32; double sums rounded once): the screen's norms.  k is not an argument.
+ *   ra_kmeans_labels  E-step for the centres d_centers [k][d] (double): assign != 0 writes d_labels [n]; assign == 0 keeps the
+ *                     labels in d_labels (entries clamped to 0 .. k - 1).  d_inertia [1] (may be NULL when assign != 0) = sum of
+ *                     |x_i - c_label|^2.  d_nrm from ra_kmeans_sqnorm, or NULL (computed in scratch).
+ *   ra_kmeans_lloyd   one Lloyd iteration: labels of d_centers (d_labels in: the previous labels, -1 before the first
+ *                     iteration; out: the new ones), member means into d_centers_new [k][d] (!= d_centers), empty clusters
+ *                     relocated to the points farthest from their centre (decreasing distance, ties by lower index) as
+ *                     sklearn's _relocate_empty_clusters_dense.  d_stats [3] = {sum_c |c_new - c_old|^2, labels changed,
+ *                     clusters found empty}.
+ *   ra_kmeans_search  d_idx [m] = np.searchsorted(cumsum(d_w), d_vals, side="left") clipped to n - 1, the cumulative sum of
+ *                     d_w [n] (double, >= 0) in a fixed order; 1 <= n <= 4194304, 1 <= m <= 16.
+ *   ra_kmeans_seed    one k-means++ step over the m candidate rows d_cand [m] (indices into d_x, clamped): potentials
+ *                     sum_i min(d_closest_i, |x_i - x_cand|^2), the first candidate of least potential is chosen and folded into
+ *                     d_closest [n] (double).  first != 0 (m = 1): the first centre, d_closest is written, not read.
+ *                     d_out [m + 2] = {chosen index, its potential, the m potentials}.  1 <= m <= 16, k is not an argument. */
+int  ra_kmeans_sqnorm(const float *d_x, int n, int d, float *d_nrm, void *hip_stream);
+int  ra_kmeans_labels(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, int *d_labels, int assign,
+                      double *d_inertia, void *hip_stream);
+int  ra_kmeans_lloyd(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, double *d_centers_new,
+                     int *d_labels, double *d_stats, void *hip_stream);
+int  ra_kmeans_search(const double *d_w, int n, const double *d_vals, int m, int *d_idx, void *hip_stream);
+int  ra_kmeans_seed(const float *d_x, int n, int d, const int *d_cand, int m, double *d_closest, int first, double *d_out,
+                    void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
