@@ -73,6 +73,7 @@ EXPORTED_SYMBOLS = [
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
+    "ra_fourier_resize",
 ]
 
 _lib = None
@@ -172,6 +173,7 @@ def load_library(path=None):
     L.ra_isac_get_references.argtypes = [float_ptr]
     L.ra_phase_flip.argtypes = [vp, ctypes.c_int, ctypes.c_int, float_ptr, ctypes.c_int, vp]
     ci = ctypes.c_int
+    L.ra_fourier_resize.argtypes = [vp, ci, ci, ci, vp, vp]
     L.ra_sdr_mean.argtypes = [vp, ci, ci, ci, vp, vp]
     L.ra_sdr_gram.argtypes = [vp, ci, ci, ci, vp, ci, vp, ci, vp, vp]
     L.ra_sdr_project.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
@@ -259,6 +261,27 @@ def rot_shift2d(images, params, out=None):
     with torch.cuda.device(images.device):
         _check(load_library().ra_rot_shift2d(ctypes.c_void_p(images.data_ptr()), n, nx, ctypes.c_void_p(d_rec.data_ptr()),
                                              ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream.cuda_stream)), "ra_rot_shift2d")
+    return out
+
+
+def fourier_resize(images, m, out=None):
+    """Fourier resizing of images [n][nx][nx] (contiguous float32 CUDA tensor) to [n][m][m], on the current stream
+    (ra_fourier_resize): y = A x A^T with resize.operator(nx, m); 1 <= nx, m <= 1024.  out: a contiguous float32 [n][m][m] tensor
+    on the same device that does not overlap images, or None (allocated).  Returns out."""
+    import torch
+    assert images.is_cuda and images.is_contiguous() and images.dtype == torch.float32, "images: contiguous float32 CUDA tensor"
+    assert images.dim() == 3 and images.shape[1] == images.shape[2], "images: [n][nx][nx]"
+    n, nx, m = int(images.shape[0]), int(images.shape[-1]), int(m)
+    if out is None:
+        if not 1 <= m <= 1024:
+            raise EngineError("fourier_resize: need 1 <= m <= 1024, got %d" % m)
+        out = torch.empty((n, m, m), dtype=torch.float32, device=images.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.device == images.device \
+        and tuple(out.shape) == (n, m, m), "out: contiguous float32 [n][m][m] on the images' device"
+    stream = torch.cuda.current_stream(images.device)
+    with torch.cuda.device(images.device):
+        _check(load_library().ra_fourier_resize(ctypes.c_void_p(images.data_ptr()), n, nx, m, ctypes.c_void_p(out.data_ptr()),
+                                                ctypes.c_void_p(stream.cuda_stream)), "ra_fourier_resize")
     return out
 
 

@@ -306,6 +306,17 @@ size_t ra_legacy_bytes(const unsigned int num_particles, const AlignConfig *cfg)
  * hipStream_t; NULL = default stream); bitwise reproducible; every particle is independent of the others. */
 int  ra_phase_flip(float *d_images, int n, int nx, const float *h_ctf, int pad, void *hip_stream);
 
+/* Fourier resizing of a stack without an engine: d_in [n][nx][nx] -> d_out [n][m][m] (device, float32), either size the larger.
+ * Per image y = A x A^T with the real m x nx operator A[j][i] = (1/nx) sum_{|k| <= min(nx, m)/2} w_k cos(2 pi k (t_j - u_i)),
+ * t_j = (j - m/2) / m, u_i = (i - nx/2) / nx, w_k = 1/2 at |k| = nx/2 for even nx and 1 otherwise: the centred trigonometric
+ * interpolant of x, band-limited to the smaller grid and sampled on the m grid (Fourier cropping for m < nx, zero padding for
+ * m > nx; m == nx is the identity; the output pixel is Apix nx / m).  A is built per call in double and rounded to f32; the
+ * products run on f32 MFMA.  RA_ERR_ARG, with nothing launched, for n < 0, nx or m outside 1 .. 1024,
+ * a null pointer with n > 0, or overlapping d_in / d_out ranges; n == 0 is a no-op.  Asynchronous on hip_stream (a
+ * hipStream_t; NULL = default stream), scratch allocated and freed on that stream; bitwise reproducible; every particle is
+ * independent of the others and of its place in the batch. */
+int  ra_fourier_resize(const float *d_in, int n, int nx, int m, float *d_out, void *hip_stream);
+
 /* Two-stage dimension reduction (utils_ralib.py MPCA / TwoSDR) of a stack in device memory, without an engine (DESIGN.md
  * section 4.6).  All pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL = default stream)
  * and allocates and frees its scratch on that stream, as ra_phase_flip does.  Images are [n][p][q] float32, centred on load
