@@ -22,6 +22,10 @@ test_reffree_gpu_align.py:252-257, 279-281): every particle is phase-flipped onc
 subtraction, and the CTF-free alignment follows.  TABLE is a [N][9] .npy or a RELION .star (cryo_ralib_amd.ctf); --apix
 gives the pixel size where the .star has none, --phase_flip_nopad flips without the 2x zero padding.  --CTF itself, which
 reads the parameters from the stack's EMAN.ctf headers, stays rejected.
+
+--wiener_averages (with --phase_flip and --snr > 0) writes, after the last iteration, CTF-corrected class averages of the
+flipped particles with the final parameters (cryo_ralib_amd.wiener, flipped weights |c|, the flip's padding):
+multi_ref_wiener.<ext> (one per class) or aqfinal_wiener.<ext> (one image).  Ranks sum their spectra before the division.
 """
 import argparse
 import os
@@ -49,6 +53,9 @@ def _common(p):
                         "reference's --CTF does on its GPU path")
     p.add_argument("--apix", type=float, default=None, help="pixel size (A) for a --phase_flip .star file that gives none")
     p.add_argument("--phase_flip_nopad", action="store_true", help="flip at the box size instead of in a 2x zero-padded image")
+    p.add_argument("--wiener_averages", action="store_true",
+                   help="after the last iteration also write CTF-corrected (Wiener) class averages, sum c^2 + 1/snr in the "
+                        "denominator: multi_ref_wiener.<ext> / aqfinal_wiener.<ext>; needs --phase_flip")
     p.add_argument("--ext", default="hdf", help="format of the written stacks: hdf (EMAN2 MDF, as the reference) | mrcs | npy")
     p.add_argument("--header_writeback", action="store_true",
                    help="write xform.align2d / assign / ID into the headers of the HDF INPUT stack itself, as the reference does "
@@ -143,6 +150,36 @@ def _ctf_shard(args, total, nx, lo, hi):
         raise SystemExit("--phase_flip: %s" % e)
 
 
+def _check_wiener(p, args):
+    if args.wiener_averages and not args.phase_flip:
+        p.error("--wiener_averages needs --phase_flip TABLE (the CTF table of the particles)")
+    if args.wiener_averages and not args.snr > 0:
+        p.error("--wiener_averages needs --snr > 0, got %g" % args.snr)
+
+
+def _write_wiener(args, al, total, lo, hi, labels, k, name, rank, world):
+    """CTF-corrected averages of the aligner's flipped particles with its final params; sums all-reduced over the ranks"""
+    from . import stackio, wiener
+    nx = al.nx
+    pad = not args.phase_flip_nopad
+    r = al.params()
+    prm = np.column_stack([r["alpha"], r["sx"], r["sy"], r["mirror"]]).astype(np.float64)
+    num, den, counts = wiener.new_sums(k, nx, pad, al.dev)
+    wiener.accumulate(al.particles, prm, labels, k, _ctf_shard(args, total, nx, lo, hi), num, den, counts, pad, flipped=True)
+    if world > 1:
+        import torch.distributed as td
+        for t in (num, den, counts):
+            if td.get_backend() == "gloo":      # gloo rehearsal of several ranks on one GPU: the collective runs on a host copy
+                h = t.cpu()
+                td.all_reduce(h, op=td.ReduceOp.SUM)
+                t.copy_(h)
+            else:
+                td.all_reduce(t, op=td.ReduceOp.SUM)
+    out = wiener.finalize(num, den, counts, nx, pad, args.snr, min_count=1)
+    if rank == 0:
+        stackio.write_stack(os.path.join(args.outdir, "%s.%s" % (name, args.ext)), out.cpu().numpy())
+
+
 def _setup(args):
     import torch
     from . import dist as rdist
@@ -173,6 +210,7 @@ def main_mref(argv=None):
     _common(p)
     args = p.parse_args(argv)
     _reject_unimplemented(args, reffree=False)
+    _check_wiener(p, args)
     rank, local, world = _setup(args)
     from . import stackio, dist as rdist
     from .mref import MrefAligner
@@ -238,6 +276,8 @@ def main_mref(argv=None):
             from . import mdfio
             rows.sort(key=lambda x: x[0])
             _write_headers(mdfio, args, [x[1:5] for x in rows], assign=[x[5] for x in rows], ids=[x[0] for x in rows])
+    if args.wiener_averages:
+        _write_wiener(args, al, total, lo, hi, r["ref_id"].astype(np.int64), al.nref, "multi_ref_wiener", rank, world)
     al.close()
     return 0
 
@@ -258,6 +298,7 @@ def main_reffree(argv=None):
     _common(p)
     args = p.parse_args(argv)
     _reject_unimplemented(args, reffree=True)
+    _check_wiener(p, args)
     rank, local, world = _setup(args)
     from . import stackio, dist as rdist
     from .mref import RefFreeAligner
@@ -317,5 +358,7 @@ def main_reffree(argv=None):
         if os.path.splitext(args.stack)[1].lower() in (".hdf", ".h5") and not args.no_header_writeback:
             from . import mdfio        # set_params2D(img, [angle, shift_x, shift_y, mirror, 1.0], "xform.align2d") (test_reffree.py:453)
             _write_headers(mdfio, args, rows)
+    if args.wiener_averages:
+        _write_wiener(args, al, total, lo, hi, np.zeros(hi - lo, np.int64), 1, "aqfinal_wiener", rank, world)
     al.close()
     return 0

@@ -86,11 +86,12 @@ struct PfCtf {
     double phi0;            // (phase_shift + asin w) / (2 pi)
 };
 
-__host__ __device__ inline PfCtf pf_ctf_constants(const float *row, int nx, int P)
+// the same with the astigmatism angle (degrees) given instead of row[4] (the Wiener averages' aligned frame, ralign_wiener.h)
+__host__ __device__ inline PfCtf pf_ctf_constants_at(const float *row, int nx, int P, double dfang_deg)
 {
     const double pi = 3.14159265358979323846;
     PfCtf c;
-    const double D = row[0], apix = row[1], dfu = row[2], dfv = row[3], ang = row[4] * pi / 180.0;
+    const double D = row[0], apix = row[1], dfu = row[2], dfv = row[3], ang = dfang_deg * pi / 180.0;
     const double volt = row[5] * 1000.0, w = row[7], ps = row[8] * pi / 180.0;
     const double apix_eff = apix * D / nx;
     const double f = 1.0 / (P * apix_eff);
@@ -104,6 +105,8 @@ __host__ __device__ inline PfCtf pf_ctf_constants(const float *row, int nx, int 
     c.phi0 = (ps + asin(w)) / (2.0 * pi);
     return c;
 }
+
+__host__ __device__ inline PfCtf pf_ctf_constants(const float *row, int nx, int P) { return pf_ctf_constants_at(row, nx, P, row[4]); }
 
 // m(iy, ix) in {+1, -1} at the signed integer frequencies (iy along the rows, ix along the fast axis)
 __host__ __device__ inline float pf_multiplier(const PfCtf &c, int iy, int ix)
@@ -251,15 +254,14 @@ __host__ __device__ inline float2 *pf_fft(const Ctx &cx, float2 *a, float2 *b, i
     return a;
 }
 
-// the three passes over one particle; img [nx][nx] in place, blk [nx][H], work 2 x nb x P, tw [P] = exp(-2 pi i t / P)
+// pass 1: forward row transforms of img [nx][nx] embedded at o, two rows per complex FFT, into blk [nx][H]
 template <class Ctx>
-__host__ __device__ inline void pf_particle(const Ctx &cx, float *img, const PfCtf &cc, const PfPlan &pl, float2 *blk, float2 *work,
-                                            const float2 *tw)
+__host__ __device__ inline void pf_rows_forward(const Ctx &cx, const float *img, const PfPlan &pl, float2 *blk, float2 *work,
+                                                const float2 *tw)
 {
     const int nx = pl.nx, P = pl.P, H = pl.H, o = pl.o, nb = pl.nb;
     float2 *wa = work, *wb = work + (size_t)nb * P;
     const int npair = (nx + 1) / 2;
-    // 1. forward row transforms, two rows per complex FFT
     for (int p0 = 0; p0 < npair; p0 += nb) {
         const int cnt = npair - p0 < nb ? npair - p0 : nb;
         for (int it = cx.tid; it < cnt * P; it += cx.nt) {
@@ -282,6 +284,51 @@ __host__ __device__ inline void pf_particle(const Ctx &cx, float *img, const PfC
         }
         cx.sync();
     }
+}
+
+// pass 3: inverse row transforms of blk [nx][H] (the window rows), the nx window outputs times 1 / P^2 into img [nx][nx]:
+// z = Xa + i Xb on the Hermitian extensions (imaginary parts of DC and Nyquist dropped, as c2r does)
+template <class Ctx>
+__host__ __device__ inline void pf_rows_inverse(const Ctx &cx, float *img, const PfPlan &pl, const float2 *blk, float2 *work,
+                                                const float2 *tw)
+{
+    const int nx = pl.nx, P = pl.P, H = pl.H, o = pl.o, nb = pl.nb;
+    float2 *wa = work, *wb = work + (size_t)nb * P;
+    const int npair = (nx + 1) / 2;
+    const float scale = 1.0f / ((float)P * (float)P);
+    for (int p0 = 0; p0 < npair; p0 += nb) {
+        const int cnt = npair - p0 < nb ? npair - p0 : nb;
+        for (int it = cx.tid; it < cnt * P; it += cx.nt) {
+            const int t = it / P, k = it - t * P, ya = 2 * (p0 + t), yb = ya + 1;
+            const bool lo = k < H;
+            const int kk = lo ? k : P - k;
+            const bool real = kk == 0 || 2 * kk == P;
+            float2 a = blk[(size_t)ya * H + kk], b = yb < nx ? blk[(size_t)yb * H + kk] : make_float2(0.f, 0.f);
+            if (real) { a.y = 0.f; b.y = 0.f; }
+            else if (!lo) { a.y = -a.y; b.y = -b.y; }
+            wa[it] = make_float2(a.x - b.y, a.y + b.x);
+        }
+        cx.sync();
+        const float2 *z = pf_fft(cx, wa, wb, cnt, pl, tw, 1.f);
+        for (int it = cx.tid; it < cnt * nx; it += cx.nt) {
+            const int t = it / nx, x = it - t * nx, ya = 2 * (p0 + t), yb = ya + 1;
+            const float2 v = z[(size_t)t * P + o + x];
+            img[(size_t)ya * nx + x] = v.x * scale;
+            if (yb < nx) img[(size_t)yb * nx + x] = v.y * scale;
+        }
+        cx.sync();
+    }
+}
+
+// the three passes over one particle; img [nx][nx] in place, blk [nx][H], work 2 x nb x P, tw [P] = exp(-2 pi i t / P)
+template <class Ctx>
+__host__ __device__ inline void pf_particle(const Ctx &cx, float *img, const PfCtf &cc, const PfPlan &pl, float2 *blk, float2 *work,
+                                            const float2 *tw)
+{
+    const int nx = pl.nx, P = pl.P, H = pl.H, o = pl.o, nb = pl.nb;
+    float2 *wa = work, *wb = work + (size_t)nb * P;
+    // 1. forward row transforms, two rows per complex FFT
+    pf_rows_forward(cx, img, pl, blk, work, tw);
     // 2. column transforms with the multiplier
     for (int c0 = 0; c0 < H; c0 += nb) {
         const int cnt = H - c0 < nb ? H - c0 : nb;
@@ -306,30 +353,8 @@ __host__ __device__ inline void pf_particle(const Ctx &cx, float *img, const PfC
         }
         cx.sync();
     }
-    // 3. inverse row transforms: z = Xa + i Xb on the Hermitian extensions (imaginary parts of DC and Nyquist dropped, as c2r does)
-    const float scale = 1.0f / ((float)P * (float)P);
-    for (int p0 = 0; p0 < npair; p0 += nb) {
-        const int cnt = npair - p0 < nb ? npair - p0 : nb;
-        for (int it = cx.tid; it < cnt * P; it += cx.nt) {
-            const int t = it / P, k = it - t * P, ya = 2 * (p0 + t), yb = ya + 1;
-            const bool lo = k < H;
-            const int kk = lo ? k : P - k;
-            const bool real = kk == 0 || 2 * kk == P;
-            float2 a = blk[(size_t)ya * H + kk], b = yb < nx ? blk[(size_t)yb * H + kk] : make_float2(0.f, 0.f);
-            if (real) { a.y = 0.f; b.y = 0.f; }
-            else if (!lo) { a.y = -a.y; b.y = -b.y; }
-            wa[it] = make_float2(a.x - b.y, a.y + b.x);
-        }
-        cx.sync();
-        const float2 *z = pf_fft(cx, wa, wb, cnt, pl, tw, 1.f);
-        for (int it = cx.tid; it < cnt * nx; it += cx.nt) {
-            const int t = it / nx, x = it - t * nx, ya = 2 * (p0 + t), yb = ya + 1;
-            const float2 v = z[(size_t)t * P + o + x];
-            img[(size_t)ya * nx + x] = v.x * scale;
-            if (yb < nx) img[(size_t)yb * nx + x] = v.y * scale;
-        }
-        cx.sync();
-    }
+    // 3. inverse row transforms
+    pf_rows_inverse(cx, img, pl, blk, work, tw);
 }
 
 // GBLK = false: block, work and twiddles in dynamic LDS, one workgroup per particle.  GBLK = true: the block in global scratch

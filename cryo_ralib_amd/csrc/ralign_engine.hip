@@ -28,6 +28,7 @@
 #include "ralign_tsne.h"
 #include "ralign_kmeans.h"
 #include "ralign_resize.h"
+#include "ralign_wiener.h"
 
 using namespace ralign;
 
@@ -2756,6 +2757,32 @@ extern "C" size_t ra_legacy_bytes(const unsigned int num_particles, const AlignC
 
 #define PF_GBLK_BYTES ((size_t)512 << 20)      // global scratch of the large-box route: the grid is sized to stay within it
 
+// the [n][9] CTF rows (host memory) within the ranges the flip and the Wiener averages accept; sets g_last_error naming the row
+static bool pf_rows_ok(const char *what, const float *ctf, int n)
+{
+    for (int i = 0; i < n; i++) {
+        const float *c = ctf + (size_t)i * 9;
+        bool finite = true;
+        for (int j = 0; j < 9; j++) finite = finite && std::isfinite(c[j]);
+        if (!finite || c[0] <= 0.f || c[1] <= 0.f || c[5] <= 0.f || c[7] < 0.f || c[7] >= 1.f) {
+            char buf[256];
+            snprintf(buf, sizeof(buf), "%s: CTF row %d out of range (needs finite values, D > 0, Apix > 0, "
+                     "voltage > 0, 0 <= w < 1)", what, i);
+            g_last_error = buf;
+            return false;
+        }
+    }
+    return true;
+}
+
+// workgroups of the global-block route: as many as fit on the chip at this LDS size (256 CUs), within PF_GBLK_BYTES of scratch
+static int pf_gblk_grid(const PfPlan &pl, int n)
+{
+    const size_t blk_bytes = (size_t)pl.nx * pl.H * sizeof(float2);
+    const size_t resident = (size_t)256 * std::max(1, std::min(4, (int)((size_t)160 * 1024 / pl.lds)));     // <= 32 waves per CU
+    return (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(resident, PF_GBLK_BYTES / blk_bytes)));
+}
+
 extern "C" int ra_phase_flip(float *d_images, int n, int nx, const float *ctf, int pad, void *hip_stream)
 {
     hipStream_t stream = (hipStream_t)hip_stream;
@@ -2765,18 +2792,7 @@ extern "C" int ra_phase_flip(float *d_images, int n, int nx, const float *ctf, i
     }
     if (n == 0) return RA_OK;
     if (!d_images || !ctf) { g_last_error = "ra_phase_flip: null argument"; return RA_ERR_ARG; }
-    for (int i = 0; i < n; i++) {
-        const float *c = ctf + (size_t)i * 9;
-        bool finite = true;
-        for (int j = 0; j < 9; j++) finite = finite && std::isfinite(c[j]);
-        if (!finite || c[0] <= 0.f || c[1] <= 0.f || c[5] <= 0.f || c[7] < 0.f || c[7] >= 1.f) {
-            char buf[256];
-            snprintf(buf, sizeof(buf), "ra_phase_flip: CTF row %d out of range (needs finite values, D > 0, Apix > 0, "
-                     "voltage > 0, 0 <= w < 1)", i);
-            g_last_error = buf;
-            return RA_ERR_ARG;
-        }
-    }
+    if (!pf_rows_ok("ra_phase_flip", ctf, n)) return RA_ERR_ARG;
     const PfPlan pl = pf_make_plan(nx, pad);
     if (pl.nb < 1) { g_last_error = "ra_phase_flip: no plan for this box"; return RA_ERR_ARG; }
     // the common boxes run a kernel specialised for their plan; any other box the kernel that takes the plan as an argument
@@ -2793,10 +2809,8 @@ extern "C" int ra_phase_flip(float *d_images, int n, int nx, const float *ctf, i
     const bool fixed = fk != nullptr;
     if (!fixed) fk = pl.gblk ? (const void *)phase_flip_kernel<true> : (const void *)phase_flip_kernel<false>;
     RA_HIP(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
-    // the global-block route: as many workgroups as fit on the chip at this LDS size (256 CUs), within PF_GBLK_BYTES of scratch
     const size_t blk_bytes = (size_t)nx * pl.H * sizeof(float2);
-    const size_t resident = (size_t)256 * std::max(1, std::min(4, (int)((size_t)160 * 1024 / pl.lds)));     // <= 32 waves per CU
-    const int grid = pl.gblk ? (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(resident, PF_GBLK_BYTES / blk_bytes))) : n;
+    const int grid = pl.gblk ? pf_gblk_grid(pl, n) : n;
     float *d_ctf = nullptr;
     float2 *d_scr = nullptr;
     RA_HIP(hipMallocAsync((void **)&d_ctf, (size_t)n * 9 * sizeof(float), stream));
@@ -3310,4 +3324,194 @@ extern "C" int ra_fourier_resize(const float *d_in, int n, int nx, int m, float 
     }
     (void)hipFreeAsync(Ap, stream);
     return he == hipSuccess ? RA_OK : sdr_launch_error("ra_fourier_resize", he);
+}
+
+// ---- CTF-corrected (Wiener) class averages (ralign_wiener.h)
+
+// the forward kernel of a box: specialised for the boxes the benchmarks know, else the one that takes the plan as an argument
+static const void *wn_forward_fn(int nx, int pad, const PfPlan &pl, bool *fixed)
+{
+    const void *fk = nullptr;
+    switch (nx * 2 + pad) {
+    case 90 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<90, 1>; break;
+    case 90 * 2: fk = (const void *)wn_forward_fixed_kernel<90, 0>; break;
+    case 100 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<100, 1>; break;
+    case 128 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<128, 1>; break;
+    case 130 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<130, 1>; break;
+    case 256 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<256, 1>; break;
+    default: break;
+    }
+    *fixed = fk != nullptr;
+    if (!fk) fk = pl.gblk ? (const void *)wn_forward_kernel<true> : (const void *)wn_forward_kernel<false>;
+    return fk;
+}
+
+extern "C" int ra_wiener_accumulate(const float *d_images, int n, int nx, const ra_result *d_params, const float *h_ctf, int pad,
+                                    int flipped, int k, float *d_num, float *d_den, int *d_counts, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 0 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || (flipped != 0 && flipped != 1) || k < 1 || k > 1024) {
+        g_last_error = "ra_wiener_accumulate: need n >= 0, 2 <= nx <= 1024, pad and flipped 0 or 1, 1 <= k <= 1024";
+        return RA_ERR_ARG;
+    }
+    if (n == 0) return RA_OK;
+    if (!d_images || !d_params || !h_ctf || !d_num || !d_den || !d_counts) {
+        g_last_error = "ra_wiener_accumulate: null argument";
+        return RA_ERR_ARG;
+    }
+    if (!pf_rows_ok("ra_wiener_accumulate", h_ctf, n)) return RA_ERR_ARG;
+    const PfPlan pl = pf_make_plan(nx, pad);
+    if (pl.nb < 1) { g_last_error = "ra_wiener_accumulate: no plan for this box"; return RA_ERR_ARG; }
+    const int P = pl.P, H = pl.H, npix = nx * nx;
+    const size_t ph = (size_t)P * H;
+
+    // 1. classes, finiteness and CTF constants on the device; the verdict and the classes come back before anything is summed
+    float *d_ctf = nullptr;
+    WnCtf *d_cst = nullptr;
+    int *d_lab = nullptr;
+    std::vector<int> lab((size_t)n + 1);
+    hipError_t he = hipMallocAsync((void **)&d_ctf, (size_t)n * 9 * sizeof(float), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_cst, (size_t)n * sizeof(WnCtf), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_lab, ((size_t)n + 1) * sizeof(int), stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_ctf, h_ctf, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess) he = hipMemsetD32Async((hipDeviceptr_t)(d_lab + n), n, 1, stream);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(wn_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_params, (const float *)d_ctf, n, nx, P, k, d_cst,
+                           d_lab, d_lab + n);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(lab.data(), d_lab, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    auto release = [&]() {
+        if (d_lab) (void)hipFreeAsync(d_lab, stream);
+        if (d_cst) (void)hipFreeAsync(d_cst, stream);
+        if (d_ctf) (void)hipFreeAsync(d_ctf, stream);
+    };
+    if (he != hipSuccess) { release(); return sdr_launch_error("ra_wiener_accumulate", he); }
+    if (lab[n] < n) {
+        const int i = lab[n];
+        char buf[256];
+        if (lab[i] < 0 || lab[i] >= k)
+            snprintf(buf, sizeof(buf), "ra_wiener_accumulate: particle %d has class label %d outside 0 .. %d", i, lab[i], k - 1);
+        else
+            snprintf(buf, sizeof(buf), "ra_wiener_accumulate: particle %d has non-finite params (alpha, sx, sy)", i);
+        g_last_error = buf;
+        release();
+        return RA_ERR_ARG;
+    }
+
+    // 2. chunks within the scratch budget; per chunk the members of every class in particle order, cut into runs so that the
+    //    reduce has enough workgroups (element blocks x runs ~ WN_BLOCKS_TARGET); a class of several runs gets partial slots
+    const int eblk = (int)((ph + WN_THREADS - 1) / WN_THREADS);
+    const int T = std::max(1, std::min(WN_MAX_RUNS, WN_BLOCKS_TARGET / eblk));
+    const int C = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, WN_SCRATCH_BYTES / (ph * sizeof(float2) + (size_t)npix * sizeof(float))));
+    std::vector<int> perm(n);
+    std::vector<WnRun> runs;
+    std::vector<int4> segs;
+    std::vector<int> run0, seg0;        // per chunk: first run / seg
+    std::vector<int> start(k + 1);
+    int slots = 0;
+    for (int c0 = 0; c0 < n; c0 += C) {
+        const int cnt = std::min(C, n - c0), L = (cnt + T - 1) / T;
+        run0.push_back((int)runs.size());
+        seg0.push_back((int)segs.size());
+        std::fill(start.begin(), start.end(), 0);
+        for (int i = 0; i < cnt; i++) start[lab[c0 + i] + 1]++;
+        for (int j = 0; j < k; j++) start[j + 1] += start[j];
+        std::vector<int> fill(start.begin(), start.end() - 1);
+        for (int i = 0; i < cnt; i++) perm[c0 + fill[lab[c0 + i]]++] = i;
+        int slot = 0;
+        for (int j = 0; j < k; j++) {
+            const int b = start[j], e = start[j + 1], s = e - b;
+            if (s == 0) continue;
+            if (s <= L) { runs.push_back(WnRun{j, b, e, -1}); continue; }
+            const int s0 = slot;
+            for (int r = b; r < e; r += L) runs.push_back(WnRun{j, r, std::min(e, r + L), slot++});
+            segs.push_back(make_int4(j, s0, slot, s));
+        }
+        slots = std::max(slots, slot);
+    }
+    run0.push_back((int)runs.size());
+    seg0.push_back((int)segs.size());
+
+    // 3. per chunk: rot_shift2D, forward transforms, reduce, combine
+    float *d_al = nullptr, *d_pden = nullptr;
+    float2 *d_spec = nullptr, *d_gscr = nullptr, *d_pnum = nullptr;
+    int *d_perm = nullptr;
+    WnRun *d_runs = nullptr;
+    int4 *d_segs = nullptr;
+    bool fixed = false;
+    const void *fk = wn_forward_fn(nx, pad, pl, &fixed);
+    const int fgrid = pl.gblk ? pf_gblk_grid(pl, C) : 0;
+    he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_al, (size_t)C * npix * sizeof(float), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_spec, (size_t)C * ph * sizeof(float2), stream);
+    if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)fgrid * nx * H * sizeof(float2), stream);
+    if (he == hipSuccess && slots) he = hipMallocAsync((void **)&d_pnum, (size_t)slots * ph * sizeof(float2), stream);
+    if (he == hipSuccess && slots) he = hipMallocAsync((void **)&d_pden, (size_t)slots * ph * sizeof(float), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_perm, (size_t)n * sizeof(int), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_runs, runs.size() * sizeof(WnRun), stream);
+    if (he == hipSuccess && !segs.empty()) he = hipMallocAsync((void **)&d_segs, segs.size() * sizeof(int4), stream);
+    // pageable host sources: hipMemcpyAsync stages them before it returns
+    if (he == hipSuccess) he = hipMemcpyAsync(d_perm, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(d_runs, runs.data(), runs.size() * sizeof(WnRun), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess && !segs.empty()) he = hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(int4), hipMemcpyHostToDevice, stream);
+    int rc = RA_OK;
+    for (int c = 0, c0 = 0; c0 < n && he == hipSuccess && rc == RA_OK; c++, c0 += C) {
+        int cnt = std::min(C, n - c0);
+        rc = ra_rot_shift2d(d_images + (size_t)c0 * npix, cnt, nx, d_params + c0, d_al, stream);
+        if (rc != RA_OK) break;
+        const float *al = d_al;
+        void *args_fixed[] = {&al, &cnt, &d_spec, &d_gscr};
+        PfPlan pl_arg = pl;
+        void *args_plan[] = {&al, &cnt, &d_spec, &pl_arg, &d_gscr};
+        he = hipLaunchKernel(fk, dim3(pl.gblk ? std::min(fgrid, cnt) : cnt), dim3(PF_THREADS), fixed ? args_fixed : args_plan, pl.lds, stream);
+        if (he == hipSuccess) he = hipGetLastError();
+        const int nrun = run0[c + 1] - run0[c], nseg = seg0[c + 1] - seg0[c];
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(wn_reduce_kernel, dim3(eblk, nrun), dim3(WN_THREADS), 0, stream, (const float2 *)d_spec, P, H,
+                               (const WnRun *)(d_runs + run0[c]), (const int *)(d_perm + c0), (const WnCtf *)(d_cst + c0), flipped,
+                               (float2 *)d_num, d_den, d_counts, d_pnum, d_pden);
+            he = hipGetLastError();
+        }
+        if (he == hipSuccess && nseg) {
+            hipLaunchKernelGGL(wn_combine_kernel, dim3(eblk, nseg), dim3(WN_THREADS), 0, stream, P, H, (const int4 *)(d_segs + seg0[c]),
+                               (const float2 *)d_pnum, (const float *)d_pden, (float2 *)d_num, d_den, d_counts);
+            he = hipGetLastError();
+        }
+    }
+    for (void *p : {(void *)d_segs, (void *)d_runs, (void *)d_perm, (void *)d_pden, (void *)d_pnum, (void *)d_gscr, (void *)d_spec, (void *)d_al})
+        if (p) (void)hipFreeAsync(p, stream);
+    release();
+    if (rc != RA_OK) return rc;
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_accumulate", he);
+}
+
+extern "C" int ra_wiener_finalize(const float *d_num, const float *d_den, const int *d_counts, int k, int nx, int pad, float snr,
+                                  int min_count, float *d_out, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (k < 1 || k > 1024 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || !(snr > 0.f) || !std::isfinite(snr)) {
+        g_last_error = "ra_wiener_finalize: need 1 <= k <= 1024, 2 <= nx <= 1024, pad 0 or 1 and a finite snr > 0";
+        return RA_ERR_ARG;
+    }
+    if (!d_num || !d_den || !d_counts || !d_out) { g_last_error = "ra_wiener_finalize: null argument"; return RA_ERR_ARG; }
+    const PfPlan pl = pf_make_plan(nx, pad);
+    if (pl.nb < 1) { g_last_error = "ra_wiener_finalize: no plan for this box"; return RA_ERR_ARG; }
+    const void *fk = pl.gblk ? (const void *)wn_finalize_kernel<true> : (const void *)wn_finalize_kernel<false>;
+    hipError_t he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (he != hipSuccess) return sdr_launch_error("ra_wiener_finalize", he);
+    const int grid = pl.gblk ? pf_gblk_grid(pl, k) : k;
+    float2 *d_gscr = nullptr;
+    if (pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)grid * nx * pl.H * sizeof(float2), stream);
+    if (he == hipSuccess) {
+        const float2 *num = (const float2 *)d_num;
+        float inv_snr = 1.0f / snr;
+        PfPlan pl_arg = pl;
+        void *args[] = {&num, &d_den, &d_counts, &k, &inv_snr, &min_count, &d_out, &pl_arg, &d_gscr};
+        he = hipLaunchKernel(fk, dim3(grid), dim3(PF_THREADS), args, pl.lds, stream);
+        if (he == hipSuccess) he = hipGetLastError();
+    }
+    if (d_gscr) (void)hipFreeAsync(d_gscr, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_finalize", he);
 }

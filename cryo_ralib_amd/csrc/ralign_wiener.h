@@ -1,0 +1,254 @@
+// CTF-corrected (Wiener-filtered) class averages (ra_wiener_accumulate / ra_wiener_finalize).
+//
+// Contract (cryo_ralib_amd/wiener.py: wiener_reference): per particle i, y_i = rot_shift2D(x_i), embedded at o = (P - nx) / 2 in a
+// P x P zero image, Y_i = rfft2 on the [P][P/2 + 1] grid; c_i = the CTF of the particle's [9] row with the astigmatism angle taken
+// into the aligned frame (DefocusAngle - alpha, or alpha - DefocusAngle for a mirrored particle); w_i = c_i, or |c_i| for
+// phase-flipped particles.  Per class j: N_j = sum w_i Y_i, D_j = sum c_i^2, A_j = crop_o(irfft2(N_j / (D_j + 1/snr))).
+//
+// Accumulation, per chunk of particles (its size fixed by a scratch budget, never by n):
+//   1. wn_prep_kernel: per particle the CTF constants in the aligned frame (double, kept on the device for the chunk kernels) and
+//      its class; labels outside 0 .. k-1 or non-finite alpha / sx / sy are reported (lowest index) before anything is summed;
+//   2. ra_rot_shift2d's transform of the chunk into scratch;
+//   3. wn_forward_kernel: the phase flip's forward row pass (ralign_ctf.h) and forward column FFTs of the P/2 + 1 columns, the
+//      spectrum [H][P] (column-major) of every particle written to scratch unweighted;
+//   4. wn_reduce_kernel: one thread per spectrum element and one workgroup row per run of class members (the chunk's particles
+//      sorted stably by class on the host): sum w Y and c^2 over the run in double, in particle order, with c recomputed from the
+//      constants; a class of one run adds straight into d_num / d_den, the runs of a longer class go to partial slots that
+//   5. wn_combine_kernel adds in run order.  Every accumulator element has one owner per launch: no atomics on the sums, a fixed
+//      association, bitwise reproducible.
+// Finalize: wn_finalize_kernel, one workgroup per class (looping when the block lives in global scratch): N / (D + 1/snr) into
+// inverse column FFTs over the full height (N is dense), the nx window rows kept, then the phase flip's inverse row pass.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include "ralign_ctf.h"
+#include "../../include/ralign.h"
+
+namespace ralign {
+
+#define WN_THREADS 256              // reduce / combine workgroup
+#define WN_SCRATCH_BYTES ((size_t)1 << 30)      // spectra + aligned images of one chunk
+#define WN_BLOCKS_TARGET 2048       // workgroups the reduce aims for: runs per chunk = this / element blocks, within 1 .. 64
+#define WN_MAX_RUNS 64
+
+// CTF constants of one particle in the aligned frame, doubles; l3 = lam^3 folded in
+struct WnCtf {
+    double q, dsum, ddif, c2a, s2a, lam, cl3, phi0;
+};
+
+__host__ __device__ inline WnCtf wn_constants(const float *row, int nx, int P, float alpha, int mirror)
+{
+    const double ang = mirror ? (double)alpha - (double)row[4] : (double)row[4] - (double)alpha;
+    const PfCtf c = pf_ctf_constants_at(row, nx, P, ang);
+    WnCtf w;
+    w.q = c.q; w.dsum = c.dsum; w.ddif = c.ddif; w.c2a = c.c2a; w.s2a = c.s2a; w.lam = c.lam;
+    w.cl3 = c.cs * c.lam * c.lam * c.lam;
+    w.phi0 = c.phi0;
+    return w;
+}
+
+// ctf(iy, ix) = sin(gamma - asin w) = sin(2 pi u), u as in pf_multiplier, reduced to [-1/2, 1/2) in double before the float sine
+__host__ __device__ inline float wn_ctf(const WnCtf &c, int iy, int ix)
+{
+    const double x = ix, y = iy, r2 = x * x + y * y;
+    double df = c.dsum;
+    if (r2 > 0.0) df += c.ddif * (((x * x - y * y) * c.c2a + 2.0 * x * y * c.s2a) / r2);
+    const double s2 = r2 * c.q;
+    const double u = -0.5 * df * c.lam * s2 + 0.25 * c.cl3 * s2 * s2 - c.phi0;
+    double fr = u - floor(u);
+    if (fr >= 0.5) fr -= 1.0;
+    return sinf(6.28318530717958648f * (float)fr);
+}
+
+// the forward transform of one aligned image: img [nx][nx] -> spec [H][P] (column kx, then the P row frequencies)
+template <class Ctx>
+__host__ __device__ inline void wn_forward(const Ctx &cx, const float *img, float2 *spec, const PfPlan &pl, float2 *blk, float2 *work,
+                                           const float2 *tw)
+{
+    const int nx = pl.nx, P = pl.P, H = pl.H, o = pl.o, nb = pl.nb;
+    float2 *wa = work, *wb = work + (size_t)nb * P;
+    pf_rows_forward(cx, img, pl, blk, work, tw);
+    for (int c0 = 0; c0 < H; c0 += nb) {
+        const int cnt = H - c0 < nb ? H - c0 : nb;
+        for (int it = cx.tid; it < cnt * P; it += cx.nt) {
+            const int t = it / P, n = it - t * P, y = n - o;
+            wa[it] = (y >= 0 && y < nx) ? blk[(size_t)y * H + c0 + t] : make_float2(0.f, 0.f);
+        }
+        cx.sync();
+        const float2 *z = pf_fft(cx, wa, wb, cnt, pl, tw, -1.f);
+        for (int it = cx.tid; it < cnt * P; it += cx.nt) spec[(size_t)c0 * P + it] = z[it];
+        cx.sync();
+    }
+}
+
+// one class: num [P][H], den [P][H] -> img [nx][nx]; inverse column FFTs of num / (den + 1/snr), the nx window rows into blk,
+// the inverse row pass
+template <class Ctx>
+__host__ __device__ inline void wn_class(const Ctx &cx, const float2 *num, const float *den, float inv_snr, float *img, const PfPlan &pl,
+                                         float2 *blk, float2 *work, const float2 *tw)
+{
+    const int nx = pl.nx, P = pl.P, H = pl.H, o = pl.o, nb = pl.nb;
+    float2 *wa = work, *wb = work + (size_t)nb * P;
+    for (int c0 = 0; c0 < H; c0 += nb) {
+        const int cnt = H - c0 < nb ? H - c0 : nb;
+        for (int it = cx.tid; it < cnt * P; it += cx.nt) {
+            const int t = it / P, n = it - t * P;
+            const size_t e = (size_t)n * H + c0 + t;
+            const float g = 1.0f / (den[e] + inv_snr);
+            wa[it] = make_float2(num[e].x * g, num[e].y * g);
+        }
+        cx.sync();
+        const float2 *z = pf_fft(cx, wa, wb, cnt, pl, tw, 1.f);
+        for (int it = cx.tid; it < cnt * nx; it += cx.nt) {
+            const int t = it / nx, y = it - t * nx;
+            blk[(size_t)y * H + c0 + t] = z[(size_t)t * P + o + y];
+        }
+        cx.sync();
+    }
+    pf_rows_inverse(cx, img, pl, blk, work, tw);
+}
+
+// per particle: class, finiteness, CTF constants in the aligned frame; *bad = the lowest offending index (n: none)
+__global__ void wn_prep_kernel(const ra_result *__restrict__ prm, const float *__restrict__ ctf, int n, int nx, int P, int k,
+                               WnCtf *__restrict__ cst, int *__restrict__ lab, int *__restrict__ bad)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ra_result r = prm[i];
+    const bool ok = r.ref_id >= 0 && r.ref_id < k && isfinite(r.alpha) && isfinite(r.sx) && isfinite(r.sy);
+    lab[i] = r.ref_id;
+    if (!ok) {
+        atomicMin(bad, i);
+        return;
+    }
+    cst[i] = wn_constants(ctf + (size_t)i * 9, nx, P, r.alpha, r.mirror != 0);
+}
+
+template <bool GBLK>
+__device__ inline void wn_forward_body(const float *imgs, int n, float2 *spec, const PfPlan &pl, float2 *gscr)
+{
+    extern __shared__ float2 pf_lds[];
+    const int P = pl.P;
+    float2 *tw = pf_lds;
+    float2 *work = pf_lds + P;
+    float2 *blk = GBLK ? gscr + (size_t)blockIdx.x * pl.nx * pl.H : work + (size_t)2 * pl.nb * P;
+    PfCtx cx{(int)threadIdx.x, PF_THREADS};
+    for (int t = cx.tid; t < P; t += cx.nt) {
+        double s, c;
+        sincospi(-2.0 * t / P, &s, &c);
+        tw[t] = make_float2((float)c, (float)s);
+    }
+    __syncthreads();
+    for (int p = blockIdx.x; p < n; p += gridDim.x)
+        wn_forward(cx, imgs + (size_t)p * pl.nx * pl.nx, spec + (size_t)p * pl.H * P, pl, blk, work, tw);
+}
+
+template <bool GBLK>
+__global__ __launch_bounds__(PF_THREADS) void wn_forward_kernel(const float *__restrict__ imgs, int n, float2 *__restrict__ spec, PfPlan pl,
+                                                                float2 *__restrict__ gscr)
+{
+    wn_forward_body<GBLK>(imgs, n, spec, pl, gscr);
+}
+
+// the boxes the benchmarks know: the plan is a compile-time constant, as for phase_flip_fixed_kernel
+template <int NX, int PAD>
+__global__ __launch_bounds__(PF_THREADS) void wn_forward_fixed_kernel(const float *__restrict__ imgs, int n, float2 *__restrict__ spec,
+                                                                      float2 *__restrict__ gscr)
+{
+    constexpr PfPlan pl = pf_make_plan(NX, PAD);
+    static_assert(pl.nb > 0, "no plan");
+    wn_forward_body<pl.gblk != 0>(imgs, n, spec, pl, gscr);
+}
+
+// one run of class members: run r = (class, first, end) into perm (chunk-local particle indices sorted by class, stable), dst < 0:
+// the class's only run this chunk, added into num / den (and its size into counts); else partial slot dst
+struct WnRun {
+    int cls, b, e, dst;
+};
+
+__global__ __launch_bounds__(WN_THREADS) void wn_reduce_kernel(const float2 *__restrict__ spec, int P, int H, const WnRun *__restrict__ runs,
+                                                               const int *__restrict__ perm, const WnCtf *__restrict__ cst, int flipped,
+                                                               float2 *__restrict__ num, float *__restrict__ den, int *__restrict__ counts,
+                                                               float2 *__restrict__ pnum, float *__restrict__ pden)
+{
+    const WnRun run = runs[blockIdx.y];
+    const size_t ph = (size_t)P * H;
+    const int e = blockIdx.x * WN_THREADS + threadIdx.x;
+    if (run.dst < 0 && blockIdx.x == 0 && threadIdx.x == 0) counts[run.cls] += run.e - run.b;
+    if (e >= (int)ph) return;
+    const int kx = e / P, n = e - kx * P;
+    const int iy = n < (P + 1) / 2 ? n : n - P;
+    double ax = 0.0, ay = 0.0, d = 0.0;
+    for (int m = run.b; m < run.e; m++) {
+        const int p = perm[m];
+        const float c = wn_ctf(cst[p], iy, kx);
+        const float w = flipped ? fabsf(c) : c;
+        const float2 y = spec[(size_t)p * ph + e];
+        ax += (double)(w * y.x);
+        ay += (double)(w * y.y);
+        d += (double)(c * c);
+    }
+    if (run.dst < 0) {
+        const size_t o = (size_t)run.cls * ph + (size_t)n * H + kx;
+        num[o] = make_float2(num[o].x + (float)ax, num[o].y + (float)ay);
+        den[o] += (float)d;
+    } else {
+        const size_t o = (size_t)run.dst * ph + e;
+        pnum[o] = make_float2((float)ax, (float)ay);
+        pden[o] = (float)d;
+    }
+}
+
+// a class of several runs: its partial slots [s0, s1) added in order; seg = (class, s0, s1, members)
+__global__ __launch_bounds__(WN_THREADS) void wn_combine_kernel(int P, int H, const int4 *__restrict__ segs, const float2 *__restrict__ pnum,
+                                                                const float *__restrict__ pden, float2 *__restrict__ num, float *__restrict__ den,
+                                                                int *__restrict__ counts)
+{
+    const int4 s = segs[blockIdx.y];
+    const size_t ph = (size_t)P * H;
+    const int e = blockIdx.x * WN_THREADS + threadIdx.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0) counts[s.x] += s.w;
+    if (e >= (int)ph) return;
+    double ax = 0.0, ay = 0.0, d = 0.0;
+    for (int r = s.y; r < s.z; r++) {
+        const float2 v = pnum[(size_t)r * ph + e];
+        ax += v.x;
+        ay += v.y;
+        d += pden[(size_t)r * ph + e];
+    }
+    const int kx = e / P, n = e - kx * P;
+    const size_t o = (size_t)s.x * ph + (size_t)n * H + kx;
+    num[o] = make_float2(num[o].x + (float)ax, num[o].y + (float)ay);
+    den[o] += (float)d;
+}
+
+template <bool GBLK>
+__global__ __launch_bounds__(PF_THREADS) void wn_finalize_kernel(const float2 *__restrict__ num, const float *__restrict__ den,
+                                                                 const int *__restrict__ counts, int k, float inv_snr, int min_count,
+                                                                 float *__restrict__ out, PfPlan pl, float2 *__restrict__ gscr)
+{
+    extern __shared__ float2 pf_lds[];
+    const int P = pl.P, nx = pl.nx;
+    const size_t ph = (size_t)P * pl.H;
+    float2 *tw = pf_lds;
+    float2 *work = pf_lds + P;
+    float2 *blk = GBLK ? gscr + (size_t)blockIdx.x * nx * pl.H : work + (size_t)2 * pl.nb * P;
+    PfCtx cx{(int)threadIdx.x, PF_THREADS};
+    for (int t = cx.tid; t < P; t += cx.nt) {
+        double s, c;
+        sincospi(-2.0 * t / P, &s, &c);
+        tw[t] = make_float2((float)c, (float)s);
+    }
+    __syncthreads();
+    for (int j = blockIdx.x; j < k; j += gridDim.x) {
+        float *img = out + (size_t)j * nx * nx;
+        if (counts[j] < min_count) {
+            for (int i = cx.tid; i < nx * nx; i += cx.nt) img[i] = 0.f;
+            continue;
+        }
+        wn_class(cx, num + (size_t)j * ph, den + (size_t)j * ph, inv_snr, img, pl, blk, work, tw);
+    }
+}
+
+}  // namespace ralign

@@ -317,6 +317,28 @@ int  ra_phase_flip(float *d_images, int n, int nx, const float *h_ctf, int pad, 
  * independent of the others and of its place in the batch. */
 int  ra_fourier_resize(const float *d_in, int n, int nx, int m, float *d_out, void *hip_stream);
 
+/* CTF-corrected (Wiener-filtered) class averages without an engine (contract: cryo_ralib_amd/wiener.py
+ * wiener_reference).  Per particle i: Y_i = rfft2 of rot_shift2D(x_i) (d_params[i]: alpha, sx, sy, mirror as ra_rot_shift2d;
+ * ref_id = the class) embedded at o = (P - nx) / 2 in a P x P zero image (P = 2 nx with pad = 1, nx with pad = 0); c_i = the CTF
+ * of its [9] row (ra_phase_flip's layout) with DefocusAngle - alpha (mirror 0) or alpha - DefocusAngle (mirror 1) as the
+ * astigmatism angle; w_i = c_i, or |c_i| with flipped = 1 (phase-flipped particles).
+ *   ra_wiener_accumulate  adds N_j += sum w_i Y_i into d_num [k][P][P/2 + 1] (complex, float2), D_j += sum c_i^2 into
+ *                         d_den [k][P][P/2 + 1] and the class sizes into d_counts [k]; the caller zeroes them, so a stack can be
+ *                         streamed through in chunks and ranks can all-reduce the sums before finalising.  h_ctf [n][9] is
+ *                         host memory, checked with ra_phase_flip's rules before anything is launched; a label outside
+ *                         0 .. k - 1 or non-finite alpha / sx / sy is found by a check on the device whose verdict is read back
+ *                         (a stream synchronisation) before any sum is written.  RA_ERR_ARG, the sums untouched, for those and
+ *                         for n < 0, nx outside 2 .. 1024, pad or flipped not 0 / 1, k outside 1 .. 1024 or a null pointer;
+ *                         n == 0 is a no-op.  Scratch is bounded by a fixed budget (chunks of particles), not by n.
+ *   ra_wiener_finalize    d_out [k][nx][nx] = crop_o(irfft2(N_j / (D_j + 1/snr))); classes with d_counts[j] < min_count are
+ *                         zero.  1 <= k <= 1024, 2 <= nx <= 1024, pad 0 / 1, finite snr > 0.
+ * Asynchronous on hip_stream (a hipStream_t; NULL = default stream) apart from the verdict above; no floating-point atomics and
+ * a fixed order of every sum: the same calls give bitwise-equal results. */
+int  ra_wiener_accumulate(const float *d_images, int n, int nx, const ra_result *d_params, const float *h_ctf, int pad, int flipped,
+                          int k, float *d_num, float *d_den, int *d_counts, void *hip_stream);
+int  ra_wiener_finalize(const float *d_num, const float *d_den, const int *d_counts, int k, int nx, int pad, float snr, int min_count,
+                        float *d_out, void *hip_stream);
+
 /* Two-stage dimension reduction (utils_ralib.py MPCA / TwoSDR) of a stack in device memory, without an engine (DESIGN.md
  * section 4.6).  All pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL = default stream)
  * and allocates and frees its scratch on that stream, as ra_phase_flip does.  Images are [n][p][q] float32, centred on load
