@@ -26,6 +26,9 @@ reads the parameters from the stack's EMAN.ctf headers, stays rejected.
 --wiener_averages (with --phase_flip and --snr > 0) writes, after the last iteration, CTF-corrected class averages of the
 flipped particles with the final parameters (cryo_ralib_amd.wiener, flipped weights |c|, the flip's padding):
 multi_ref_wiener.<ext> (one per class) or aqfinal_wiener.<ext> (one image).  Ranks sum their spectra before the division.
+--wiener_ssnr (with --wiener_averages) also writes the SSNR-weighted averages, whose per-shell term comes from the FRC of the
+even / odd half sets (global particle index), and each class's resolution at FRC 0.5 and 0.143: multi_ref_wiener_ssnr.<ext> and
+multi_ref_wiener_frc.txt, or aqfinal_wiener_ssnr.<ext> and aqfinal_wiener_frc.txt; --snr then only sets the half averages.
 """
 import argparse
 import os
@@ -56,6 +59,10 @@ def _common(p):
     p.add_argument("--wiener_averages", action="store_true",
                    help="after the last iteration also write CTF-corrected (Wiener) class averages, sum c^2 + 1/snr in the "
                         "denominator: multi_ref_wiener.<ext> / aqfinal_wiener.<ext>; needs --phase_flip")
+    p.add_argument("--wiener_ssnr", action="store_true",
+                   help="with --wiener_averages: also write SSNR-weighted averages (per-shell term from the half-set FRC) and the "
+                        "classes' resolutions: multi_ref_wiener_ssnr.<ext> + multi_ref_wiener_frc.txt / aqfinal_wiener_ssnr.<ext> + "
+                        "aqfinal_wiener_frc.txt")
     p.add_argument("--ext", default="hdf", help="format of the written stacks: hdf (EMAN2 MDF, as the reference) | mrcs | npy")
     p.add_argument("--header_writeback", action="store_true",
                    help="write xform.align2d / assign / ID into the headers of the HDF INPUT stack itself, as the reference does "
@@ -155,29 +162,53 @@ def _check_wiener(p, args):
         p.error("--wiener_averages needs --phase_flip TABLE (the CTF table of the particles)")
     if args.wiener_averages and not args.snr > 0:
         p.error("--wiener_averages needs --snr > 0, got %g" % args.snr)
+    if args.wiener_ssnr and not args.wiener_averages:
+        p.error("--wiener_ssnr needs --wiener_averages")
 
 
-def _write_wiener(args, al, total, lo, hi, labels, k, name, rank, world):
-    """CTF-corrected averages of the aligner's flipped particles with its final params; sums all-reduced over the ranks"""
-    from . import stackio, wiener
-    nx = al.nx
-    pad = not args.phase_flip_nopad
-    r = al.params()
-    prm = np.column_stack([r["alpha"], r["sx"], r["sy"], r["mirror"]]).astype(np.float64)
-    num, den, counts = wiener.new_sums(k, nx, pad, al.dev)
-    wiener.accumulate(al.particles, prm, labels, k, _ctf_shard(args, total, nx, lo, hi), num, den, counts, pad, flipped=True)
+def _sum_over_ranks(tensors, world):
     if world > 1:
         import torch.distributed as td
-        for t in (num, den, counts):
+        for t in tensors:
             if td.get_backend() == "gloo":      # gloo rehearsal of several ranks on one GPU: the collective runs on a host copy
                 h = t.cpu()
                 td.all_reduce(h, op=td.ReduceOp.SUM)
                 t.copy_(h)
             else:
                 td.all_reduce(t, op=td.ReduceOp.SUM)
+
+
+def _write_wiener(args, al, total, lo, hi, labels, k, name, rank, world):
+    """CTF-corrected averages of the aligner's flipped particles with its final params; sums all-reduced over the ranks.  With
+    --wiener_ssnr also the SSNR-weighted averages (<name>_ssnr.<ext>) and the classes' resolutions (<name>_frc.txt)"""
+    from . import stackio, wiener
+    nx = al.nx
+    pad = not args.phase_flip_nopad
+    r = al.params()
+    prm = np.column_stack([r["alpha"], r["sx"], r["sy"], r["mirror"]]).astype(np.float64)
+    tab = _ctf_shard(args, total, nx, lo, hi)
+    num, den, counts = wiener.new_sums(k, nx, pad, al.dev)
+    wiener.accumulate(al.particles, prm, labels, k, tab, num, den, counts, pad, flipped=True)
+    _sum_over_ranks((num, den, counts), world)
     out = wiener.finalize(num, den, counts, nx, pad, args.snr, min_count=1)
     if rank == 0:
         stackio.write_stack(os.path.join(args.outdir, "%s.%s" % (name, args.ext)), out.cpu().numpy())
+    if not args.wiener_ssnr:
+        return
+    num2, den2, counts2 = wiener.new_half_sums(k, nx, pad, al.dev)
+    wiener.accumulate_halves(al.particles, prm, labels, k, tab, num2, den2, counts2, index0=lo, pad=pad, flipped=True)
+    _sum_over_ranks((num2, den2, counts2), world)
+    f, reg = wiener.frc(num2, den2, counts2, nx, pad, args.snr, 1, wiener.SSNR_FLOOR)
+    out = wiener.finalize_ssnr(num2, den2, counts2, reg, nx, pad, 1)
+    if rank == 0:
+        stackio.write_stack(os.path.join(args.outdir, "%s_ssnr.%s" % (name, args.ext)), out.cpu().numpy())
+        apix = args.apix if args.apix is not None else wiener.table_apix(_ctf_shard(args, total, nx, 0, total), nx)
+        counts = counts2.sum(1).cpu().numpy()
+        res = wiener.resolutions(f.cpu().numpy(), counts, nx, pad, apix)
+        with open(os.path.join(args.outdir, "%s_frc.txt" % name), "w") as fh:
+            fh.write("# class count res_0.5 res_0.143 (%s)\n" % ("A" if apix is not None else "pixels: the CTF table gives no single pixel size"))
+            for j in range(k):
+                fh.write("%d %d %.6g %.6g\n" % (j, counts[j], res["res_05"][j], res["res_0143"][j]))
 
 
 def _setup(args):
@@ -218,6 +249,8 @@ def main_mref(argv=None):
     lo, hi = rdist.shard_range(total, world, rank)
     data = stackio.read_stack(args.stack, lo, hi)                # every rank reads its own slice only (:1358-1375)
     refs = stackio.read_stack(args.refstack)
+    if args.wiener_ssnr and len(refs) > 512:
+        p.error("--wiener_ssnr takes at most 512 references (its half sums are two classes per reference), got %d" % len(refs))
     nx = data.shape[-1]
     ou = int(args.ou) if args.ou > 0 else nx // 2 - 2            # last_ring default (:311)
     mask = stackio.read_stack(args.maskfile)[0] if args.maskfile else None      # get_image(maskfile) (:317-319)

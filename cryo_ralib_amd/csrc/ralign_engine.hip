@@ -3487,6 +3487,26 @@ extern "C" int ra_wiener_accumulate(const float *d_images, int n, int nx, const 
     return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_accumulate", he);
 }
 
+// a finalize kernel's launch: one workgroup per class, or, when the plan keeps its block in global scratch, a grid of scratch
+// blocks that loops over the classes; args(pl_arg, d_gscr) gives the kernel's argument pointers
+template <class Args>
+static hipError_t wn_finalize_launch(const PfPlan &pl, const void *fk, int k, hipStream_t stream, Args args)
+{
+    hipError_t he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (he != hipSuccess) return he;
+    const int grid = pl.gblk ? pf_gblk_grid(pl, k) : k;
+    float2 *d_gscr = nullptr;
+    if (pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)grid * pl.nx * pl.H * sizeof(float2), stream);
+    if (he == hipSuccess) {
+        PfPlan pl_arg = pl;
+        std::vector<void *> a = args(pl_arg, d_gscr);
+        he = hipLaunchKernel(fk, dim3(grid), dim3(PF_THREADS), a.data(), pl.lds, stream);
+        if (he == hipSuccess) he = hipGetLastError();
+    }
+    if (d_gscr) (void)hipFreeAsync(d_gscr, stream);
+    return he;
+}
+
 extern "C" int ra_wiener_finalize(const float *d_num, const float *d_den, const int *d_counts, int k, int nx, int pad, float snr,
                                   int min_count, float *d_out, void *hip_stream)
 {
@@ -3499,19 +3519,65 @@ extern "C" int ra_wiener_finalize(const float *d_num, const float *d_den, const 
     const PfPlan pl = pf_make_plan(nx, pad);
     if (pl.nb < 1) { g_last_error = "ra_wiener_finalize: no plan for this box"; return RA_ERR_ARG; }
     const void *fk = pl.gblk ? (const void *)wn_finalize_kernel<true> : (const void *)wn_finalize_kernel<false>;
-    hipError_t he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-    if (he != hipSuccess) return sdr_launch_error("ra_wiener_finalize", he);
-    const int grid = pl.gblk ? pf_gblk_grid(pl, k) : k;
-    float2 *d_gscr = nullptr;
-    if (pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)grid * nx * pl.H * sizeof(float2), stream);
-    if (he == hipSuccess) {
-        const float2 *num = (const float2 *)d_num;
-        float inv_snr = 1.0f / snr;
-        PfPlan pl_arg = pl;
-        void *args[] = {&num, &d_den, &d_counts, &k, &inv_snr, &min_count, &d_out, &pl_arg, &d_gscr};
-        he = hipLaunchKernel(fk, dim3(grid), dim3(PF_THREADS), args, pl.lds, stream);
-        if (he == hipSuccess) he = hipGetLastError();
-    }
-    if (d_gscr) (void)hipFreeAsync(d_gscr, stream);
+    const float2 *num = (const float2 *)d_num;
+    float inv_snr = 1.0f / snr;
+    const hipError_t he = wn_finalize_launch(pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
+        return {&num, &d_den, &d_counts, &k, &inv_snr, &min_count, &d_out, &pl_arg, &d_gscr};
+    });
     return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_finalize", he);
+}
+
+// ---- half-set FRC and SSNR-weighted averages (ralign_wiener.h)
+
+extern "C" int ra_wiener_frc(const float *d_num2, const float *d_den2, const int *d_counts2, int k, int nx, int pad, float snr,
+                             int min_count, float ssnr_floor, double *d_frc, float *d_reg, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (k < 1 || k > 512 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || !(snr > 0.f) || !std::isfinite(snr) ||
+        !(ssnr_floor > 0.f) || !std::isfinite(ssnr_floor)) {
+        g_last_error = "ra_wiener_frc: need 1 <= k <= 512, 2 <= nx <= 1024, pad 0 or 1, a finite snr > 0 and a finite ssnr_floor > 0";
+        return RA_ERR_ARG;
+    }
+    if (!d_num2 || !d_den2 || !d_counts2 || !d_frc || !d_reg) { g_last_error = "ra_wiener_frc: null argument"; return RA_ERR_ARG; }
+    const int P = pad ? 2 * nx : nx, S = P / 2 + 1;
+    // row blocks of `rows` rows, about WN_FRC_BLOCKS workgroups over all classes, none of them empty
+    const int want = std::max(1, std::min(std::min(P, WN_FRC_MAX_ROW_BLOCKS), WN_FRC_BLOCKS / k));
+    const int rows = (P + want - 1) / want, nb = (P + rows - 1) / rows;
+    const int threads = std::min(WN_THREADS, (S + 63) / 64 * 64);
+    double *d_part = nullptr;
+    hipError_t he = hipMallocAsync((void **)&d_part, (size_t)k * nb * 5 * S * sizeof(double), stream);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(wn_frc_rows_kernel, dim3(nb, k), dim3(threads), 0, stream, (const float2 *)d_num2, d_den2, P, rows,
+                           1.0 / (double)snr, d_part);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(wn_frc_combine_kernel, dim3((S + WN_THREADS - 1) / WN_THREADS, k), dim3(WN_THREADS), 0, stream,
+                           (const double *)d_part, nb, S, d_counts2, min_count, ssnr_floor, d_frc, d_reg);
+        he = hipGetLastError();
+    }
+    if (d_part) (void)hipFreeAsync(d_part, stream);
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_frc", he);
+}
+
+extern "C" int ra_wiener_finalize_ssnr(const float *d_num2, const float *d_den2, const int *d_counts2, const float *d_reg, int k, int nx,
+                                       int pad, int min_count, float *d_out, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (k < 1 || k > 512 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1)) {
+        g_last_error = "ra_wiener_finalize_ssnr: need 1 <= k <= 512, 2 <= nx <= 1024 and pad 0 or 1";
+        return RA_ERR_ARG;
+    }
+    if (!d_num2 || !d_den2 || !d_counts2 || !d_reg || !d_out) {
+        g_last_error = "ra_wiener_finalize_ssnr: null argument";
+        return RA_ERR_ARG;
+    }
+    const PfPlan pl = pf_make_plan(nx, pad);
+    if (pl.nb < 1) { g_last_error = "ra_wiener_finalize_ssnr: no plan for this box"; return RA_ERR_ARG; }
+    const void *fk = pl.gblk ? (const void *)wn_finalize_ssnr_kernel<true> : (const void *)wn_finalize_ssnr_kernel<false>;
+    const float2 *num2 = (const float2 *)d_num2;
+    const hipError_t he = wn_finalize_launch(pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
+        return {&num2, &d_den2, &d_counts2, &d_reg, &k, &min_count, &d_out, &pl_arg, &d_gscr};
+    });
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_finalize_ssnr", he);
 }

@@ -18,6 +18,18 @@
 //      association, bitwise reproducible.
 // Finalize: wn_finalize_kernel, one workgroup per class (looping when the block lives in global scratch): N / (D + 1/snr) into
 // inverse column FFTs over the full height (N is dense), the nx window rows kept, then the phase flip's inverse row pass.
+//
+// Half-set FRC and SSNR-weighted finalize (ra_wiener_frc / ra_wiener_finalize_ssnr; contract: wiener.py
+// ssnr_reference).  The half sums are ra_wiener_accumulate's with labels 2j + h and 2k classes, so class j's halves are slots 2j and
+// 2j + 1 of num2 / den2 / counts2.  Shell s = floor(r + 0.5) of element (iy, ix), r = |(ix, ky)|, ky the signed row frequency;
+// shells 0 .. P/2 take part in the sums, with the Hermitian weight g = 1 on column 0 (and P/2 for even P), 2 elsewhere.
+//   1. wn_frc_rows_kernel: one workgroup per (row block, class), one thread per shell; the thread walks the block's rows in order
+//      and, in each row, the columns of its shell (a contiguous run: s does not decrease along a row), summing in double
+//      g Re(V0 conj V1), g |V0|^2, g |V1|^2, g (D0 + D1) and g, V_h = N_h / (D_h + 1/snr), into the block's partial slot;
+//   2. wn_frc_combine_kernel: one thread per (class, shell) adds the row blocks' slots in block order, then the FRC and
+//      R = mean(D0 + D1) / max(2F / (1 - F), floor), F = min(FRC, 0.999);
+//   3. wn_finalize_ssnr_kernel: wn_finalize_kernel's transforms of (N0 + N1) / (D0 + D1 + R(min(s, P/2))).
+// One writer per output element and a fixed order of every sum: bitwise reproducible.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -31,6 +43,8 @@ namespace ralign {
 #define WN_SCRATCH_BYTES ((size_t)1 << 30)      // spectra + aligned images of one chunk
 #define WN_BLOCKS_TARGET 2048       // workgroups the reduce aims for: runs per chunk = this / element blocks, within 1 .. 64
 #define WN_MAX_RUNS 64
+#define WN_FRC_BLOCKS 1024          // workgroups the FRC row pass aims for over all classes: row blocks = this / k, within 1 .. 64
+#define WN_FRC_MAX_ROW_BLOCKS 64
 
 // CTF constants of one particle in the aligned frame, doubles; l3 = lam^3 folded in
 struct WnCtf {
@@ -82,11 +96,52 @@ __host__ __device__ inline void wn_forward(const Ctx &cx, const float *img, floa
     }
 }
 
-// one class: num [P][H], den [P][H] -> img [nx][nx]; inverse column FFTs of num / (den + 1/snr), the nx window rows into blk,
-// the inverse row pass
-template <class Ctx>
-__host__ __device__ inline void wn_class(const Ctx &cx, const float2 *num, const float *den, float inv_snr, float *img, const PfPlan &pl,
-                                         float2 *blk, float2 *work, const float2 *tw)
+// shell of the rfft-grid element at column ix and signed row frequency ky: s = floor(r + 0.5).  In integers, with r2 = r^2:
+// (s - 1/2)^2 <= r2 < (s + 1/2)^2 is s (s - 1) < r2 <= s (s + 1) for s >= 1 (r2 = 0 for s = 0), so a float estimate settled by
+// these exact tests gives the shell of the float64 contract without a double square root
+__host__ __device__ inline int wn_shell(int ix, int ky)
+{
+    const int r2 = ix * ix + ky * ky;
+    int s = (int)(sqrtf((float)r2) + 0.5f);
+    while (s * (s + 1) < r2) s++;
+    while (s > 0 && s * (s - 1) >= r2) s--;
+    return s;
+}
+
+// what ra_wiener_finalize transforms: num / (den + 1/snr) at element e = n * H + kx of one class
+struct WnConstSrc {
+    const float2 *num;
+    const float *den;
+    float inv_snr;
+    __host__ __device__ float2 operator()(size_t e, int, int) const
+    {
+        const float g = 1.0f / (den[e] + inv_snr);
+        return make_float2(num[e].x * g, num[e].y * g);
+    }
+};
+
+// what ra_wiener_finalize_ssnr transforms: (N0 + N1) / (D0 + D1 + R(min(s, P/2))) of one class's half sums, 0 where that
+// denominator is 0; reg [P/2 + 1] the class's per-shell term
+struct WnSsnrSrc {
+    const float2 *n0, *n1;
+    const float *d0, *d1, *reg;
+    int P;
+    __host__ __device__ float2 operator()(size_t e, int n, int kx) const
+    {
+        const int s = wn_shell(kx, n <= P / 2 ? n : n - P), h = P / 2;
+        const float d = (d0[e] + d1[e]) + reg[s < h ? s : h];
+        if (d == 0.f) return make_float2(0.f, 0.f);
+        const float g = 1.0f / d;
+        const float2 a = n0[e], b = n1[e];
+        return make_float2((a.x + b.x) * g, (a.y + b.y) * g);
+    }
+};
+
+// one class: src(e, n, kx) the divided spectrum at row n, column kx of [P][H] -> img [nx][nx]; inverse column FFTs, the nx window
+// rows into blk, the inverse row pass
+template <class Ctx, class Src>
+__host__ __device__ inline void wn_class_src(const Ctx &cx, const Src &src, float *img, const PfPlan &pl, float2 *blk, float2 *work,
+                                             const float2 *tw)
 {
     const int nx = pl.nx, P = pl.P, H = pl.H, o = pl.o, nb = pl.nb;
     float2 *wa = work, *wb = work + (size_t)nb * P;
@@ -94,9 +149,7 @@ __host__ __device__ inline void wn_class(const Ctx &cx, const float2 *num, const
         const int cnt = H - c0 < nb ? H - c0 : nb;
         for (int it = cx.tid; it < cnt * P; it += cx.nt) {
             const int t = it / P, n = it - t * P;
-            const size_t e = (size_t)n * H + c0 + t;
-            const float g = 1.0f / (den[e] + inv_snr);
-            wa[it] = make_float2(num[e].x * g, num[e].y * g);
+            wa[it] = src((size_t)n * H + c0 + t, n, c0 + t);
         }
         cx.sync();
         const float2 *z = pf_fft(cx, wa, wb, cnt, pl, tw, 1.f);
@@ -107,6 +160,14 @@ __host__ __device__ inline void wn_class(const Ctx &cx, const float2 *num, const
         cx.sync();
     }
     pf_rows_inverse(cx, img, pl, blk, work, tw);
+}
+
+// one class of the constant-snr finalize: num [P][H], den [P][H] -> img [nx][nx]
+template <class Ctx>
+__host__ __device__ inline void wn_class(const Ctx &cx, const float2 *num, const float *den, float inv_snr, float *img, const PfPlan &pl,
+                                         float2 *blk, float2 *work, const float2 *tw)
+{
+    wn_class_src(cx, WnConstSrc{num, den, inv_snr}, img, pl, blk, work, tw);
 }
 
 // per particle: class, finiteness, CTF constants in the aligned frame; *bad = the lowest offending index (n: none)
@@ -223,14 +284,13 @@ __global__ __launch_bounds__(WN_THREADS) void wn_combine_kernel(int P, int H, co
     den[o] += (float)d;
 }
 
-template <bool GBLK>
-__global__ __launch_bounds__(PF_THREADS) void wn_finalize_kernel(const float2 *__restrict__ num, const float *__restrict__ den,
-                                                                 const int *__restrict__ counts, int k, float inv_snr, int min_count,
-                                                                 float *__restrict__ out, PfPlan pl, float2 *__restrict__ gscr)
+// the finalize of classes blockIdx.x, blockIdx.x + gridDim.x, ...: zeros where live(j) is false, else src(j) (a WnConstSrc or
+// WnSsnrSrc) through wn_class_src
+template <bool GBLK, class Live, class Src>
+__device__ inline void wn_finalize_body(int k, const Live &live, const Src &src, float *out, const PfPlan &pl, float2 *gscr)
 {
     extern __shared__ float2 pf_lds[];
     const int P = pl.P, nx = pl.nx;
-    const size_t ph = (size_t)P * pl.H;
     float2 *tw = pf_lds;
     float2 *work = pf_lds + P;
     float2 *blk = GBLK ? gscr + (size_t)blockIdx.x * nx * pl.H : work + (size_t)2 * pl.nb * P;
@@ -243,12 +303,120 @@ __global__ __launch_bounds__(PF_THREADS) void wn_finalize_kernel(const float2 *_
     __syncthreads();
     for (int j = blockIdx.x; j < k; j += gridDim.x) {
         float *img = out + (size_t)j * nx * nx;
-        if (counts[j] < min_count) {
+        if (!live(j)) {
             for (int i = cx.tid; i < nx * nx; i += cx.nt) img[i] = 0.f;
             continue;
         }
-        wn_class(cx, num + (size_t)j * ph, den + (size_t)j * ph, inv_snr, img, pl, blk, work, tw);
+        wn_class_src(cx, src(j), img, pl, blk, work, tw);
     }
+}
+
+template <bool GBLK>
+__global__ __launch_bounds__(PF_THREADS) void wn_finalize_kernel(const float2 *__restrict__ num, const float *__restrict__ den,
+                                                                 const int *__restrict__ counts, int k, float inv_snr, int min_count,
+                                                                 float *__restrict__ out, PfPlan pl, float2 *__restrict__ gscr)
+{
+    const size_t ph = (size_t)pl.P * pl.H;
+    wn_finalize_body<GBLK>(
+        k, [=](int j) { return counts[j] >= min_count; },
+        [=](int j) { return WnConstSrc{num + (size_t)j * ph, den + (size_t)j * ph, inv_snr}; }, out, pl, gscr);
+}
+
+// num2 [k][2][P][H], den2 [k][2][P][H], counts2 [k][2], reg [k][P/2 + 1]
+template <bool GBLK>
+__global__ __launch_bounds__(PF_THREADS) void wn_finalize_ssnr_kernel(const float2 *__restrict__ num2, const float *__restrict__ den2,
+                                                                      const int *__restrict__ counts2, const float *__restrict__ reg, int k,
+                                                                      int min_count, float *__restrict__ out, PfPlan pl,
+                                                                      float2 *__restrict__ gscr)
+{
+    const int P = pl.P;
+    const size_t ph = (size_t)P * pl.H;
+    wn_finalize_body<GBLK>(
+        k, [=](int j) { return counts2[2 * j] + counts2[2 * j + 1] >= min_count; },
+        [=](int j) {
+            const size_t a = (size_t)2 * j * ph;
+            return WnSsnrSrc{num2 + a, num2 + a + ph, den2 + a, den2 + a + ph, reg + (size_t)j * (P / 2 + 1), P};
+        },
+        out, pl, gscr);
+}
+
+// the five sums of shell s over rows [y0, y1) of one class's halves n0 / n1, d0 / d1 ([P][P/2 + 1]), rows in order and in each row
+// the shell's columns in order: a = (g Re(V0 conj V1), g |V0|^2, g |V1|^2, g (D0 + D1), g), V_h = N_h / (D_h + 1/snr)
+__host__ __device__ inline void wn_frc_shell_rows(const float2 *n0, const float2 *n1, const float *d0, const float *d1, int P, int y0,
+                                                  int y1, int s, double inv_snr, double *a)
+{
+    const int H = P / 2 + 1;
+    double xr = 0.0, a0 = 0.0, a1 = 0.0, dd = 0.0, gg = 0.0;
+    for (int iy = y0; iy < y1; iy++) {
+        const int ky = iy <= P / 2 ? iy : iy - P;
+        if (ky > s || -ky > s) continue;            // r >= |ky| >= s + 1
+        // the shell's columns: lo < ix^2 + ky^2 <= hi (wn_shell's bounds; every column from 0 for s = 0); the first one from a
+        // float estimate settled by the exact tests
+        const int k2 = ky * ky, lo = s * (s - 1), hi = s * (s + 1);
+        int ix = 0;
+        if (s > 0) {
+            ix = lo - k2 > 0 ? (int)sqrtf((float)(lo - k2)) : 0;
+            if (ix > H) ix = H;
+            while (ix > 0 && (ix - 1) * (ix - 1) + k2 > lo) ix--;
+            while (ix < H && ix * ix + k2 <= lo) ix++;
+        }
+        for (; ix < H && ix * ix + k2 <= hi; ix++) {
+            const size_t e = (size_t)iy * H + ix;
+            const double g = (ix == 0 || 2 * ix == P) ? 1.0 : 2.0;
+            const double q0 = 1.0 / ((double)d0[e] + inv_snr), q1 = 1.0 / ((double)d1[e] + inv_snr);
+            const float2 u = n0[e], v = n1[e];
+            const double ux = u.x * q0, uy = u.y * q0, vx = v.x * q1, vy = v.y * q1;
+            xr += g * (ux * vx + uy * vy);
+            a0 += g * (ux * ux + uy * uy);
+            a1 += g * (vx * vx + vy * vy);
+            dd += g * ((double)d0[e] + (double)d1[e]);
+            gg += g;
+        }
+    }
+    a[0] = xr; a[1] = a0; a[2] = a1; a[3] = dd; a[4] = gg;
+}
+
+// one shell's FRC and regulariser from its five sums; live: the class has min_count members
+__host__ __device__ inline void wn_frc_shell(const double *a, bool live, float ssnr_floor, double *frc, float *reg)
+{
+    const double f = live && a[1] > 0.0 && a[2] > 0.0 ? a[0] / sqrt(a[1] * a[2]) : 0.0;
+    const double F = f < 0.999 ? f : 0.999;
+    double rho = F > 0.0 ? 2.0 * F / (1.0 - F) : 0.0;
+    if (rho < (double)ssnr_floor) rho = ssnr_floor;
+    *frc = f;
+    *reg = (float)(a[3] / a[4] / rho);
+}
+
+// grid (row blocks, k): part [k][blocks][5][S], S = P/2 + 1
+__global__ __launch_bounds__(WN_THREADS) void wn_frc_rows_kernel(const float2 *__restrict__ num2, const float *__restrict__ den2, int P,
+                                                                 int rows, double inv_snr, double *__restrict__ part)
+{
+    const int j = blockIdx.y, b = blockIdx.x, S = P / 2 + 1;
+    const size_t ph = (size_t)P * S;
+    const float2 *n0 = num2 + (size_t)2 * j * ph;
+    const float *d0 = den2 + (size_t)2 * j * ph;
+    const int y0 = b * rows, y1 = y0 + rows < P ? y0 + rows : P;
+    double *o = part + ((size_t)j * gridDim.x + b) * 5 * S;
+    for (int s = threadIdx.x; s < S; s += blockDim.x) {
+        double a[5];
+        wn_frc_shell_rows(n0, n0 + ph, d0, d0 + ph, P, y0, y1, s, inv_snr, a);
+        for (int q = 0; q < 5; q++) o[(size_t)q * S + s] = a[q];
+    }
+}
+
+// grid (shell blocks, k): the row blocks' sums in block order, then frc [k][S], reg [k][S]
+__global__ __launch_bounds__(WN_THREADS) void wn_frc_combine_kernel(const double *__restrict__ part, int nb, int S,
+                                                                    const int *__restrict__ counts2, int min_count, float ssnr_floor,
+                                                                    double *__restrict__ frc, float *__restrict__ reg)
+{
+    const int j = blockIdx.y, s = blockIdx.x * WN_THREADS + threadIdx.x;
+    if (s >= S) return;
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int b = 0; b < nb; b++) {
+        const double *p = part + ((size_t)j * nb + b) * 5 * S + s;
+        for (int q = 0; q < 5; q++) a[q] += p[(size_t)q * S];
+    }
+    wn_frc_shell(a, counts2[2 * j] + counts2[2 * j + 1] >= min_count, ssnr_floor, frc + (size_t)j * S + s, reg + (size_t)j * S + s);
 }
 
 }  // namespace ralign

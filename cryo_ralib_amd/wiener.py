@@ -1,7 +1,7 @@
 """CTF-corrected (Wiener-filtered) class averages of an aligned particle stack.
 
     python -m cryo_ralib_amd.wiener STACK PARAMS CTF OUT [--labels labels.npy] [--k K] [--snr S] [--nopad] [--flipped]
-                                    [--min_count M] [--apix A] [--ou R] [--device D]
+                                    [--min_count M] [--apix A] [--ou R] [--device D] [--ssnr [--ssnr_floor F] [--frc FRC.npz]]
 
 The contract, stated in float64 by `wiener_reference`: inputs are a stack x [n][nx][nx], params [n][4]
 (alpha, sx, sy, mirror, as api.rot_shift2d takes them), labels [n] in 0 .. k-1, a CTF table [n][9] in the layout of ctf.py,
@@ -23,6 +23,20 @@ damping of rot_shift2D's interpolation.  Signs: particles formed as -c * F (EMAN
 
 The device path is ra_wiener_accumulate / ra_wiener_finalize (csrc/ralign_wiener.h); `accumulate` and `finalize` expose them
 for callers that stream a stack in chunks or sum over ranks in between, `wiener_averages` runs both.
+
+SSNR-weighted averages (--ssnr; DESIGN.md section 4.11, stated in float64 by `ssnr_reference`) replace the constant 1/snr with a
+per-shell term that the data set.  Particle i of a call goes to half h_i = (index0 + i) % 2 of its class, index0 the global index
+of its first image (the engine's even / odd split, so chunks and ranks agree when each passes its own offset); N_jh, D_jh and n_jh
+are the sums above over class j's half h.  Shells s = floor(r + 0.5) of the rfft grid (r = |(kx, ky)|, ky the signed row
+frequency) run 0 .. P/2; every shell sum carries the Hermitian weight g (1 on column 0 and, for even P, on column P/2; 2
+elsewhere), so it equals the sum over the full plane.  V_jh = N_jh / (D_jh + 1/snr) and FRC_j(s) = sum g Re(V_j0 conj V_j1) /
+sqrt(sum g |V_j0|^2 sum g |V_j1|^2), 0 where either sum is 0 and for classes with n_j0 + n_j1 < min_count.  With F = min(FRC, 0.999),
+rho = max(2F / (1 - F), ssnr_floor) (0 before the floor where F <= 0) and R_j(s) = (sum g (D_j0 + D_j1) / sum g) / rho,
+A_j = crop_o(irfft2((N_j0 + N_j1) / (D_j0 + D_j1 + R_j(min(s, P/2))))), 0 where that denominator is 0 (corner elements beyond
+shell P/2 take its term).  --snr then only sets the half averages V.  The FRC also gives each class's resolution (`resolution`):
+s1 = the first shell s >= 1 with FRC < t (P/2 + 1 if none), P apix / (s1 - 1) A, or pixels without a pixel size.  The device path
+is ra_wiener_accumulate with labels 2j + h (`accumulate_halves`), ra_wiener_frc (`frc`) and ra_wiener_finalize_ssnr
+(`finalize_ssnr`); `ssnr_averages` runs all three.
 
 PARAMS is a driver's params.txt (idx angle sx sy mirror class; the class column gives the labels) or an initial2Dparams.txt
 (alpha sx sy mirror; one class); --labels (an int .npy) overrides the classes, e.g. with k-means labels.  CTF is a [n][9] .npy
@@ -99,15 +113,19 @@ def check_inputs(n, nx, params, labels, k, table, snr=1.0):
     return prm, lab, tab
 
 
-def wiener_reference(x, params, labels, k, table, snr=1.0, pad=True, flipped=False, min_count=1, aligned=None):
-    """float64 statement of the contract: [k][nx][nx] averages and the class sizes.  aligned: the rot_shift2D images [n][nx][nx]
-    to use in step 1 (e.g. the device's own, to isolate the rest); default synth.rot_shift2d_np of x"""
-    from . import synth
+def _images(x):
     x = np.asarray(x)
     if x.ndim != 3 or x.shape[1] != x.shape[2]:
         raise WienerError("images are [n][nx][nx], got %s" % (x.shape,))
-    n, nx = x.shape[0], x.shape[-1]
-    prm, lab, tab = check_inputs(n, nx, params, labels, k, table, snr)
+    return x, x.shape[0], x.shape[-1]
+
+
+def class_sums_reference(x, params, labels, k, table, pad=True, flipped=False, aligned=None):
+    """float64 N_j [k][P][P/2 + 1] (complex), D_j [k][P][P/2 + 1] and the class sizes of the contract.  aligned: the rot_shift2D
+    images [n][nx][nx] to use in step 1 (e.g. the device's own, to isolate the rest); default synth.rot_shift2d_np of x"""
+    from . import synth
+    x, n, nx = _images(x)
+    prm, lab, tab = check_inputs(n, nx, params, labels, k, table)
     P = 2 * nx if pad else nx
     o = (P - nx) // 2
     tab = aligned_table(tab, prm)
@@ -125,11 +143,149 @@ def wiener_reference(x, params, labels, k, table, snr=1.0, pad=True, flipped=Fal
         w = np.abs(c) if flipped else c
         num[lab[i]] += w * np.fft.rfft2(big)
         den[lab[i]] += c * c
+    return num, den, counts
+
+
+def wiener_reference(x, params, labels, k, table, snr=1.0, pad=True, flipped=False, min_count=1, aligned=None):
+    """float64 statement of the contract: [k][nx][nx] averages and the class sizes.  aligned: the rot_shift2D images [n][nx][nx]
+    to use in step 1 (e.g. the device's own, to isolate the rest); default synth.rot_shift2d_np of x"""
+    x, n, nx = _images(x)
+    check_inputs(n, nx, params, labels, k, table, snr)
+    num, den, counts = class_sums_reference(x, params, labels, k, table, pad, flipped, aligned)
+    P = 2 * nx if pad else nx
+    o = (P - nx) // 2
     out = np.zeros((k, nx, nx))
     for j in range(k):
         if counts[j] >= min_count and counts[j] > 0:
             out[j] = np.fft.irfft2(num[j] / (den[j] + 1.0 / snr), s=(P, P))[o:o + nx, o:o + nx]
     return out, counts
+
+
+# ---- the SSNR contract in float64 numpy
+
+MAX_K_SSNR = MAX_K // 2
+SSNR_FLOOR = 1e-3
+
+
+def check_ssnr(k, ssnr_floor):
+    """the SSNR path's own domain: 1 <= k <= 512 (its half sums are 2k classes), a finite ssnr_floor > 0"""
+    if not (isinstance(k, (int, np.integer)) and 1 <= k <= MAX_K_SSNR):
+        raise WienerError("the SSNR averages need 1 <= k <= %d, got %r" % (MAX_K_SSNR, k))
+    if not (np.isfinite(ssnr_floor) and ssnr_floor > 0):
+        raise WienerError("need a finite ssnr_floor > 0, got %r" % ssnr_floor)
+
+
+def shells(P):
+    """(s, g) on the rfft2 grid [P][P/2 + 1] of a P x P image: the shell floor(r + 0.5) of every element (r = |(kx, ky)|, ky the
+    signed row frequency) and its Hermitian weight (1 on column 0 and, for even P, on column P/2; 2 elsewhere)"""
+    H = P // 2 + 1
+    iy = np.arange(P)
+    ky = np.where(iy <= P // 2, iy, iy - P).astype(np.float64)[:, None]
+    kx = np.arange(H, dtype=np.float64)[None, :]
+    s = np.floor(np.sqrt(kx ** 2 + ky ** 2) + 0.5).astype(np.int64)
+    g = np.full((P, H), 2.0)
+    g[:, 0] = 1.0
+    if P % 2 == 0:
+        g[:, P // 2] = 1.0
+    return s, g
+
+
+def half_labels(labels, index0=0):
+    """2 j + h per particle, h = (index0 + i) % 2: the labels of the half sums (2k classes)"""
+    lab = np.asarray(labels).astype(np.int64)
+    return 2 * lab + (int(index0) + np.arange(lab.shape[0])) % 2
+
+
+def frc_from_sums(num2, den2, counts2, nx, pad=True, snr=1.0, min_count=1, ssnr_floor=SSNR_FLOOR):
+    """steps 2 - 4 of the SSNR contract in float64 on given half sums: num2 [k][2][P][P/2 + 1] complex (or float pairs
+    [..][2]), den2 [k][2][P][P/2 + 1], counts2 [k][2]; returns (frc [k][P/2 + 1], reg [k][P/2 + 1])"""
+    num2 = np.asarray(num2)
+    if not np.iscomplexobj(num2):
+        num2 = num2[..., 0].astype(np.float64) + 1j * num2[..., 1].astype(np.float64)
+    num2 = num2.astype(np.complex128)
+    den2 = np.asarray(den2, np.float64)
+    counts2 = np.asarray(counts2)
+    P = 2 * nx if pad else nx
+    S = P // 2 + 1
+    k = num2.shape[0]
+    if num2.shape != (k, 2, P, S) or den2.shape != num2.shape or counts2.shape != (k, 2):
+        raise WienerError("half sums are [k][2][%d][%d] and counts [k][2], got %s, %s, %s" % (P, S, num2.shape, den2.shape, counts2.shape))
+    s, g = shells(P)
+    inside = s <= P // 2
+    idx, gw = s[inside], g[inside]
+    v = num2 / (den2 + 1.0 / snr)
+    gsum = np.bincount(idx, gw, S)
+    frc, reg = np.zeros((k, S)), np.zeros((k, S))
+    for j in range(k):
+        v0, v1 = v[j, 0][inside], v[j, 1][inside]
+        xr = np.bincount(idx, gw * (v0 * np.conj(v1)).real, S)
+        a0 = np.bincount(idx, gw * np.abs(v0) ** 2, S)
+        a1 = np.bincount(idx, gw * np.abs(v1) ** 2, S)
+        dbar = np.bincount(idx, gw * (den2[j, 0] + den2[j, 1])[inside], S) / gsum
+        ok = (a0 > 0) & (a1 > 0) & (counts2[j].sum() >= min_count)
+        f = np.where(ok, xr / np.sqrt(np.where(ok, a0 * a1, 1.0)), 0.0)
+        F = np.minimum(f, 0.999)
+        rho = np.maximum(np.where(F > 0, 2 * F / (1 - F), 0.0), ssnr_floor)
+        frc[j], reg[j] = f, dbar / rho
+    return frc, reg
+
+
+def ssnr_reference(x, params, labels, k, table, snr=1.0, ssnr_floor=SSNR_FLOOR, pad=True, flipped=False, min_count=1, index0=0,
+                   aligned=None):
+    """float64 statement of the SSNR contract: (averages [k][nx][nx], class sizes [k], frc [k][P/2 + 1], reg [k][P/2 + 1]).
+    aligned: as for class_sums_reference"""
+    x, n, nx = _images(x)
+    check_inputs(n, nx, params, labels, k, table, snr)
+    check_ssnr(k, ssnr_floor)
+    P = 2 * nx if pad else nx
+    o, S = (P - nx) // 2, P // 2 + 1
+    num, den, cnt = class_sums_reference(x, params, half_labels(labels, index0), 2 * k, table, pad, flipped, aligned)
+    num2, den2, counts2 = num.reshape(k, 2, P, S), den.reshape(k, 2, P, S), cnt.reshape(k, 2)
+    frc, reg = frc_from_sums(num2, den2, counts2, nx, pad, snr, min_count, ssnr_floor)
+    s, _ = shells(P)
+    s = np.minimum(s, P // 2)
+    counts = counts2.sum(1)
+    out = np.zeros((k, nx, nx))
+    for j in range(k):
+        if counts[j] >= min_count and counts[j] > 0:
+            d = den2[j, 0] + den2[j, 1] + reg[j][s]
+            q = np.where(d != 0, (num2[j, 0] + num2[j, 1]) / np.where(d != 0, d, 1.0), 0.0)
+            out[j] = np.fft.irfft2(q, s=(P, P))[o:o + nx, o:o + nx]
+    return out, counts, frc, reg
+
+
+def resolution(frc, nx, pad=True, apix=None, threshold=0.143, counts=None, min_count=1):
+    """resolution of FRC curves [k][P/2 + 1] (or one curve) at `threshold`: s1 = the smallest shell s >= 1 with FRC < threshold, or
+    P/2 + 1 if there is none, s* = s1 - 1; P apix / s* A, or P / s* pixels when apix is None; inf where s* = 0, nan for classes
+    with counts < min_count (when counts are given)"""
+    f = np.asarray(frc, np.float64)
+    one = f.ndim == 1
+    f = np.atleast_2d(f)
+    P = 2 * nx if pad else nx
+    if f.shape[1] != P // 2 + 1:
+        raise WienerError("FRC curves have %d shells for P = %d, got %d" % (P // 2 + 1, P, f.shape[1]))
+    below = f[:, 1:] < threshold
+    star = np.where(below.any(1), below.argmax(1), P // 2)
+    res = np.where(star > 0, P * (1.0 if apix is None else float(apix)) / np.maximum(star, 1), np.inf)
+    if counts is not None:
+        res = np.where(np.asarray(counts) < min_count, np.nan, res)
+    return res[0] if one else res
+
+
+def table_apix(table, nx):
+    """the images' pixel size Apix D / nx when every row of the table agrees to a relative 1e-4, else None"""
+    t = np.asarray(table, np.float64)
+    if t.ndim != 2 or t.shape[0] == 0:
+        return None
+    a = t[:, 1] * t[:, 0] / nx
+    return float(a[0]) if np.all(np.abs(a - a[0]) <= 1e-4 * abs(a[0])) else None
+
+
+def resolutions(frc, counts, nx, pad=True, apix=None, min_count=1):
+    """{"res_05", "res_0143": [k] at FRC 0.5 and 0.143, "units": "A" with a pixel size, else "px"}"""
+    return {"res_05": resolution(frc, nx, pad, apix, 0.5, counts, min_count),
+            "res_0143": resolution(frc, nx, pad, apix, 0.143, counts, min_count),
+            "units": "px" if apix is None else "A"}
 
 
 # ---- the device path
@@ -195,11 +351,80 @@ def finalize(num, den, counts, nx, pad=True, snr=1.0, min_count=1, out=None):
     return out
 
 
-def wiener_averages(images, params, labels, k, ctf, snr=1.0, pad=True, flipped=False, min_count=1, ou=None, preprocess=False,
-                    device=0):
-    """[k][nx][nx] float32 CTF-corrected averages (numpy) and the class sizes [k] of the stack on the device (the contract of
-    wiener_reference).  preprocess=True subtracts the mean under model_circle(ou) first (Engine.normalize_particles, as
-    kmeans.class_averages does; ou defaults to nx // 2 - 2)."""
+def new_half_sums(k, nx, pad=True, device=0):
+    """zeroed half sums (num2 [k][2][P][P/2 + 1][2] float32, den2 [k][2][P][P/2 + 1] float32, counts2 [k][2] int32) CUDA
+    tensors: new_sums(2 k) with class j's half h in slot 2 j + h"""
+    num, den, counts = new_sums(2 * k, nx, pad, device)
+    P = 2 * nx if pad else nx
+    return num.view(k, 2, P, P // 2 + 1, 2), den.view(k, 2, P, P // 2 + 1), counts.view(k, 2)
+
+
+def _flat_halves(num2, den2, counts2):
+    k = int(counts2.shape[0])
+    for t in (num2, den2, counts2):
+        assert t.is_contiguous(), "half sums: new_half_sums(k, nx, pad)"
+    return k, num2.view(2 * k, *num2.shape[2:]), den2.view(2 * k, *den2.shape[2:]), counts2.view(2 * k)
+
+
+def accumulate_halves(images, params, labels, k, table, num2, den2, counts2, index0=0, pad=True, flipped=False):
+    """accumulate into the half sums (new_half_sums) on the current stream: particle i of images goes to half (index0 + i) % 2 of
+    its class, index0 the global index of images[0] (the engine's even / odd split), through ra_wiener_accumulate with labels
+    2j + h.  Labels outside 0 .. k - 1 are refused here (WienerError), the rest as by `accumulate`"""
+    n = int(images.shape[0])
+    lab = np.asarray(labels)
+    if lab.shape != (n,) or (n and not np.issubdtype(lab.dtype, np.integer)):
+        raise WienerError("labels are [%d] integers, got %s %s" % (n, lab.dtype, lab.shape))
+    if n and (lab.min() < 0 or lab.max() >= k):
+        raise WienerError("labels must lie in 0 .. %d, got %d .. %d" % (k - 1, lab.min(), lab.max()))
+    check_ssnr(k, SSNR_FLOOR)
+    k2, num, den, counts = _flat_halves(num2, den2, counts2)
+    assert k2 == k, "half sums of %d classes for k = %d" % (k2, k)
+    accumulate(images, params, half_labels(lab, index0), 2 * k, table, num, den, counts, pad, flipped)
+
+
+def frc(num2, den2, counts2, nx, pad=True, snr=1.0, min_count=1, ssnr_floor=SSNR_FLOOR):
+    """ra_wiener_frc on the current stream: (frc [k][P/2 + 1] float64, reg [k][P/2 + 1] float32) CUDA tensors from the half sums"""
+    import ctypes
+    import torch
+    from . import api
+    k = int(counts2.shape[0])
+    _flat_halves(num2, den2, counts2)
+    S = (2 * nx if pad else nx) // 2 + 1
+    f = torch.empty((k, S), dtype=torch.float64, device=num2.device)
+    r = torch.empty((k, S), dtype=torch.float32, device=num2.device)
+    stream = torch.cuda.current_stream(num2.device)
+    with torch.cuda.device(num2.device):
+        api._check(api.load_library().ra_wiener_frc(
+            ctypes.c_void_p(num2.data_ptr()), ctypes.c_void_p(den2.data_ptr()), ctypes.c_void_p(counts2.data_ptr()), k, int(nx),
+            int(bool(pad)), float(snr), int(min_count), float(ssnr_floor), ctypes.c_void_p(f.data_ptr()), ctypes.c_void_p(r.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream)), "ra_wiener_frc")
+    return f, r
+
+
+def finalize_ssnr(num2, den2, counts2, reg, nx, pad=True, min_count=1, out=None):
+    """ra_wiener_finalize_ssnr on the current stream: [k][nx][nx] float32 CUDA tensor of the SSNR-weighted averages"""
+    import ctypes
+    import torch
+    from . import api
+    k = int(counts2.shape[0])
+    _flat_halves(num2, den2, counts2)
+    S = (2 * nx if pad else nx) // 2 + 1
+    assert reg.is_contiguous() and reg.dtype == torch.float32 and tuple(reg.shape) == (k, S), "reg: frc()'s [k][P/2 + 1]"
+    if out is None:
+        out = torch.empty((k, nx, nx), dtype=torch.float32, device=num2.device)
+    assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (k, nx, nx)
+    stream = torch.cuda.current_stream(num2.device)
+    with torch.cuda.device(num2.device):
+        api._check(api.load_library().ra_wiener_finalize_ssnr(
+            ctypes.c_void_p(num2.data_ptr()), ctypes.c_void_p(den2.data_ptr()), ctypes.c_void_p(counts2.data_ptr()),
+            ctypes.c_void_p(reg.data_ptr()), k, int(nx), int(bool(pad)), int(min_count), ctypes.c_void_p(out.data_ptr()),
+            ctypes.c_void_p(stream.cuda_stream)), "ra_wiener_finalize_ssnr")
+    return out
+
+
+def _device_stack(images, params, labels, k, ctf, snr, ou, preprocess, device):
+    """(device, contiguous float32 images on it, params, labels, table) checked against the contract; preprocess=True subtracts
+    the mean under model_circle(ou) first"""
     import torch
     from . import api
     dev = torch.device("cuda", device) if not isinstance(device, torch.device) else device
@@ -220,10 +445,43 @@ def wiener_averages(images, params, labels, k, ctf, snr=1.0, pad=True, flipped=F
                 eng.normalize_particles(x)
             finally:
                 eng.close()
+    return dev, x, prm, lab, tab
+
+
+def wiener_averages(images, params, labels, k, ctf, snr=1.0, pad=True, flipped=False, min_count=1, ou=None, preprocess=False,
+                    device=0):
+    """[k][nx][nx] float32 CTF-corrected averages (numpy) and the class sizes [k] of the stack on the device (the contract of
+    wiener_reference).  preprocess=True subtracts the mean under model_circle(ou) first (Engine.normalize_particles, as
+    kmeans.class_averages does; ou defaults to nx // 2 - 2)."""
+    import torch
+    dev, x, prm, lab, tab = _device_stack(images, params, labels, k, ctf, snr, ou, preprocess, device)
+    nx = int(x.shape[-1])
+    with torch.cuda.device(dev):
         num, den, counts = new_sums(k, nx, pad, dev)
         accumulate(x, prm, lab, k, tab, num, den, counts, pad, flipped)
         out = finalize(num, den, counts, nx, pad, snr, min_count)
         return out.cpu().numpy(), counts.cpu().numpy()
+
+
+def ssnr_averages(images, params, labels, k, ctf, snr=1.0, ssnr_floor=SSNR_FLOOR, pad=True, flipped=False, min_count=1, index0=0,
+                  ou=None, preprocess=False, device=0, apix=None):
+    """SSNR-weighted averages of the stack on the device (the contract of ssnr_reference): ([k][nx][nx] float32 averages, class
+    sizes [k], frc [k][P/2 + 1] float64, resolutions), all numpy; resolutions = {"res_05", "res_0143", "units"} at FRC 0.5 and
+    0.143 in A with apix, or with table_apix(ctf) when the table gives one pixel size, else in pixels.  index0: the global index of
+    images[0] (the half split); the other arguments as for wiener_averages"""
+    import torch
+    check_ssnr(k, ssnr_floor)
+    dev, x, prm, lab, tab = _device_stack(images, params, labels, k, ctf, snr, ou, preprocess, device)
+    nx = int(x.shape[-1])
+    with torch.cuda.device(dev):
+        num2, den2, counts2 = new_half_sums(k, nx, pad, dev)
+        accumulate_halves(x, prm, lab, k, tab, num2, den2, counts2, index0, pad, flipped)
+        f, reg = frc(num2, den2, counts2, nx, pad, snr, min_count, ssnr_floor)
+        out = finalize_ssnr(num2, den2, counts2, reg, nx, pad, min_count)
+        counts = counts2.sum(1).cpu().numpy()
+        f = f.cpu().numpy()
+        res = resolutions(f, counts, nx, pad, apix if apix is not None else table_apix(tab, nx), min_count)
+        return out.cpu().numpy(), counts, f, res
 
 
 # ---- command line
@@ -255,6 +513,12 @@ def main(argv=None):
     ap.add_argument("--apix", type=float, default=None, help="pixel size (A) for a .star file that gives none")
     ap.add_argument("--ou", type=int, default=None, help="subtract the mean under model_circle(ou) from every particle first")
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--ssnr", action="store_true",
+                    help="SSNR-weighted averages: the per-shell term from the half-set FRC replaces 1/snr (--snr then only sets the "
+                         "half averages); prints each class's resolution at FRC 0.5 and 0.143")
+    ap.add_argument("--ssnr_floor", type=float, default=SSNR_FLOOR, help="lower bound of the per-shell SSNR (with --ssnr)")
+    ap.add_argument("--frc", default=None, metavar="FRC.npz",
+                    help="with --ssnr: write frc [k][P/2 + 1], freq (cycles/pixel), counts, res_05, res_0143 and units here")
     args = ap.parse_args(argv)
     from . import stackio
     try:
@@ -271,16 +535,36 @@ def main(argv=None):
         k = args.k if args.k is not None else (int(lab.max()) + 1 if n else 1)
         tab = _ctf.load_table(args.ctf, n, nx, args.apix)
         check_inputs(n, nx, prm, lab, k, tab, args.snr)
+        if args.ssnr:
+            check_ssnr(k, args.ssnr_floor)
+        elif args.frc:
+            raise WienerError("--frc needs --ssnr")
     except (WienerError, _ctf.CtfTableError, OSError, ValueError) as e:
         raise SystemExit("error: %s" % e)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU visible: the averages run on the device (wiener_reference is the float64 checker)")
-    avg, counts = wiener_averages(stack, prm, lab, k, tab, args.snr, not args.nopad, args.flipped, args.min_count, ou=args.ou,
-                                  preprocess=args.ou is not None, device=args.device)
+    if not args.ssnr:
+        avg, counts = wiener_averages(stack, prm, lab, k, tab, args.snr, not args.nopad, args.flipped, args.min_count, ou=args.ou,
+                                      preprocess=args.ou is not None, device=args.device)
+        stackio.write_stack(args.output, avg)
+        print("%s: %d CTF-corrected averages of %d particles (%d x %d, snr %g%s), class sizes %s"
+              % (args.output, k, n, nx, nx, args.snr, ", flipped" if args.flipped else "", " ".join(str(int(c)) for c in counts)))
+        return 0
+    avg, counts, f, res = ssnr_averages(stack, prm, lab, k, tab, args.snr, args.ssnr_floor, not args.nopad, args.flipped,
+                                        args.min_count, ou=args.ou, preprocess=args.ou is not None, device=args.device,
+                                        apix=args.apix)
     stackio.write_stack(args.output, avg)
-    print("%s: %d CTF-corrected averages of %d particles (%d x %d, snr %g%s), class sizes %s"
-          % (args.output, k, n, nx, nx, args.snr, ", flipped" if args.flipped else "", " ".join(str(int(c)) for c in counts)))
+    P = 2 * nx if not args.nopad else nx
+    if args.frc:
+        np.savez(args.frc, frc=f, freq=np.arange(P // 2 + 1) / P, counts=counts, res_05=res["res_05"], res_0143=res["res_0143"],
+                 units=res["units"])
+    print("%s: %d SSNR-weighted averages of %d particles (%d x %d, half averages at snr %g, floor %g%s); resolution in %s%s"
+          % (args.output, k, n, nx, nx, args.snr, args.ssnr_floor, ", flipped" if args.flipped else "", res["units"],
+             "" if res["units"] == "A" else " (no single pixel size: give --apix)"))
+    for j in range(k):
+        print("  class %3d: %7d particles   FRC 0.5: %8.2f %s   FRC 0.143: %8.2f %s"
+              % (j, counts[j], res["res_05"][j], res["units"], res["res_0143"][j], res["units"]))
     return 0
 
 

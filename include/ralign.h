@@ -339,6 +339,23 @@ int  ra_wiener_accumulate(const float *d_images, int n, int nx, const ra_result 
 int  ra_wiener_finalize(const float *d_num, const float *d_den, const int *d_counts, int k, int nx, int pad, float snr, int min_count,
                         float *d_out, void *hip_stream);
 
+/* Half-set FRC and SSNR-weighted class averages (contract: cryo_ralib_amd/wiener.py ssnr_reference).  The
+ * half sums are ra_wiener_accumulate's with labels 2j + h and 2k classes, h = (index0 + i) % 2 the particle's global even / odd
+ * index: d_num2 [k][2][P][P/2 + 1] (complex), d_den2 [k][2][P][P/2 + 1], d_counts2 [k][2].  Shell s = floor(|(kx, ky)| + 0.5) of
+ * each rfft-grid element; shells 0 .. P/2 (S = P/2 + 1) are summed with Hermitian weights (1 on column 0 and, for even P, on column
+ * P/2; 2 elsewhere), in double and in a fixed order, over several workgroups per class.
+ *   ra_wiener_frc            d_frc [k][S] (double): the FRC of the half averages V_h = N_h / (D_h + 1/snr); 0 where either half
+ *                            has no power in the shell, and on every shell of a class with fewer than min_count members.
+ *                            d_reg [k][S] (float): R = (shell mean of D0 + D1) / max(2F / (1 - F), ssnr_floor), F = min(FRC, 0.999).
+ *   ra_wiener_finalize_ssnr  d_out [k][nx][nx] = crop_o(irfft2((N0 + N1) / (D0 + D1 + R(min(s, P/2))))), 0 where that denominator
+ *                            is 0; classes with fewer than min_count members are zero.
+ * RA_ERR_ARG, nothing launched, for k outside 1 .. 512, nx outside 2 .. 1024, pad not 0 / 1, snr or ssnr_floor not finite and > 0,
+ * or a null pointer.  Asynchronous on hip_stream; no floating-point atomics: the same calls give bitwise-equal results. */
+int  ra_wiener_frc(const float *d_num2, const float *d_den2, const int *d_counts2, int k, int nx, int pad, float snr, int min_count,
+                   float ssnr_floor, double *d_frc, float *d_reg, void *hip_stream);
+int  ra_wiener_finalize_ssnr(const float *d_num2, const float *d_den2, const int *d_counts2, const float *d_reg, int k, int nx, int pad,
+                             int min_count, float *d_out, void *hip_stream);
+
 /* Two-stage dimension reduction (utils_ralib.py MPCA / TwoSDR) of a stack in device memory, without an engine (DESIGN.md
  * section 4.6).  All pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL = default stream)
  * and allocates and frees its scratch on that stream, as ra_phase_flip does.  Images are [n][p][q] float32, centred on load
