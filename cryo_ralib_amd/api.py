@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = [
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
-    "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr",
+    "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
 ]
 
 _lib = None
@@ -178,6 +178,7 @@ def load_library(path=None):
     L.ra_wiener_finalize.argtypes = [vp, vp, vp, ci, ci, ci, ctypes.c_float, ci, vp, vp]
     L.ra_wiener_frc.argtypes = [vp, vp, vp, ci, ci, ci, ctypes.c_float, ci, ctypes.c_float, vp, vp, vp]
     L.ra_wiener_finalize_ssnr.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]
+    L.ra_wiener_score.argtypes = [vp, ci, ci, vp, float_ptr, ci, ci, ci, vp, vp, vp, ctypes.c_float, vp, ci, ci, ci, vp, vp]
     L.ra_sdr_mean.argtypes = [vp, ci, ci, ci, vp, vp]
     L.ra_sdr_gram.argtypes = [vp, ci, ci, ci, vp, ci, vp, ci, vp, vp]
     L.ra_sdr_project.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
@@ -300,6 +301,13 @@ def ssnr_averages(images, params, labels, k, ctf, **kw):
     (wiener.ssnr_averages)."""
     from . import wiener
     return wiener.ssnr_averages(images, params, labels, k, ctf, **kw)
+
+
+def particle_scores(images, params, labels, k, ctf, **kw):
+    """Per-particle agreement with the class's Wiener estimate, leave-one-out by default: ({"cc", "scale", "sums"}, class sizes)
+    (wiener.particle_scores; wiener.select turns cc into a mask of the particles to keep)."""
+    from . import wiener
+    return wiener.particle_scores(images, params, labels, k, ctf, **kw)
 
 
 def two_sdr(images, p0, q0, r, **kw):

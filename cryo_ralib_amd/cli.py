@@ -29,6 +29,9 @@ multi_ref_wiener.<ext> (one per class) or aqfinal_wiener.<ext> (one image).  Ran
 --wiener_ssnr (with --wiener_averages) also writes the SSNR-weighted averages, whose per-shell term comes from the FRC of the
 even / odd half sets (global particle index), and each class's resolution at FRC 0.5 and 0.143: multi_ref_wiener_ssnr.<ext> and
 multi_ref_wiener_frc.txt, or aqfinal_wiener_ssnr.<ext> and aqfinal_wiener_frc.txt; --snr then only sets the half averages.
+--wiener_scores (with --wiener_averages) writes every particle's agreement with its class's Wiener estimate (leave-one-out, all
+shells but DC; with --wiener_ssnr the per-shell term) to multi_ref_wiener_scores.txt / aqfinal_wiener_scores.txt: one line
+`index class cc scale` per particle in global order.  Each rank scores its own particles against the rank-summed sums.
 """
 import argparse
 import os
@@ -63,6 +66,9 @@ def _common(p):
                    help="with --wiener_averages: also write SSNR-weighted averages (per-shell term from the half-set FRC) and the "
                         "classes' resolutions: multi_ref_wiener_ssnr.<ext> + multi_ref_wiener_frc.txt / aqfinal_wiener_ssnr.<ext> + "
                         "aqfinal_wiener_frc.txt")
+    p.add_argument("--wiener_scores", action="store_true",
+                   help="with --wiener_averages: also write every particle's leave-one-out agreement with its class's Wiener "
+                        "estimate, `index class cc scale` per line: multi_ref_wiener_scores.txt / aqfinal_wiener_scores.txt")
     p.add_argument("--ext", default="hdf", help="format of the written stacks: hdf (EMAN2 MDF, as the reference) | mrcs | npy")
     p.add_argument("--header_writeback", action="store_true",
                    help="write xform.align2d / assign / ID into the headers of the HDF INPUT stack itself, as the reference does "
@@ -164,6 +170,8 @@ def _check_wiener(p, args):
         p.error("--wiener_averages needs --snr > 0, got %g" % args.snr)
     if args.wiener_ssnr and not args.wiener_averages:
         p.error("--wiener_ssnr needs --wiener_averages")
+    if args.wiener_scores and not args.wiener_averages:
+        p.error("--wiener_scores needs --wiener_averages")
 
 
 def _sum_over_ranks(tensors, world):
@@ -178,9 +186,25 @@ def _sum_over_ranks(tensors, world):
                 td.all_reduce(t, op=td.ReduceOp.SUM)
 
 
+def _write_scores(args, name, lo, labels, sc, rank, world):
+    """<name>_scores.txt: `index class cc scale` of every particle in global order, gathered on rank 0"""
+    rows = [(lo + i, int(labels[i]), float(sc["cc"][i]), float(sc["scale"][i])) for i in range(len(labels))]
+    if world > 1:
+        import torch.distributed as td
+        gathered = [None] * world
+        td.all_gather_object(gathered, rows)
+        rows = sorted(x for part in gathered for x in part)
+    if rank == 0:
+        with open(os.path.join(args.outdir, "%s_scores.txt" % name), "w") as fh:
+            fh.write("# index class cc scale\n")
+            for r in rows:
+                fh.write("%d %d %.9g %.9g\n" % r)
+
+
 def _write_wiener(args, al, total, lo, hi, labels, k, name, rank, world):
     """CTF-corrected averages of the aligner's flipped particles with its final params; sums all-reduced over the ranks.  With
-    --wiener_ssnr also the SSNR-weighted averages (<name>_ssnr.<ext>) and the classes' resolutions (<name>_frc.txt)"""
+    --wiener_ssnr also the SSNR-weighted averages (<name>_ssnr.<ext>) and the classes' resolutions (<name>_frc.txt); with
+    --wiener_scores the particles' scores against the summed sums (<name>_scores.txt)"""
     from . import stackio, wiener
     nx = al.nx
     pad = not args.phase_flip_nopad
@@ -194,12 +218,19 @@ def _write_wiener(args, al, total, lo, hi, labels, k, name, rank, world):
     if rank == 0:
         stackio.write_stack(os.path.join(args.outdir, "%s.%s" % (name, args.ext)), out.cpu().numpy())
     if not args.wiener_ssnr:
+        if args.wiener_scores:
+            _write_scores(args, name, lo, labels, wiener.score(al.particles, prm, labels, k, tab, num, den, counts, snr=args.snr, pad=pad,
+                                                               flipped=True), rank, world)
         return
     num2, den2, counts2 = wiener.new_half_sums(k, nx, pad, al.dev)
     wiener.accumulate_halves(al.particles, prm, labels, k, tab, num2, den2, counts2, index0=lo, pad=pad, flipped=True)
     _sum_over_ranks((num2, den2, counts2), world)
     f, reg = wiener.frc(num2, den2, counts2, nx, pad, args.snr, 1, wiener.SSNR_FLOOR)
     out = wiener.finalize_ssnr(num2, den2, counts2, reg, nx, pad, 1)
+    if args.wiener_scores:
+        sc = wiener.score(al.particles, prm, labels, k, tab, (num2[:, 0] + num2[:, 1]).contiguous(), (den2[:, 0] + den2[:, 1]).contiguous(),
+                          counts2.sum(1).to(counts.dtype).contiguous(), reg=reg, pad=pad, flipped=True)
+        _write_scores(args, name, lo, labels, sc, rank, world)
     if rank == 0:
         stackio.write_stack(os.path.join(args.outdir, "%s_ssnr.%s" % (name, args.ext)), out.cpu().numpy())
         apix = args.apix if args.apix is not None else wiener.table_apix(_ctf_shard(args, total, nx, 0, total), nx)

@@ -3346,6 +3346,60 @@ static const void *wn_forward_fn(int nx, int pad, const PfPlan &pl, bool *fixed)
     return fk;
 }
 
+// step 1 of ra_wiener_accumulate / ra_wiener_score: the table and the particles' classes, finiteness and CTF constants on the
+// device; the verdict and the classes come back (a stream synchronisation) before the caller launches anything else
+struct WnPrep {
+    float *d_ctf = nullptr;
+    WnCtf *d_cst = nullptr;
+    int *d_lab = nullptr;
+    std::vector<int> lab;           // [n] classes, then the lowest offending index (n: none)
+    void release(hipStream_t stream)
+    {
+        if (d_lab) (void)hipFreeAsync(d_lab, stream);
+        if (d_cst) (void)hipFreeAsync(d_cst, stream);
+        if (d_ctf) (void)hipFreeAsync(d_ctf, stream);
+        d_lab = nullptr; d_cst = nullptr; d_ctf = nullptr;
+    }
+};
+
+// RA_OK with w filled (the caller releases it), else the error with w released
+static int wn_prepare(const char *fn, const ra_result *d_params, const float *h_ctf, int n, int nx, int P, int k, hipStream_t stream,
+                      WnPrep &w)
+{
+    w.lab.assign((size_t)n + 1, 0);
+    hipError_t he = hipMallocAsync((void **)&w.d_ctf, (size_t)n * 9 * sizeof(float), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&w.d_cst, (size_t)n * sizeof(WnCtf), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&w.d_lab, ((size_t)n + 1) * sizeof(int), stream);
+    if (he == hipSuccess) he = hipMemcpyAsync(w.d_ctf, h_ctf, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, stream);
+    if (he == hipSuccess) he = hipMemsetD32Async((hipDeviceptr_t)(w.d_lab + n), n, 1, stream);
+    if (he == hipSuccess) {
+        hipLaunchKernelGGL(wn_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_params, (const float *)w.d_ctf, n, nx, P, k,
+                           w.d_cst, w.d_lab, w.d_lab + n);
+        he = hipGetLastError();
+    }
+    if (he == hipSuccess) he = hipMemcpyAsync(w.lab.data(), w.d_lab, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) { w.release(stream); return sdr_launch_error(fn, he); }
+    if (w.lab[n] < n) {
+        const int i = w.lab[n];
+        char buf[256];
+        if (w.lab[i] < 0 || w.lab[i] >= k)
+            snprintf(buf, sizeof(buf), "%s: particle %d has class label %d outside 0 .. %d", fn, i, w.lab[i], k - 1);
+        else
+            snprintf(buf, sizeof(buf), "%s: particle %d has non-finite params (alpha, sx, sy)", fn, i);
+        g_last_error = buf;
+        w.release(stream);
+        return RA_ERR_ARG;
+    }
+    return RA_OK;
+}
+
+// particles per chunk of ra_wiener_accumulate / ra_wiener_score: the spectra and aligned images of one chunk fit the scratch budget
+static int wn_chunk(int n, size_t ph, int npix)
+{
+    return (int)std::max<size_t>(1, std::min<size_t>((size_t)n, WN_SCRATCH_BYTES / (ph * sizeof(float2) + (size_t)npix * sizeof(float))));
+}
+
 extern "C" int ra_wiener_accumulate(const float *d_images, int n, int nx, const ra_result *d_params, const float *h_ctf, int pad,
                                     int flipped, int k, float *d_num, float *d_den, int *d_counts, void *hip_stream)
 {
@@ -3366,45 +3420,19 @@ extern "C" int ra_wiener_accumulate(const float *d_images, int n, int nx, const 
     const size_t ph = (size_t)P * H;
 
     // 1. classes, finiteness and CTF constants on the device; the verdict and the classes come back before anything is summed
-    float *d_ctf = nullptr;
-    WnCtf *d_cst = nullptr;
-    int *d_lab = nullptr;
-    std::vector<int> lab((size_t)n + 1);
-    hipError_t he = hipMallocAsync((void **)&d_ctf, (size_t)n * 9 * sizeof(float), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_cst, (size_t)n * sizeof(WnCtf), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_lab, ((size_t)n + 1) * sizeof(int), stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_ctf, h_ctf, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = hipMemsetD32Async((hipDeviceptr_t)(d_lab + n), n, 1, stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(wn_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_params, (const float *)d_ctf, n, nx, P, k, d_cst,
-                           d_lab, d_lab + n);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(lab.data(), d_lab, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    auto release = [&]() {
-        if (d_lab) (void)hipFreeAsync(d_lab, stream);
-        if (d_cst) (void)hipFreeAsync(d_cst, stream);
-        if (d_ctf) (void)hipFreeAsync(d_ctf, stream);
-    };
-    if (he != hipSuccess) { release(); return sdr_launch_error("ra_wiener_accumulate", he); }
-    if (lab[n] < n) {
-        const int i = lab[n];
-        char buf[256];
-        if (lab[i] < 0 || lab[i] >= k)
-            snprintf(buf, sizeof(buf), "ra_wiener_accumulate: particle %d has class label %d outside 0 .. %d", i, lab[i], k - 1);
-        else
-            snprintf(buf, sizeof(buf), "ra_wiener_accumulate: particle %d has non-finite params (alpha, sx, sy)", i);
-        g_last_error = buf;
-        release();
-        return RA_ERR_ARG;
-    }
+    WnPrep prep;
+    const int prc = wn_prepare("ra_wiener_accumulate", d_params, h_ctf, n, nx, P, k, stream, prep);
+    if (prc != RA_OK) return prc;
+    const std::vector<int> &lab = prep.lab;
+    WnCtf *d_cst = prep.d_cst;
+    auto release = [&]() { prep.release(stream); };
+    hipError_t he = hipSuccess;
 
     // 2. chunks within the scratch budget; per chunk the members of every class in particle order, cut into runs so that the
     //    reduce has enough workgroups (element blocks x runs ~ WN_BLOCKS_TARGET); a class of several runs gets partial slots
     const int eblk = (int)((ph + WN_THREADS - 1) / WN_THREADS);
     const int T = std::max(1, std::min(WN_MAX_RUNS, WN_BLOCKS_TARGET / eblk));
-    const int C = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, WN_SCRATCH_BYTES / (ph * sizeof(float2) + (size_t)npix * sizeof(float))));
+    const int C = wn_chunk(n, ph, npix);
     std::vector<int> perm(n);
     std::vector<WnRun> runs;
     std::vector<int4> segs;
@@ -3580,4 +3608,91 @@ extern "C" int ra_wiener_finalize_ssnr(const float *d_num2, const float *d_den2,
         return {&num2, &d_den2, &d_counts2, &d_reg, &k, &min_count, &d_out, &pl_arg, &d_gscr};
     });
     return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_finalize_ssnr", he);
+}
+
+// ---- per-particle agreement scores (ralign_wiener.h)
+
+extern "C" int ra_wiener_score(const float *d_images, int n, int nx, const ra_result *d_params, const float *h_ctf, int pad, int flipped,
+                               int k, const float *d_num, const float *d_den, const int *d_counts, float snr, const float *d_reg,
+                               int leave_one_out, int s_lo, int s_hi, double *d_sums, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 0 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || (flipped != 0 && flipped != 1) || k < 1 || k > 1024 ||
+        (leave_one_out != 0 && leave_one_out != 1)) {
+        g_last_error = "ra_wiener_score: need n >= 0, 2 <= nx <= 1024, pad, flipped and leave_one_out 0 or 1, 1 <= k <= 1024";
+        return RA_ERR_ARG;
+    }
+    if (s_lo < 0 || s_lo > s_hi || s_hi > (pad ? 2 * nx : nx) / 2) {
+        g_last_error = "ra_wiener_score: need 0 <= s_lo <= s_hi <= P/2";
+        return RA_ERR_ARG;
+    }
+    if (d_reg ? k > 512 : (!(snr > 0.f) || !std::isfinite(snr))) {
+        g_last_error = "ra_wiener_score: need a finite snr > 0, or a per-shell term with k <= 512";
+        return RA_ERR_ARG;
+    }
+    if (n == 0) return RA_OK;
+    if (!d_images || !d_params || !h_ctf || !d_num || !d_den || !d_counts || !d_sums) {
+        g_last_error = "ra_wiener_score: null argument";
+        return RA_ERR_ARG;
+    }
+    if (!pf_rows_ok("ra_wiener_score", h_ctf, n)) return RA_ERR_ARG;
+    const PfPlan pl = pf_make_plan(nx, pad);
+    if (pl.nb < 1) { g_last_error = "ra_wiener_score: no plan for this box"; return RA_ERR_ARG; }
+    const int P = pl.P, H = pl.H, npix = nx * nx;
+    const size_t ph = (size_t)P * H;
+
+    // 1. as ra_wiener_accumulate: the verdict on labels and params before anything is written
+    WnPrep prep;
+    const int prc = wn_prepare("ra_wiener_score", d_params, h_ctf, n, nx, P, k, stream, prep);
+    if (prc != RA_OK) return prc;
+
+    // 2. the accumulate's chunks; in each the particles in class order (stable), so that a class's sums are read while they are hot
+    const int C = wn_chunk(n, ph, npix);
+    std::vector<int> perm(n), start(k + 1);
+    for (int c0 = 0; c0 < n; c0 += C) {
+        const int cnt = std::min(C, n - c0);
+        std::fill(start.begin(), start.end(), 0);
+        for (int i = 0; i < cnt; i++) start[prep.lab[c0 + i] + 1]++;
+        for (int j = 0; j < k; j++) start[j + 1] += start[j];
+        for (int i = 0; i < cnt; i++) perm[c0 + start[prep.lab[c0 + i]]++] = i;
+    }
+
+    // 3. per chunk: rot_shift2D, forward transforms, scores
+    float *d_al = nullptr;
+    float2 *d_spec = nullptr, *d_gscr = nullptr;
+    int *d_perm = nullptr;
+    bool fixed = false;
+    const void *fk = wn_forward_fn(nx, pad, pl, &fixed);
+    const int fgrid = pl.gblk ? pf_gblk_grid(pl, C) : 0;
+    hipError_t he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_al, (size_t)C * npix * sizeof(float), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_spec, (size_t)C * ph * sizeof(float2), stream);
+    if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)fgrid * nx * H * sizeof(float2), stream);
+    if (he == hipSuccess) he = hipMallocAsync((void **)&d_perm, (size_t)n * sizeof(int), stream);
+    // pageable host source: hipMemcpyAsync stages it before it returns
+    if (he == hipSuccess) he = hipMemcpyAsync(d_perm, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream);
+    const double tau = d_reg ? 0.0 : 1.0 / (double)snr;
+    int rc = RA_OK;
+    for (int c0 = 0; c0 < n && he == hipSuccess && rc == RA_OK; c0 += C) {
+        int cnt = std::min(C, n - c0);
+        rc = ra_rot_shift2d(d_images + (size_t)c0 * npix, cnt, nx, d_params + c0, d_al, stream);
+        if (rc != RA_OK) break;
+        const float *al = d_al;
+        void *args_fixed[] = {&al, &cnt, &d_spec, &d_gscr};
+        PfPlan pl_arg = pl;
+        void *args_plan[] = {&al, &cnt, &d_spec, &pl_arg, &d_gscr};
+        he = hipLaunchKernel(fk, dim3(pl.gblk ? std::min(fgrid, cnt) : cnt), dim3(PF_THREADS), fixed ? args_fixed : args_plan, pl.lds, stream);
+        if (he == hipSuccess) he = hipGetLastError();
+        if (he == hipSuccess) {
+            hipLaunchKernelGGL(wn_score_kernel, dim3(cnt), dim3(WN_THREADS), 0, stream, (const float2 *)d_spec, P, H,
+                               (const int *)(d_perm + c0), (const int *)(prep.d_lab + c0), (const WnCtf *)(prep.d_cst + c0), flipped,
+                               (const float2 *)d_num, d_den, d_counts, tau, d_reg, leave_one_out, s_lo, s_hi, d_sums + (size_t)c0 * 3);
+            he = hipGetLastError();
+        }
+    }
+    for (void *p : {(void *)d_perm, (void *)d_gscr, (void *)d_spec, (void *)d_al})
+        if (p) (void)hipFreeAsync(p, stream);
+    prep.release(stream);
+    if (rc != RA_OK) return rc;
+    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_score", he);
 }

@@ -30,6 +30,16 @@
 //      R = mean(D0 + D1) / max(2F / (1 - F), floor), F = min(FRC, 0.999);
 //   3. wn_finalize_ssnr_kernel: wn_finalize_kernel's transforms of (N0 + N1) / (D0 + D1 + R(min(s, P/2))).
 // One writer per output element and a fixed order of every sum: bitwise reproducible.
+//
+// Per-particle agreement scores (ra_wiener_score; contract: wiener.py score_reference).  Per chunk, steps
+// 1 - 3 of the accumulation (the same kernels), then wn_score_kernel: one workgroup per particle, the chunk's particles in class
+// order (a class's N, D stay in L2 while its members are scored; the result does not depend on it).  The workgroup walks the
+// spectrum in 16 x 16 tiles (columns kx outer, rows n inner), each wave an 8 x 8 quarter, so that the particle's spectrum ([H][P])
+// and the class sums ([P][H]) are both read in 64-byte pieces.  Per element inside the shell band: c from the constants as in
+// wn_reduce_kernel, the rest of the class's estimate M = w (N - w Y) / (max(D - c^2, 0) + tau) in double (N, D as they are
+// without leave-one-out), and g Re(Y conj M), g |Y|^2, g |M|^2 added to the thread's three double partials in tile order; then a
+// fixed shuffle tree per wave and the four waves' sums added in wave order by one thread, which writes the particle's [3].  A
+// particle's sums depend on nothing but its own spectrum, constants and class sums: not on its place in the batch or the chunk.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -417,6 +427,89 @@ __global__ __launch_bounds__(WN_THREADS) void wn_frc_combine_kernel(const double
         for (int q = 0; q < 5; q++) a[q] += p[(size_t)q * S];
     }
     wn_frc_shell(a, counts2[2 * j] + counts2[2 * j + 1] >= min_count, ssnr_floor, frc + (size_t)j * S + s, reg + (size_t)j * S + s);
+}
+
+// ---- per-particle agreement scores
+
+#define WN_SCORE_TILE 16            // the score kernel's tile edge: 4 waves of 8 x 8
+
+// one element of one particle's score: y its spectrum, c its CTF, (N, D) its class's sums there, tau the Wiener term, g the
+// Hermitian weight; model false: the class has nothing to predict the particle with (M = 0).  a += (g Re(y conj M), g |y|^2, g |M|^2)
+__host__ __device__ inline void wn_score_element(float2 y, float c, int flipped, float2 N, float D, bool loo, bool model, double tau,
+                                                 double g, double *a)
+{
+    const double w = flipped ? fabsf(c) : c;
+    const double yx = y.x, yy = y.y;
+    double mx = 0.0, my = 0.0;
+    if (model) {
+        double nx = N.x, ny = N.y, d = D;
+        if (loo) {
+            nx -= w * yx;
+            ny -= w * yy;
+            d -= (double)c * (double)c;
+            if (d < 0.0) d = 0.0;
+        }
+        const double q = d + tau;
+        if (q != 0.0) {
+            const double f = w / q;
+            mx = f * nx;
+            my = f * ny;
+        }
+    }
+    a[0] += g * (yx * mx + yy * my);
+    a[1] += g * (yx * yx + yy * yy);
+    a[2] += g * (mx * mx + my * my);
+}
+
+// element (row n, column kx) of particle spectrum spec [H][P] against its class's num / den [P][H]: skipped outside the band
+// s_lo <= s <= s_hi (s_hi <= P/2); reg: the class's per-shell term [P/2 + 1], or null for the constant tau
+__host__ __device__ inline void wn_score_at(const float2 *spec, int P, int H, int n, int kx, const WnCtf &cst, int flipped,
+                                            const float2 *num, const float *den, bool loo, bool model, double tau, const float *reg,
+                                            int s_lo, int s_hi, double *a)
+{
+    // s_lo <= s <= s_hi by wn_shell's integer bounds, without the shell itself: s >= a is r2 > a (a - 1), s <= b is r2 <= b (b + 1)
+    const int ky = n <= P / 2 ? n : n - P, r2 = kx * kx + ky * ky;
+    if ((s_lo > 0 && r2 <= s_lo * (s_lo - 1)) || r2 > s_hi * (s_hi + 1)) return;
+    const float c = wn_ctf(cst, n < (P + 1) / 2 ? n : n - P, kx);
+    const size_t o = (size_t)n * H + kx;
+    wn_score_element(spec[(size_t)kx * P + n], c, flipped, num[o], den[o], loo, model, reg ? (double)reg[wn_shell(kx, ky)] : tau,
+                     (kx == 0 || 2 * kx == P) ? 1.0 : 2.0, a);
+}
+
+// grid: the chunk's particles; perm: chunk-local indices in class order; sums [chunk][3]
+__global__ __launch_bounds__(WN_THREADS) void wn_score_kernel(const float2 *__restrict__ spec, int P, int H, const int *__restrict__ perm,
+                                                              const int *__restrict__ lab, const WnCtf *__restrict__ cst, int flipped,
+                                                              const float2 *__restrict__ num, const float *__restrict__ den,
+                                                              const int *__restrict__ counts, double tau, const float *__restrict__ reg,
+                                                              int loo, int s_lo, int s_hi, double *__restrict__ sums)
+{
+    static_assert(WN_THREADS == 256 && WN_SCORE_TILE == 16, "four waves of 8 x 8 make one tile");
+    __shared__ double part[WN_THREADS / 64][3];
+    const int p = perm[blockIdx.x], cls = lab[p];
+    const size_t ph = (size_t)P * H;
+    const WnCtf c = cst[p];
+    const float2 *y = spec + (size_t)p * ph, *N = num + (size_t)cls * ph;
+    const float *D = den + (size_t)cls * ph, *R = reg ? reg + (size_t)cls * (P / 2 + 1) : nullptr;
+    const bool model = !loo || counts[cls] >= 2;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int tn = (wave & 1) * 8 + (lane & 7), tk = (wave >> 1) * 8 + (lane >> 3);
+    double a[3] = {0.0, 0.0, 0.0};
+    for (int k0 = 0; k0 < H; k0 += WN_SCORE_TILE) {
+        const int kx = k0 + tk;
+        if (kx >= H) continue;
+        for (int n = tn; n < P; n += WN_SCORE_TILE) wn_score_at(y, P, H, n, kx, c, flipped, N, D, loo != 0, model, tau, R, s_lo, s_hi, a);
+    }
+    for (int q = 0; q < 3; q++) {
+        double v = a[q];
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        if (lane == 0) part[wave][q] = v;
+    }
+    __syncthreads();
+    if (threadIdx.x < 3) {
+        double v = part[0][threadIdx.x];
+        for (int w = 1; w < WN_THREADS / 64; w++) v += part[w][threadIdx.x];
+        sums[(size_t)p * 3 + threadIdx.x] = v;
+    }
 }
 
 }  // namespace ralign

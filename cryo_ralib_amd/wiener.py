@@ -2,6 +2,7 @@
 
     python -m cryo_ralib_amd.wiener STACK PARAMS CTF OUT [--labels labels.npy] [--k K] [--snr S] [--nopad] [--flipped]
                                     [--min_count M] [--apix A] [--ou R] [--device D] [--ssnr [--ssnr_floor F] [--frc FRC.npz]]
+                                    [--scores SCORES.npz [--band LO HI] [--no_leave_one_out] [--keep F] [--min_cc T]]
 
 The contract, stated in float64 by `wiener_reference`: inputs are a stack x [n][nx][nx], params [n][4]
 (alpha, sx, sy, mirror, as api.rot_shift2d takes them), labels [n] in 0 .. k-1, a CTF table [n][9] in the layout of ctf.py,
@@ -37,6 +38,20 @@ shell P/2 take its term).  --snr then only sets the half averages V.  The FRC al
 s1 = the first shell s >= 1 with FRC < t (P/2 + 1 if none), P apix / (s1 - 1) A, or pixels without a pixel size.  The device path
 is ra_wiener_accumulate with labels 2j + h (`accumulate_halves`), ra_wiener_frc (`frc`) and ra_wiener_finalize_ssnr
 (`finalize_ssnr`); `ssnr_averages` runs all three.
+
+Per-particle agreement scores (--scores; DESIGN.md section 4.12, stated in float64 by `score_reference`) hold every particle
+against what the rest of its class predicts for it.  Given class sums N, D and sizes (normally over all particles, the scored ones
+included), for particle i of class j: N' = N_j - w_i Y_i, D' = max(D_j - c_i^2, 0) (leave-one-out, the default: a particle is part
+of the average it is compared with, and in a class of n noise images the plain correlation is about 1/sqrt(n), not 0; without it
+N' = N_j, D' = D_j), tau = 1/snr or the per-shell term reg[j][s] of the SSNR path, M_i = w_i N' / (D' + tau) (0 where that
+denominator is 0, and everywhere when leave-one-out leaves nobody: n_j < 2), and over the elements of the shell band
+s_lo <= s <= s_hi (default 1 .. P/2: no DC, everything up to Nyquist) with the Hermitian weights g:
+X_i = sum g Re(Y_i conj M_i), E_i = sum g |Y_i|^2, F_i = sum g |M_i|^2.  cc_i = X / sqrt(E F) (0 where E F = 0) and the
+least-squares amplitude scale_i = X / F (0 where F = 0); both nan in a class of fewer than max(min_count, 2) members
+(max(min_count, 1) without leave-one-out).  The device path is ra_wiener_score (`score`); `particle_scores` accumulates, runs the FRC
+when asked and scores; `select` turns cc into a mask (per class the best fraction --keep and / or cc >= --min_cc; unscored
+particles stay).  With --keep / --min_cc the tool writes OUT (and --frc) from the kept particles only, the halves still by the
+original particle index, and prints per class its size, the number kept and the kept particles' lowest and median cc.
 
 PARAMS is a driver's params.txt (idx angle sx sy mirror class; the class column gives the labels) or an initial2Dparams.txt
 (alpha sx sy mirror; one class); --labels (an int .npy) overrides the classes, e.g. with k-means labels.  CTF is a [n][9] .npy
@@ -190,10 +205,16 @@ def shells(P):
     return s, g
 
 
-def half_labels(labels, index0=0):
-    """2 j + h per particle, h = (index0 + i) % 2: the labels of the half sums (2k classes)"""
+def half_labels(labels, index0=0, index=None):
+    """2 j + h per particle, h = (index0 + i) % 2: the labels of the half sums (2k classes).  index: the particles' global indices
+    [n] instead of index0 + i (a subset of a stack that keeps its original even / odd split)"""
     lab = np.asarray(labels).astype(np.int64)
-    return 2 * lab + (int(index0) + np.arange(lab.shape[0])) % 2
+    if index is None:
+        return 2 * lab + (int(index0) + np.arange(lab.shape[0])) % 2
+    idx = np.asarray(index)
+    if idx.shape != lab.shape or (idx.size and not np.issubdtype(idx.dtype, np.integer)):
+        raise WienerError("index is [%d] integers (the particles' global indices), got %s %s" % (lab.shape[0], idx.dtype, idx.shape))
+    return 2 * lab + idx.astype(np.int64) % 2
 
 
 def frc_from_sums(num2, den2, counts2, nx, pad=True, snr=1.0, min_count=1, ssnr_floor=SSNR_FLOOR):
@@ -288,6 +309,122 @@ def resolutions(frc, counts, nx, pad=True, apix=None, min_count=1):
             "units": "px" if apix is None else "A"}
 
 
+# ---- the score contract in float64 numpy
+
+def check_score(nx, pad, k, snr=1.0, reg=None, band=None):
+    """the score's own domain: the band 0 <= s_lo <= s_hi <= P/2 (None: 1 .. P/2), and either a finite snr > 0 or reg [k][P/2 + 1]
+    finite and >= 0 with k <= 512; returns (s_lo, s_hi, reg float64 or None)"""
+    P = 2 * nx if pad else nx
+    try:
+        lo, hi = (min(1, P // 2), P // 2) if band is None else tuple(band)
+    except (TypeError, ValueError):
+        raise WienerError("the shell band is (s_lo, s_hi), got %r" % (band,))
+    if not all(isinstance(v, (int, np.integer)) for v in (lo, hi)) or not 0 <= lo <= hi <= P // 2:
+        raise WienerError("the shell band needs integers 0 <= s_lo <= s_hi <= P/2 = %d, got %r" % (P // 2, band))
+    if reg is None:
+        if not (np.isfinite(snr) and snr > 0):
+            raise WienerError("need a finite snr > 0, got %r" % snr)
+        return int(lo), int(hi), None
+    check_ssnr(k, SSNR_FLOOR)
+    r = np.asarray(reg, np.float64)
+    if r.shape != (k, P // 2 + 1) or not np.isfinite(r).all() or (r < 0).any():
+        raise WienerError("the per-shell term is [%d][%d], finite and >= 0, got %s" % (k, P // 2 + 1, r.shape))
+    return int(lo), int(hi), r
+
+
+def _host_sums(num, den, counts, k, P):
+    num = np.asarray(num)
+    if not np.iscomplexobj(num):
+        if num.ndim != 4 or num.shape[-1] != 2:
+            raise WienerError("class sums are [k][P][P/2 + 1] complex (or float pairs [..][2]), got %s" % (num.shape,))
+        num = num[..., 0].astype(np.float64) + 1j * num[..., 1].astype(np.float64)
+    num = num.astype(np.complex128)
+    den = np.asarray(den, np.float64)
+    counts = np.asarray(counts)
+    if num.shape != (k, P, P // 2 + 1) or den.shape != num.shape or counts.shape != (k,):
+        raise WienerError("class sums are [%d][%d][%d] and counts [%d], got %s, %s, %s"
+                          % (k, P, P // 2 + 1, k, num.shape, den.shape, counts.shape))
+    return num, den, counts.astype(np.int64)
+
+
+def scores_from_sums(sums, labels, counts, leave_one_out=True, min_count=1):
+    """(cc, scale) [n] from the three sums [n][3] = (X, E, F): cc = X / sqrt(E F) (0 where E F = 0), scale = X / F (0 where F = 0);
+    nan for particles of a class with fewer than max(min_count, 2) members (max(min_count, 1) without leave-one-out)"""
+    a = np.asarray(sums, np.float64).reshape(-1, 3)
+    X, E, F = a[:, 0], a[:, 1], a[:, 2]
+    ef = E * F
+    cc = np.where(ef > 0, X / np.sqrt(np.where(ef > 0, ef, 1.0)), 0.0)
+    scale = np.where(F > 0, X / np.where(F > 0, F, 1.0), 0.0)
+    lab = np.asarray(labels).astype(np.int64)
+    unscored = np.asarray(counts)[lab] < max(int(min_count), 2 if leave_one_out else 1)
+    cc[unscored] = np.nan
+    scale[unscored] = np.nan
+    return cc, scale
+
+
+def score_reference(x, params, labels, k, table, num, den, counts, snr=1.0, reg=None, leave_one_out=True, band=None, pad=True,
+                    flipped=False, min_count=1, aligned=None):
+    """float64 statement of the score contract: {"cc" [n], "scale" [n], "sums" [n][3] = (X, E, F)} of the particles against the
+    class sums num [k][P][P/2 + 1] (complex, or float pairs [..][2]), den, counts.  aligned: as for class_sums_reference"""
+    from . import synth
+    x, n, nx = _images(x)
+    prm, lab, tab = check_inputs(n, nx, params, labels, k, table)
+    lo, hi, reg = check_score(nx, pad, k, snr, reg, band)
+    P = 2 * nx if pad else nx
+    o = (P - nx) // 2
+    num, den, counts = _host_sums(num, den, counts, k, P)
+    tab = aligned_table(tab, prm)
+    s, g = shells(P)
+    sel = (s >= lo) & (s <= hi)
+    gs = g[sel]
+    sums = np.zeros((n, 3))
+    for i in range(n):
+        if aligned is not None:
+            y = np.asarray(aligned[i], np.float64)
+        else:
+            y = synth.rot_shift2d_np(x[i], prm[i, 0], prm[i, 1], prm[i, 2], int(prm[i, 3] != 0)).astype(np.float64)
+        big = np.zeros((P, P))
+        big[o:o + nx, o:o + nx] = y
+        Y = np.fft.rfft2(big)
+        c = _ctf.ctf_grid(tab[i], nx, P)
+        w = np.abs(c) if flipped else c
+        j = lab[i]
+        M = np.zeros_like(Y)
+        if not leave_one_out or counts[j] >= 2:
+            N, D = (num[j] - w * Y, np.maximum(den[j] - c * c, 0.0)) if leave_one_out else (num[j], den[j])
+            q = D + (1.0 / snr if reg is None else reg[j][np.minimum(s, P // 2)])
+            M = np.where(q != 0, w * N / np.where(q != 0, q, 1.0), 0.0)
+        sums[i] = ((gs * (Y * np.conj(M)).real[sel]).sum(), (gs * np.abs(Y[sel]) ** 2).sum(), (gs * np.abs(M[sel]) ** 2).sum())
+    cc, scale = scores_from_sums(sums, lab, counts, leave_one_out, min_count)
+    return {"cc": cc, "scale": scale, "sums": sums}
+
+
+def select(cc, labels, k, keep=None, min_cc=None):
+    """boolean mask [n] of the particles to keep.  Per class, the scored members by cc descending (ties: the lower index first):
+    keep=f (0 < f <= 1) keeps the first ceil(f n_j) of them, min_cc=t those with cc >= t; with both, a particle must pass both.
+    Unscored particles (cc nan) are always kept"""
+    cc = np.asarray(cc, np.float64)
+    lab = np.asarray(labels)
+    if cc.ndim != 1 or lab.shape != cc.shape or (cc.size and not np.issubdtype(lab.dtype, np.integer)):
+        raise WienerError("cc is [n] and labels [n] integers, got %s and %s %s" % (cc.shape, lab.dtype, lab.shape))
+    if not (isinstance(k, (int, np.integer)) and k >= 1) or (cc.size and (lab.min() < 0 or lab.max() >= k)):
+        raise WienerError("labels must lie in 0 .. k - 1 with k >= 1, got k = %r" % (k,))
+    if keep is not None and not (np.isfinite(keep) and 0 < keep <= 1):
+        raise WienerError("need 0 < keep <= 1, got %r" % (keep,))
+    if min_cc is not None and np.isnan(min_cc):
+        raise WienerError("min_cc is a number, got nan")
+    mask = np.ones(cc.shape, bool)
+    scored = ~np.isnan(cc)
+    if min_cc is not None:
+        mask[scored] = cc[scored] >= min_cc
+    if keep is not None:
+        for j in range(k):
+            idx = np.nonzero(scored & (lab == j))[0]
+            order = idx[np.argsort(-cc[idx], kind="stable")]
+            mask[order[int(np.ceil(keep * len(idx))):]] = False
+    return mask
+
+
 # ---- the device path
 
 def new_sums(k, nx, pad=True, device=0):
@@ -366,10 +503,11 @@ def _flat_halves(num2, den2, counts2):
     return k, num2.view(2 * k, *num2.shape[2:]), den2.view(2 * k, *den2.shape[2:]), counts2.view(2 * k)
 
 
-def accumulate_halves(images, params, labels, k, table, num2, den2, counts2, index0=0, pad=True, flipped=False):
+def accumulate_halves(images, params, labels, k, table, num2, den2, counts2, index0=0, pad=True, flipped=False, index=None):
     """accumulate into the half sums (new_half_sums) on the current stream: particle i of images goes to half (index0 + i) % 2 of
     its class, index0 the global index of images[0] (the engine's even / odd split), through ra_wiener_accumulate with labels
-    2j + h.  Labels outside 0 .. k - 1 are refused here (WienerError), the rest as by `accumulate`"""
+    2j + h.  index: the particles' global indices [n] instead of index0 + i (a subset that keeps its original split).  Labels
+    outside 0 .. k - 1 are refused here (WienerError), the rest as by `accumulate`"""
     n = int(images.shape[0])
     lab = np.asarray(labels)
     if lab.shape != (n,) or (n and not np.issubdtype(lab.dtype, np.integer)):
@@ -379,7 +517,7 @@ def accumulate_halves(images, params, labels, k, table, num2, den2, counts2, ind
     check_ssnr(k, SSNR_FLOOR)
     k2, num, den, counts = _flat_halves(num2, den2, counts2)
     assert k2 == k, "half sums of %d classes for k = %d" % (k2, k)
-    accumulate(images, params, half_labels(lab, index0), 2 * k, table, num, den, counts, pad, flipped)
+    accumulate(images, params, half_labels(lab, index0, index), 2 * k, table, num, den, counts, pad, flipped)
 
 
 def frc(num2, den2, counts2, nx, pad=True, snr=1.0, min_count=1, ssnr_floor=SSNR_FLOOR):
@@ -464,24 +602,103 @@ def wiener_averages(images, params, labels, k, ctf, snr=1.0, pad=True, flipped=F
 
 
 def ssnr_averages(images, params, labels, k, ctf, snr=1.0, ssnr_floor=SSNR_FLOOR, pad=True, flipped=False, min_count=1, index0=0,
-                  ou=None, preprocess=False, device=0, apix=None):
+                  ou=None, preprocess=False, device=0, apix=None, index=None):
     """SSNR-weighted averages of the stack on the device (the contract of ssnr_reference): ([k][nx][nx] float32 averages, class
     sizes [k], frc [k][P/2 + 1] float64, resolutions), all numpy; resolutions = {"res_05", "res_0143", "units"} at FRC 0.5 and
     0.143 in A with apix, or with table_apix(ctf) when the table gives one pixel size, else in pixels.  index0: the global index of
-    images[0] (the half split); the other arguments as for wiener_averages"""
+    images[0] (the half split), or index: every particle's global index [n] (a subset that keeps its original split); the other
+    arguments as for wiener_averages"""
     import torch
     check_ssnr(k, ssnr_floor)
     dev, x, prm, lab, tab = _device_stack(images, params, labels, k, ctf, snr, ou, preprocess, device)
     nx = int(x.shape[-1])
     with torch.cuda.device(dev):
         num2, den2, counts2 = new_half_sums(k, nx, pad, dev)
-        accumulate_halves(x, prm, lab, k, tab, num2, den2, counts2, index0, pad, flipped)
+        accumulate_halves(x, prm, lab, k, tab, num2, den2, counts2, index0, pad, flipped, index)
         f, reg = frc(num2, den2, counts2, nx, pad, snr, min_count, ssnr_floor)
         out = finalize_ssnr(num2, den2, counts2, reg, nx, pad, min_count)
         counts = counts2.sum(1).cpu().numpy()
         f = f.cpu().numpy()
         res = resolutions(f, counts, nx, pad, apix if apix is not None else table_apix(tab, nx), min_count)
         return out.cpu().numpy(), counts, f, res
+
+
+def score(images, params, labels, k, table, num, den, counts, snr=1.0, reg=None, leave_one_out=True, band=None, pad=True,
+          flipped=False, min_count=1):
+    """ra_wiener_score on the current stream: {"cc" [n], "scale" [n], "sums" [n][3] float64} (numpy) of images [n][nx][nx]
+    (contiguous float32 CUDA tensor) against the class sums num / den / counts (new_sums' layout, as `accumulate` left them; only
+    read).  reg: the per-shell term [k][P/2 + 1] (float32 CUDA tensor, `frc`'s) instead of 1/snr; band: (s_lo, s_hi), default
+    (1, P/2).  The band, snr, k and reg's shape are checked here (WienerError) before anything is launched; labels, params and
+    table rows as by `accumulate`"""
+    import ctypes
+    import torch
+    from . import api
+    assert images.is_cuda and images.is_contiguous() and images.dtype == torch.float32, "images: contiguous float32 CUDA tensor"
+    assert images.dim() == 3 and images.shape[1] == images.shape[2], "images: [n][nx][nx]"
+    n, nx = int(images.shape[0]), int(images.shape[-1])
+    prm = np.asarray(params, np.float64)
+    lab = np.asarray(labels).astype(np.int64)
+    tab = np.ascontiguousarray(table, np.float32)
+    if prm.shape != (n, 4) or lab.shape != (n,) or tab.shape != (n, 9):
+        raise WienerError("need params [%d][4], labels [%d] and a table [%d][9], got %s, %s, %s" % (n, n, n, prm.shape, lab.shape, tab.shape))
+    if not (isinstance(k, (int, np.integer)) and 1 <= k <= MAX_K):
+        raise WienerError("need 1 <= k <= %d, got %r" % (MAX_K, k))
+    if n and (lab.min() < 0 or lab.max() >= k):
+        raise WienerError("labels must lie in 0 .. %d, got %d .. %d" % (k - 1, lab.min(), lab.max()))
+    P = 2 * nx if pad else nx
+    lo, hi, _ = check_score(nx, pad, k, snr, None if reg is None else np.zeros((k, P // 2 + 1)), band)
+    shp = (k, P, P // 2 + 1)
+    for t, s, dt in ((num, shp + (2,), torch.float32), (den, shp, torch.float32), (counts, (k,), torch.int32)):
+        assert t.is_cuda and t.is_contiguous() and t.dtype == dt and tuple(t.shape) == s and t.device == images.device, \
+            "sums: new_sums(k, nx, pad) on the images' device"
+    if reg is not None:
+        if not (hasattr(reg, "is_cuda") and reg.is_cuda and reg.is_contiguous() and reg.dtype == torch.float32
+                and tuple(reg.shape) == (k, P // 2 + 1) and reg.device == images.device):
+            raise WienerError("reg: frc()'s contiguous float32 [%d][%d] on the images' device" % (k, P // 2 + 1))
+    rec = np.zeros(n, api.RESULT_DTYPE)
+    rec["alpha"], rec["sx"], rec["sy"] = prm[:, 0], prm[:, 1], prm[:, 2]
+    rec["mirror"] = (prm[:, 3] != 0).astype(np.int32)
+    rec["ref_id"] = lab.astype(np.int32)
+    d_rec = torch.from_numpy(rec.view(np.uint8)).to(images.device)
+    sums = torch.zeros((n, 3), dtype=torch.float64, device=images.device)
+    stream = torch.cuda.current_stream(images.device)
+    with torch.cuda.device(images.device):
+        api._check(api.load_library().ra_wiener_score(
+            ctypes.c_void_p(images.data_ptr()), n, nx, ctypes.c_void_p(d_rec.data_ptr()), tab.ctypes.data_as(api.float_ptr),
+            int(bool(pad)), int(bool(flipped)), int(k), ctypes.c_void_p(num.data_ptr()), ctypes.c_void_p(den.data_ptr()),
+            ctypes.c_void_p(counts.data_ptr()), float(snr), ctypes.c_void_p(reg.data_ptr()) if reg is not None else None,
+            int(bool(leave_one_out)), lo, hi, ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(stream.cuda_stream)),
+            "ra_wiener_score")
+        h_sums, h_counts = sums.cpu().numpy(), counts.cpu().numpy()
+    cc, scale = scores_from_sums(h_sums, lab, h_counts, leave_one_out, min_count)
+    return {"cc": cc, "scale": scale, "sums": h_sums}
+
+
+def particle_scores(images, params, labels, k, ctf, snr=1.0, ssnr=False, ssnr_floor=SSNR_FLOOR, leave_one_out=True, band=None,
+                    pad=True, flipped=False, min_count=1, index0=0, ou=None, preprocess=False, device=0):
+    """every particle of the stack against its class's Wiener estimate, on the device: ({"cc", "scale", "sums"}, class sizes [k]),
+    numpy (the contract of score_reference on the stack's own sums).  ssnr=False: accumulate, then score with 1/snr.  ssnr=True:
+    the half sums (index0 as for ssnr_averages), the FRC's per-shell term, and the score against N0 + N1, D0 + D1 with that term;
+    snr then only sets the half averages.  The other arguments as for wiener_averages"""
+    import torch
+    if ssnr:
+        check_ssnr(k, ssnr_floor)
+    dev, x, prm, lab, tab = _device_stack(images, params, labels, k, ctf, snr, ou, preprocess, device)
+    nx = int(x.shape[-1])
+    check_score(nx, pad, k, snr, None, band)
+    with torch.cuda.device(dev):
+        if not ssnr:
+            num, den, counts = new_sums(k, nx, pad, dev)
+            accumulate(x, prm, lab, k, tab, num, den, counts, pad, flipped)
+            reg = None
+        else:
+            num2, den2, counts2 = new_half_sums(k, nx, pad, dev)
+            accumulate_halves(x, prm, lab, k, tab, num2, den2, counts2, index0, pad, flipped)
+            _, reg = frc(num2, den2, counts2, nx, pad, snr, min_count, ssnr_floor)
+            num, den = (num2[:, 0] + num2[:, 1]).contiguous(), (den2[:, 0] + den2[:, 1]).contiguous()
+            counts = counts2.sum(1).to(torch.int32).contiguous()
+        res = score(x, prm, lab, k, tab, num, den, counts, snr, reg, leave_one_out, band, pad, flipped, min_count)
+        return res, counts.cpu().numpy()
 
 
 # ---- command line
@@ -519,7 +736,27 @@ def main(argv=None):
     ap.add_argument("--ssnr_floor", type=float, default=SSNR_FLOOR, help="lower bound of the per-shell SSNR (with --ssnr)")
     ap.add_argument("--frc", default=None, metavar="FRC.npz",
                     help="with --ssnr: write frc [k][P/2 + 1], freq (cycles/pixel), counts, res_05, res_0143 and units here")
+    ap.add_argument("--scores", default=None, metavar="SCORES.npz",
+                    help="score every particle against its class's Wiener estimate (with --ssnr: the per-shell term) and write cc, "
+                         "scale, sums, labels, counts and the options used here")
+    ap.add_argument("--band", type=int, nargs=2, default=None, metavar=("LO", "HI"),
+                    help="with --scores: the shells LO .. HI that are compared (default 1 .. P/2)")
+    ap.add_argument("--no_leave_one_out", action="store_true",
+                    help="with --scores: compare with the class's estimate as it is, the particle's own term included")
+    ap.add_argument("--keep", type=float, default=None, metavar="F",
+                    help="with --scores: keep the best fraction F of every class by cc; OUT (and --frc) then come from the kept "
+                         "particles, and SCORES.npz gets the mask `keep`")
+    ap.add_argument("--min_cc", type=float, default=None, metavar="T", help="with --scores: keep the particles with cc >= T")
     args = ap.parse_args(argv)
+    if not args.scores:
+        for flag, given in (("--keep", args.keep is not None), ("--min_cc", args.min_cc is not None), ("--band", args.band is not None),
+                            ("--no_leave_one_out", args.no_leave_one_out)):
+            if given:
+                ap.error("%s needs --scores" % flag)
+    if args.keep is not None and not 0 < args.keep <= 1:
+        ap.error("--keep needs 0 < F <= 1, got %g" % args.keep)
+    if args.min_cc is not None and np.isnan(args.min_cc):
+        ap.error("--min_cc needs a number")
     from . import stackio
     try:
         stack = np.ascontiguousarray(stackio.read_stack(args.stack), np.float32)
@@ -541,9 +778,41 @@ def main(argv=None):
             raise WienerError("--frc needs --ssnr")
     except (WienerError, _ctf.CtfTableError, OSError, ValueError) as e:
         raise SystemExit("error: %s" % e)
+    if args.scores:
+        try:
+            check_score(nx, not args.nopad, k, args.snr, None, args.band)
+        except WienerError as e:
+            ap.error("--scores: %s" % e)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("no GPU visible: the averages run on the device (wiener_reference is the float64 checker)")
+    index = None
+    if args.scores:
+        res, counts = particle_scores(stack, prm, lab, k, tab, args.snr, args.ssnr, args.ssnr_floor, not args.no_leave_one_out,
+                                      args.band, not args.nopad, args.flipped, args.min_count, ou=args.ou,
+                                      preprocess=args.ou is not None, device=args.device)
+        P = 2 * nx if not args.nopad else nx
+        band = tuple(args.band) if args.band else (min(1, P // 2), P // 2)
+        extra = {}
+        pruned = args.keep is not None or args.min_cc is not None
+        if pruned:
+            mask = select(res["cc"], lab, k, args.keep, args.min_cc)
+            extra["keep"] = mask
+        np.savez(args.scores, cc=res["cc"], scale=res["scale"], sums=res["sums"], labels=lab.astype(np.int64), counts=counts,
+                 band=np.array(band), leave_one_out=not args.no_leave_one_out, snr=args.snr, ssnr=args.ssnr,
+                 ssnr_floor=args.ssnr_floor, flipped=args.flipped, pad=not args.nopad, min_count=args.min_count, **extra)
+        print("%s: scores of %d particles in %d classes (shells %d .. %d%s%s)"
+              % (args.scores, n, k, band[0], band[1], "" if not args.no_leave_one_out else ", no leave-one-out",
+                 ", per-shell term" if args.ssnr else ", snr %g" % args.snr))
+        if pruned:
+            for j in range(k):
+                m = lab == j
+                c = res["cc"][m & mask]
+                c = c[~np.isnan(c)]
+                print("  class %3d: %7d particles, %7d kept   min cc %8.4f   median cc %8.4f"
+                      % (j, m.sum(), (m & mask).sum(), c.min() if c.size else np.nan, np.median(c) if c.size else np.nan))
+            index = np.nonzero(mask)[0]
+            stack, prm, lab, tab, n = stack[index], prm[index], lab[index], tab[index], len(index)
     if not args.ssnr:
         avg, counts = wiener_averages(stack, prm, lab, k, tab, args.snr, not args.nopad, args.flipped, args.min_count, ou=args.ou,
                                       preprocess=args.ou is not None, device=args.device)
@@ -553,7 +822,7 @@ def main(argv=None):
         return 0
     avg, counts, f, res = ssnr_averages(stack, prm, lab, k, tab, args.snr, args.ssnr_floor, not args.nopad, args.flipped,
                                         args.min_count, ou=args.ou, preprocess=args.ou is not None, device=args.device,
-                                        apix=args.apix)
+                                        apix=args.apix, index=index)
     stackio.write_stack(args.output, avg)
     P = 2 * nx if not args.nopad else nx
     if args.frc:

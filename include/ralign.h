@@ -356,6 +356,23 @@ int  ra_wiener_frc(const float *d_num2, const float *d_den2, const int *d_counts
 int  ra_wiener_finalize_ssnr(const float *d_num2, const float *d_den2, const int *d_counts2, const float *d_reg, int k, int nx, int pad,
                              int min_count, float *d_out, void *hip_stream);
 
+/* Per-particle agreement with the class's Wiener estimate (contract: cryo_ralib_amd/wiener.py
+ * score_reference).  d_images, d_params, h_ctf, pad, flipped and k as for ra_wiener_accumulate; d_num, d_den, d_counts are sums it
+ * left (over all chunks and ranks, so they normally contain the scored particles) and are only read.  For particle i of class j,
+ * with Y, c, w as above: N' = N_j - w Y, D' = max(D_j - c^2, 0) with leave_one_out = 1 (N_j, D_j with 0); tau = 1/snr, or
+ * d_reg[j][s] (ra_wiener_frc's term [k][P/2 + 1], used with N = N0 + N1, D = D0 + D1) when d_reg is not NULL;
+ * M = w N' / (D' + tau), 0 where that denominator is 0 and, with leave_one_out, everywhere when d_counts[j] < 2.
+ * d_sums [n][3] (double) = (sum g Re(Y conj M), sum g |Y|^2, sum g |M|^2) over the elements of shells s_lo <= s <= s_hi, shells
+ * and Hermitian weights g as for ra_wiener_frc.  cc = X / sqrt(E F) and the amplitude X / F are the caller's to form.
+ * RA_ERR_ARG, d_sums untouched, for everything ra_wiener_accumulate refuses (the device's verdict on labels and params
+ * included: one stream synchronisation), leave_one_out not 0 / 1, a band outside 0 <= s_lo <= s_hi <= P/2, d_reg NULL and snr not
+ * finite and > 0, d_reg given and k > 512 (snr is then ignored), or a null pointer; n == 0 is a no-op.  Scratch as for
+ * ra_wiener_accumulate.  The sums are double, reduced in a fixed order with one writer each: the same call gives the same bits,
+ * and a particle's three sums depend neither on its place in the batch nor on how a stack is cut into calls. */
+int  ra_wiener_score(const float *d_images, int n, int nx, const ra_result *d_params, const float *h_ctf, int pad, int flipped,
+                     int k, const float *d_num, const float *d_den, const int *d_counts, float snr, const float *d_reg,
+                     int leave_one_out, int s_lo, int s_hi, double *d_sums, void *hip_stream);
+
 /* Two-stage dimension reduction (utils_ralib.py MPCA / TwoSDR) of a stack in device memory, without an engine (DESIGN.md
  * section 4.6).  All pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL = default stream)
  * and allocates and frees its scratch on that stream, as ra_phase_flip does.  Images are [n][p][q] float32, centred on load
