@@ -55,6 +55,13 @@ RESULT_DTYPE = np.dtype([("alpha", np.float32), ("sx", np.float32), ("sy", np.fl
                          ("ref_id", np.int32), ("peak", np.float32), ("angle_bin", np.int32),
                          ("shift_idx", np.int32)])
 
+
+
+class RaLdsRow(ctypes.Structure):
+    _fields_ = [("kernel", ctypes.c_char * 64), ("static_bytes", ctypes.c_int), ("dynamic_bytes", ctypes.c_int),
+                ("limit_bytes", ctypes.c_int)]
+
+
 float_ptr = ctypes.POINTER(ctypes.c_float)
 aln_param_ptr = ctypes.POINTER(AlignParam)
 
@@ -68,7 +75,7 @@ EXPORTED_SYMBOLS = [
     "ra_reset_shifts", "ra_set_references", "ra_get_prepared_references", "ra_align", "ra_state_from_params", "ra_set_refine", "ra_set_class_references", "ra_align_classes",
     "ra_debug_spectra", "ra_transform_accumulate", "ra_update_references", "ra_normalize_particles", "ra_sync", "ra_kernel_time",
     "ra_fsc_len", "ra_class_fsc", "ra_last_class_fsc", "ra_fit_tanh", "ra_class_averages", "ra_filter_references",
-    "ra_state_from_params_dev", "ra_class_fsc_fit", "ra_filter_references_dev", "ra_last_refine_count",
+    "ra_state_from_params_dev", "ra_class_fsc_fit", "ra_filter_references_dev", "ra_last_refine_count", "ra_lds_report",
     "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
@@ -122,6 +129,7 @@ def load_library(path=None):
     L.ra_state_from_params.argtypes = [vp, vp, ctypes.c_int, float_ptr, vp]
     L.ra_set_refine.argtypes = [vp, ctypes.c_float]
     L.ra_last_refine_count.argtypes = [vp]
+    L.ra_lds_report.argtypes = [vp, ctypes.POINTER(RaLdsRow), ctypes.c_int]
     L.ra_state_from_params_dev.argtypes = [vp, vp, ctypes.c_int, vp, vp]
     L.ra_class_fsc_fit.argtypes = [vp, vp, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float, vp, vp]
     L.ra_filter_references_dev.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, ctypes.c_int, vp]
@@ -496,6 +504,17 @@ class Engine:
     def last_refine_count(self):
         """particles the last search launch re-evaluated in the CPU path's arithmetic (diagnostics; synchronises)"""
         return self.lib.ra_last_refine_count(self.handle)
+
+    def lds_report(self):
+        """the LDS ledger (ra_lds_report): one dict per kernel whose dynamic LDS the engine has raised -- kernel, static_bytes (of the
+        loaded code object), dynamic_bytes, limit_bytes (per workgroup of the device)"""
+        n = self.lib.ra_lds_report(self.handle, None, 0)
+        if n < 0:
+            _check(n, "ra_lds_report")
+        rows = (RaLdsRow * max(n, 1))()
+        n = min(n, self.lib.ra_lds_report(self.handle, rows, n))
+        return [{"kernel": rows[i].kernel.decode(), "static_bytes": rows[i].static_bytes, "dynamic_bytes": rows[i].dynamic_bytes,
+                 "limit_bytes": rows[i].limit_bytes} for i in range(n)]
 
     def state_from_params_dev(self, result, state, cs_dev):
         """state_from_params with the centre correction in a CUDA tensor [2] (no host value in the path)"""

@@ -70,8 +70,15 @@ struct WorkspacePlan {
     size_t bytes;          // everything ra_create and the first reference update take from the device
 };
 
+// one row of the LDS ledger (ra_lds_report): a kernel whose dynamic LDS the engine raised (raise_dynamic_lds)
+struct LdsRow {
+    std::string kernel;
+    int stat, dyn, limit;          // the code object's static LDS, the dynamic LDS asked for, the device's limit per workgroup (bytes)
+};
+
 struct ra_engine {
     ra_config cfg{};
+    std::vector<LdsRow> lds_rows;
     Geometry geo;
     DevGeom dg{};
     hipStream_t stream = nullptr;
@@ -160,6 +167,38 @@ struct ra_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> ev_ccf, ev_polar;
     size_t ev_used_ccf = 0, ev_used_polar = 0;
 };
+
+// Every site that raises a kernel's dynamic LDS goes through here.  The host rules that size the dynamic part know nothing of the
+// __shared__ arrays a kernel declares: the static size is read from the loaded code object and the sum compared with what a
+// workgroup of this device can have, BEFORE anything is launched -- a kernel that gains a static array then fails here, by name,
+// instead of in a launch.  Engines keep what was configured (ra_lds_report); e == nullptr: the engine-less entry points.
+static int raise_dynamic_lds(ra_engine *e, const void *fn, const char *name, size_t dyn)
+{
+    int dev = 0, limit = 0;
+    hipFuncAttributes fa{};
+    RA_HIP(hipGetDevice(&dev));
+    RA_HIP(hipDeviceGetAttribute(&limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    RA_HIP(hipFuncGetAttributes(&fa, fn));
+    const size_t stat = fa.sharedSizeBytes;
+    if (stat + dyn > (size_t)limit) {
+        char buf[512];
+        snprintf(buf, sizeof(buf), "%s: %zu bytes of static and %zu bytes of dynamic LDS do not fit the %d bytes of a workgroup", name, stat, dyn, limit);
+        g_last_error = buf;
+        return RA_ERR_HIP;
+    }
+    hipError_t he = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dyn);
+    if (he != hipSuccess) {
+        g_last_error = std::string("hipFuncSetAttribute(") + name + "): " + hipGetErrorString(he);
+        return RA_ERR_HIP;
+    }
+    if (e) {
+        auto it = std::find_if(e->lds_rows.begin(), e->lds_rows.end(), [&](const LdsRow &r) { return r.kernel == name; });
+        if (it == e->lds_rows.end()) e->lds_rows.push_back(LdsRow{name, (int)stat, (int)dyn, limit});
+        else { it->stat = (int)stat; it->dyn = (int)dyn; it->limit = limit; }
+    }
+    return RA_OK;
+}
+#define RA_LDS(e, kernel, dyn) raise_dynamic_lds(e, (const void *)(kernel), #kernel, dyn)
 
 template <typename T> static int upload(ra_engine *e, const std::vector<T> &h, const T **dptr)
 {
@@ -636,6 +675,24 @@ static bool resident_expected(const Geometry &g, const ra_config &cfg, bool gene
     return true;
 }
 
+// LDS of the exact kernels (ralign_exact.h) with their ring buffers resident: 2 lcirc floats (or lcirc + the 2 maxrin floats of a
+// candidate's spectrum, for very short ring sets) + the twiddles and samples of the f64 CCF (RA_EXACT_TABLE_BYTES)
+static size_t refine_resident_lds(const Geometry &g)
+{
+    return (size_t)((std::max(2 * g.lcirc, g.lcirc + 2 * g.maxrin) + 3) & ~3) * sizeof(float) + RA_EXACT_TABLE_BYTES(g.maxrin);
+}
+// ... and whether they keep those buffers in global scratch instead: when the resident layout and the kernels' static LDS
+// (RA_EXACT_STATIC_LDS) exceed the 160 KB of a workgroup, or when RALIGN_REFINE_GM=1 asks for that route (tests).  The one rule of
+// plan_workspace (no device: ra_legacy_bytes) and setup_refine.
+#define RA_LDS_PER_WORKGROUP ((size_t)160 * 1024)
+static bool refine_rings_global(const Geometry &g)
+{
+    // (a candidate's spectrum, maxrin doubles, lies in the second half of a block of global scratch: ring sets shorter than that
+    // keep the resident layout, which has room for it)
+    if (getenv("RALIGN_REFINE_GM") && atoi(getenv("RALIGN_REFINE_GM")) != 0 && g.lcirc >= 2 * g.maxrin) return true;
+    return refine_resident_lds(g) + RA_EXACT_STATIC_LDS > RA_LDS_PER_WORKGROUP;
+}
+
 static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, bool generic)
 {
     WorkspacePlan w{};
@@ -691,9 +748,8 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, boo
     const size_t sums_ws = xs ? nseg * chunk * sizeof(int) + std::min<size_t>(512, (1024 + nseg - 1) / nseg) * nseg * npix * sizeof(float) + (size_t)chunk * sizeof(float2)
                               : w.alscratch_floats * sizeof(float) + nseg * chunk * sizeof(int) + 16 * nseg * npix * sizeof(float);
     // sub-bin refinement (ralign_exact.h): exact reference spectra, the list of flagged particles, global ring buffers of large boxes
-    const size_t lds_ref = (size_t)std::max(2 * g.lcirc, g.lcirc + 2 * g.maxrin) * sizeof(float) + RA_EXACT_TABLE_BYTES(g.maxrin);
     const size_t exact_ws = (size_t)cfg.nref * g.lcirc * sizeof(float) + (size_t)chunk * sizeof(RefineRec) +
-                            (lds_ref > 160 * 1024 - 1024 ? (size_t)std::max(256, cfg.nref) * 2 * g.lcirc * sizeof(float) : 0);
+                            (refine_rings_global(g) ? (size_t)std::max(256, cfg.nref) * 2 * g.lcirc * sizeof(float) : 0);
     w.bytes = (w.refspec_floats + w.b_floats + 2) * sizeof(float) + search_ws + sums_ws + exact_ws +
               (resident ? 0 : w.zscr_recs * sizeof(float2)) + refine + tables;
     // every hipMalloc is rounded up to the allocator's granule; ~40 small tables and buffers
@@ -839,8 +895,8 @@ static int setup_fused(ra_engine *e)
     for (int pk = 0; pk < (e->tiled ? 1 : 2); pk++) {
         const fused_fn fk = e->tiled ? select_tiled(fp.f.nh, e->dg.sbuf) : select_fused(g.maxrin, e->cfg.nref, fp.f.nzr, e->dg.sbuf, pk != 0, e->tcrop);
         if (!fk) continue;
-        hipError_t he = hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds_bytes);
-        if (he != hipSuccess) { g_last_error = std::string("hipFuncSetAttribute(fused): ") + hipGetErrorString(he); return RA_ERR_HIP; }
+        const std::string kn = std::string(e->tiled ? "search_tiled_kernel" : pk ? "search_fused_kernel<pack>" : "search_fused_kernel") + (e->tcrop ? " (crop)" : "");
+        if ((rc = raise_dynamic_lds(e, (const void *)fk, kn.c_str(), fp.lds_bytes))) return rc;
     }
     if (getenv("RALIGN_INFO")) fprintf(stderr, "libralign_hip: %s plan: %zu bytes of LDS (polar part %zu), sbuf %d, pst %d, nzr %d, rz %d\n", e->tiled ? "tiled" : "fused", fp.lds_bytes, e->lds_polar, e->dg.sbuf, e->dg.pst, fp.f.nzr, fp.f.rz);
     e->fused = true;
@@ -921,9 +977,7 @@ static int setup_solo(ra_engine *e)
         if (!e->d_Bf && (rc = dev_alloc(e, &e->d_Bf, (size_t)fp.f.b_floats + 256, true))) return rc;
         if (!e->d_gcdc && (rc = dev_alloc(e, &e->d_gcdc, (size_t)e->cfg.nref, true))) return rc;
         fp.f.bsrc = e->d_fbsrc; fp.f.cdc_w = e->d_gcdc;
-        hipError_t he = hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds_bytes);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)search_pair_kernel<256, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds_bytes);
-        if (he != hipSuccess) { g_last_error = std::string("hipFuncSetAttribute(pair): ") + hipGetErrorString(he); return RA_ERR_HIP; }
+        if ((rc = raise_dynamic_lds(e, (const void *)fk, "search_pair_kernel", fp.lds_bytes)) || (rc = raise_dynamic_lds(e, (const void *)search_pair_kernel<256, 1>, "search_pair_kernel<256, 1>", fp.lds_bytes))) return rc;
         if (getenv("RALIGN_INFO")) fprintf(stderr, "libralign_hip: pair plan: %zu bytes of LDS, image %d x %d, 2 ring buffers of %d floats, %d jobs, %d tiles of 2 x %d reference pairs\n",
                                            fp.lds_bytes, fp.f.s_rows, fp.f.s_pst, fp.f.s_sbuf, e->dg.n_job, fp.f.ntile, fp.f.nrpw);
         e->solo = true; e->pair = true;
@@ -939,10 +993,8 @@ static int setup_solo(ra_engine *e)
     if (!e->d_Bf && (rc = dev_alloc(e, &e->d_Bf, (size_t)fp.f.b_floats + 256, true))) return rc;
     if (!e->d_gcdc && (rc = dev_alloc(e, &e->d_gcdc, (size_t)e->cfg.nref, true))) return rc;
     fp.f.bsrc = e->d_fbsrc; fp.f.cdc_w = e->d_gcdc;
-    hipError_t he = hipFuncSetAttribute((const void *)fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds_bytes);
-    if (he == hipSuccess)          // ra_debug_spectra: the polar stage through the solo kernel's debug path
-        he = hipFuncSetAttribute((const void *)search_solo_kernel<512, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)fp.lds_bytes);
-    if (he != hipSuccess) { g_last_error = std::string("hipFuncSetAttribute(solo): ") + hipGetErrorString(he); return RA_ERR_HIP; }
+    if ((rc = raise_dynamic_lds(e, (const void *)fk, e->duo ? "search_duo_kernel" : "search_solo_kernel", fp.lds_bytes)) ||
+        (rc = raise_dynamic_lds(e, (const void *)search_solo_kernel<512, 1, true>, "search_solo_kernel<512, 1, true>", fp.lds_bytes))) return rc;          // ra_debug_spectra: the polar stage through the solo kernel's debug path
     if (getenv("RALIGN_INFO")) fprintf(stderr, "libralign_hip: %s plan:", e->duo ? "duo" : "solo");
     if (getenv("RALIGN_INFO")) fprintf(stderr, " %zu bytes of LDS, image %d x %d, ring buffer %d floats, %d jobs, %d tiles of %d reference pairs\n",
                                        fp.lds_bytes, fp.f.s_rows, fp.f.s_pst, fp.f.s_sbuf, e->dg.n_job, fp.f.ntile, fp.f.nh);
@@ -972,8 +1024,7 @@ static int setup_zones(ra_engine *e)
         if ((rc = dev_grow(e, &e->d_stats_part, need, true))) return rc;
         e->stats_part_cap = need;
     }
-    hipError_t he = hipFuncSetAttribute((const void *)polar_zone_kernel<RA_ZONE_NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)zp.lds_bytes);
-    if (he != hipSuccess) { g_last_error = std::string("hipFuncSetAttribute(zones): ") + hipGetErrorString(he); return RA_ERR_HIP; }
+    if ((rc = RA_LDS(e, polar_zone_kernel<RA_ZONE_NW>, zp.lds_bytes))) return rc;
     e->zdev.zones = e->d_zone_desc; e->zdev.rowtab = e->d_zone_rows; e->zdev.pixtab = e->d_zone_pix;
     e->zdev.nzone = (int)zp.zones.size(); e->zdev.nchunk = zp.nchunk; e->zdev.nquad_total = zp.nquad_total; e->zdev.max_rows = zp.max_rows;
     if (getenv("RALIGN_INFO")) {
@@ -1031,12 +1082,24 @@ static int setup_refine(ra_engine *e)
     const Geometry &g = e->geo;
     e->refine_ok = false;
     if (getenv("RALIGN_REFINE")) e->refine_thr = (float)atof(getenv("RALIGN_REFINE"));
-    // ring buffers (2 lcirc floats) + the twiddles and samples of the f64 CCF (RA_EXACT_TABLE_BYTES)
-    e->lds_refine = (size_t)((std::max(2 * g.lcirc, g.lcirc + 2 * g.maxrin) + 3) & ~3) * sizeof(float) + RA_EXACT_TABLE_BYTES(g.maxrin);
+    e->lds_refine = refine_resident_lds(g);
     if (g.lcirc & 1) return RA_OK;
     // large boxes: one offset's rings exceed the LDS (271 KB at 256 x 256 / ou = 120) -- the same kernels with the ring buffers
-    // in global scratch
-    e->refine_gm = e->lds_refine > 160 * 1024 - 1024;          // (the kernel's static LDS: reduction scratch and the tie candidates, ~0.7 KB)
+    // in global scratch.  The rule reserves RA_EXACT_STATIC_LDS for the kernels' static LDS (reduction scratch, the tie candidates
+    // and their replay list: 1280 bytes); the figure of the loaded code object must not exceed the reserve, or the rule -- which
+    // plan_workspace shares and applies without a device -- would keep a geometry in LDS that no longer fits.
+    for (const void *fn : {(const void *)refine_winner_kernel<false>, (const void *)refspec_exact_kernel<false>}) {
+        hipFuncAttributes fa{};
+        RA_HIP(hipFuncGetAttributes(&fa, fn));
+        if (fa.sharedSizeBytes > RA_EXACT_STATIC_LDS) {
+            char buf[256];
+            snprintf(buf, sizeof(buf), "the exact kernels have %zu bytes of static LDS, RA_EXACT_STATIC_LDS reserves %zu: update the reserve (ralign_exact.h)",
+                     (size_t)fa.sharedSizeBytes, RA_EXACT_STATIC_LDS);
+            g_last_error = buf;
+            return RA_ERR_HIP;
+        }
+    }
+    e->refine_gm = refine_rings_global(g);
     e->refine_grid = e->refine_gm ? 256 : 2048;
     if (e->refine_gm) e->lds_refine = RA_EXACT_TABLE_BYTES(g.maxrin);
     std::vector<float> tw;
@@ -1060,12 +1123,9 @@ static int setup_refine(ra_engine *e)
     if (e->refine_gm) {
         if ((rc = dev_alloc(e, &e->d_rscratch, (size_t)std::max(e->refine_grid, e->cfg.nref) * 2 * g.lcirc, false))) return rc;
         // the f64 twiddles and samples stay in LDS (24 maxrin bytes: 96 KB at maxrin 4096, beyond the 64 KB a kernel gets unasked)
-        hipError_t he = hipFuncSetAttribute((const void *)refine_winner_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_refine);
-        if (he != hipSuccess) { g_last_error = std::string("hipFuncSetAttribute(refine, global ring buffers): ") + hipGetErrorString(he); return RA_ERR_HIP; }
+        if ((rc = RA_LDS(e, refine_winner_kernel<true>, e->lds_refine))) return rc;
     } else {
-        hipError_t he = hipFuncSetAttribute((const void *)refine_winner_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_refine);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)refspec_exact_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_refine);
-        if (he != hipSuccess) { g_last_error = std::string("hipFuncSetAttribute(refine): ") + hipGetErrorString(he); return RA_ERR_HIP; }
+        if ((rc = RA_LDS(e, refine_winner_kernel<false>, e->lds_refine)) || (rc = RA_LDS(e, refspec_exact_kernel<false>, e->lds_refine))) return rc;
     }
     e->refine_ok = true;
     return RA_OK;
@@ -1268,28 +1328,27 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
     while (e->g_P > 1 && (size_t)e->g_P * (g.maxrin + 1) * sizeof(float2) > 66 * 1024) e->g_P >>= 1;      // two workgroups per CU
     e->lds_gccf = ((size_t)e->g_P * (g.maxrin + 1) + g.maxrin) * sizeof(float2);      // pair buffers (in-place transforms) + twiddle table
     e->lds_gpolar = ((size_t)(RA_GEN_THREADS / 64 + 1) * g.maxrin + e->dg.n_qtab) * sizeof(float2);      // per-wave ring buffers + twiddle table + (sinf, cosf) tables
-    hipError_t he = hipSuccess;
     if (!e->generic) {
-        he = hipFuncSetAttribute((const void *)polar_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_polar);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)ref_polar_fft_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_ref);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)select_ccf(g.maxrin), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_ccf);
+        if (!rc) rc = RA_LDS(e, polar_fft_kernel, e->lds_polar);
+        if (!rc) rc = RA_LDS(e, ref_polar_fft_kernel, e->lds_ref);
+        if (!rc) rc = raise_dynamic_lds(e, (const void *)select_ccf(g.maxrin), "ccf_kernel", e->lds_ccf);
     } else {
-        he = hipFuncSetAttribute((const void *)gpolar_kernel(e, false), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_gpolar);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)gpolar_kernel(e, true), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_gpolar);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)ccf_generic_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_gccf);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)ccf_generic_kernel<1, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_gccf);
-        if (he == hipSuccess) he = hipFuncSetAttribute((const void *)ccf_generic_kernel<2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_gccf);
+        if (!rc) rc = raise_dynamic_lds(e, (const void *)gpolar_kernel(e, false), "polar_generic_kernel<false>", e->lds_gpolar);
+        if (!rc) rc = raise_dynamic_lds(e, (const void *)gpolar_kernel(e, true), "polar_generic_kernel<true>", e->lds_gpolar);
+        if (!rc) rc = raise_dynamic_lds(e, (const void *)ccf_generic_kernel<2, 2>, "ccf_generic_kernel<2, 2>", e->lds_gccf);
+        if (!rc) rc = raise_dynamic_lds(e, (const void *)ccf_generic_kernel<1, 7>, "ccf_generic_kernel<1, 7>", e->lds_gccf);
+        if (!rc) rc = raise_dynamic_lds(e, (const void *)ccf_generic_kernel<2, 7>, "ccf_generic_kernel<2, 7>", e->lds_gccf);
         if (g.maxrin == 1024) {
-            const int lds2 = (int)(((size_t)8 * RA_IFFT3_PSTRIDE + 16 * 16 + 16 * 64) * sizeof(float2));
-            if (he == hipSuccess) he = hipFuncSetAttribute((const void *)gccf_ifft_kernel<1, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-            if (he == hipSuccess) he = hipFuncSetAttribute((const void *)gccf_ifft_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-            if (he == hipSuccess) he = hipFuncSetAttribute((const void *)gccf_ifft_kernel<2, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
-            if (he == hipSuccess) he = hipFuncSetAttribute((const void *)gccf_ifft_kernel<4, 7>, hipFuncAttributeMaxDynamicSharedMemorySize, lds2);
+            const size_t lds2 = ((size_t)8 * RA_IFFT3_PSTRIDE + 16 * 16 + 16 * 64) * sizeof(float2);
+            if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<1, 7>, "gccf_ifft_kernel<1, 7>", lds2);
+            if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<2, 2>, "gccf_ifft_kernel<2, 2>", lds2);
+            if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<2, 7>, "gccf_ifft_kernel<2, 7>", lds2);
+            if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<4, 7>, "gccf_ifft_kernel<4, 7>", lds2);
         }
     }
-    if (he == hipSuccess && !e->xf_generic) he = hipFuncSetAttribute((const void *)transform_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_xf);
-    if (he == hipSuccess) he = hipFuncSetAttribute((const void *)class_sum_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 64);
-    if (he != hipSuccess) { g_last_error = std::string("hipFuncSetAttribute: ") + hipGetErrorString(he); ra_destroy(e); return RA_ERR_HIP; }
+    if (!rc && !e->xf_generic) rc = RA_LDS(e, transform_kernel, e->lds_xf);
+    if (!rc) rc = RA_LDS(e, class_sum_kernel, (size_t)160 * 1024 - 64);
+    if (rc) { ra_destroy(e); return rc; }
 
     // workspace.  The spectra panels and candidate records of the two-kernel path are allocated on first use only
     // (ensure_unfused_ws); the fused kernel needs candidate records alone.
@@ -1392,6 +1451,18 @@ extern "C" int ra_last_refine_count(ra_engine *e)
     int h = 0;
     if (hipStreamSynchronize(e->stream) != hipSuccess || hipMemcpy(&h, e->d_rcount, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return RA_ERR_HIP;
     return h;
+}
+// the LDS ledger: every kernel whose dynamic LDS this engine raised, with the static LDS of the loaded code object
+extern "C" int ra_lds_report(const ra_engine *e, ra_lds_row *rows, int cap)
+{
+    if (!e || cap < 0 || (cap > 0 && !rows)) return RA_ERR_ARG;
+    const int n = (int)e->lds_rows.size();
+    for (int i = 0; i < std::min(n, cap); i++) {
+        const LdsRow &r = e->lds_rows[i];
+        snprintf(rows[i].kernel, sizeof(rows[i].kernel), "%s", r.kernel.c_str());
+        rows[i].static_bytes = r.stat; rows[i].dynamic_bytes = r.dyn; rows[i].limit_bytes = r.limit;
+    }
+    return n;
 }
 extern "C" int ra_search_tiled(const ra_engine *e) { return !e ? RA_ERR_ARG : (e->fused && e->tiled) ? 1 : 0; }
 extern "C" int ra_search_path(const ra_engine *e) { return !e ? RA_ERR_ARG : e->solo ? 3 : e->fused ? 1 : e->generic ? 2 : 0; }
@@ -1642,8 +1713,17 @@ extern "C" int ra_set_class_references(ra_engine *e, const float *d_refs, int nc
                        (const float *)e->d_cls_refspec, 1, e->d_cls_Bf);
     RA_HIP(hipGetLastError());
     if (e->refine_ok && e->refine_thr != 0.f && e->d_cls_refx) {
-        hipLaunchKernelGGL(refspec_exact_kernel<false>, dim3(ncls), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr,
-                           (const float *)e->d_wr, (const float *)e->d_twx, (const int *)e->d_twxoff, d_refs, ncls, e->d_cls_refx, (float *)nullptr);
+        if (e->refine_gm) {          // ring buffers in global scratch: as many classes per launch as the scratch has blocks (setup_refine)
+            const int cap = std::max(e->refine_grid, e->cfg.nref);
+            for (int c0 = 0; c0 < ncls; c0 += cap) {
+                const int cnt = std::min(cap, ncls - c0);
+                hipLaunchKernelGGL(refspec_exact_kernel<true>, dim3(cnt), dim3(RA_EXACT_THREADS), 0, e->stream, e->dg, (const int *)e->d_numr,
+                                   (const float *)e->d_wr, (const float *)e->d_twx, (const int *)e->d_twxoff, d_refs + (size_t)c0 * e->geo.nx * e->geo.nx, cnt,
+                                   e->d_cls_refx + (size_t)c0 * e->geo.lcirc, e->d_rscratch);
+            }
+        } else
+            hipLaunchKernelGGL(refspec_exact_kernel<false>, dim3(ncls), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr,
+                               (const float *)e->d_wr, (const float *)e->d_twx, (const int *)e->d_twxoff, d_refs, ncls, e->d_cls_refx, (float *)nullptr);
         RA_HIP(hipGetLastError());
     }
     e->cls_ready = ncls;
@@ -1929,7 +2009,10 @@ static int transform_sum(ra_engine *e, const float *d_particles, int n, int inde
     const xs_fn fn = tiles ? transform_sum_tile_kernel : select_xs(nx, &nband);
     const int ntile = ((nx + RA_XT_TS - 1) / RA_XT_TS) * ((nx + RA_XT_TS - 1) / RA_XT_TS);
     const size_t xs_lds = tiles ? (size_t)2 * RA_XT_BB * RA_XT_BB * sizeof(float) : (size_t)(nx + 2) * ((nx + 2) | 1) * sizeof(float);
-    if (xs_lds > 64 * 1024) RA_HIP(hipFuncSetAttribute((const void *)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)xs_lds));
+    if (xs_lds > 64 * 1024) {
+        const int rc = raise_dynamic_lds(e, (const void *)fn, tiles ? "transform_sum_tile_kernel" : "transform_sum_kernel", xs_lds);
+        if (rc) return rc;
+    }
     for (int start = 0; start < n; start += RA_XS_BATCH) {
         const int cn = std::min(RA_XS_BATCH, n - start);
         // runs per segment: ~1024 workgroups, at least ~8 members per run on average
@@ -2145,7 +2228,7 @@ static int class_fsc_kernels(ra_engine *e, const float *d_sums, int masked)
     }
     const int threads = std::min(1024, (RA_FSC_PARTS * len + 63) / 64 * 64);
     const size_t lds = (size_t)RA_FSC_PARTS * len * 4 * sizeof(double);
-    if (lds > 64 * 1024) RA_HIP(hipFuncSetAttribute((const void *)fsc_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 64 * 1024 && (rc = RA_LDS(e, fsc_kernel, lds))) return rc;
     hipLaunchKernelGGL(fsc_kernel, dim3(R), dim3(threads), lds, e->stream, nx, e->d_rfF, e->d_fsc_off, e->d_fsc_idx, e->d_rffsc);
     RA_HIP(hipGetLastError());
     return RA_OK;
@@ -2808,7 +2891,7 @@ extern "C" int ra_phase_flip(float *d_images, int n, int nx, const float *ctf, i
     }
     const bool fixed = fk != nullptr;
     if (!fixed) fk = pl.gblk ? (const void *)phase_flip_kernel<true> : (const void *)phase_flip_kernel<false>;
-    RA_HIP(hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds));
+    if (const int rc = raise_dynamic_lds(nullptr, fk, fixed ? "phase_flip_fixed_kernel" : "phase_flip_kernel", (size_t)pl.lds)) return rc;
     const size_t blk_bytes = (size_t)nx * pl.H * sizeof(float2);
     const int grid = pl.gblk ? pf_gblk_grid(pl, n) : n;
     float *d_ctf = nullptr;
@@ -2889,9 +2972,8 @@ extern "C" int ra_sdr_gram(const float *d_images, int n, int p, int q, const flo
     const int nrun = (n + g.run - 1) / g.run, TD = 16 * g.ns;
     const size_t lds = (size_t)16 * g.kt * (2 * TD + 16) * sizeof(float);
     const void *fk = form == 0 ? (const void *)sdr_gram_kernel<0> : form == 1 ? (const void *)sdr_gram_kernel<1> : (const void *)sdr_gram_kernel<2>;
-    hipError_t he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (he != hipSuccess) return sdr_launch_error("ra_sdr_gram", he);
-    he = hipMallocAsync((void **)&g.part, (size_t)nrun * g.ntile * TD * TD * sizeof(float), stream);
+    if (const int rc = raise_dynamic_lds(nullptr, fk, "sdr_gram_kernel", lds)) return rc;
+    hipError_t he = hipMallocAsync((void **)&g.part, (size_t)nrun * g.ntile * TD * TD * sizeof(float), stream);
     if (he != hipSuccess) return sdr_launch_error("ra_sdr_gram", he);
     void *args[] = {&g};
     he = hipLaunchKernel(fk, dim3(nrun, g.ntile), dim3(SDR_THREADS), args, lds, stream);
@@ -2916,11 +2998,9 @@ extern "C" int ra_sdr_project(const float *d_images, int n, int p, int q, const 
     }
     if (!d_images || !d_A || !d_B || !d_U) { g_last_error = "ra_sdr_project: null argument"; return RA_ERR_ARG; }
     const size_t lds = (size_t)16 * ((q0 + 15) / 16) * (16 * ((p + 15) / 16) + 4) * sizeof(float);
-    hipError_t he = hipFuncSetAttribute((const void *)sdr_project_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(sdr_project_kernel, dim3(n), dim3(SDR_THREADS), lds, stream, d_images, d_mean, p, q, d_A, p0, d_B, q0, d_U);
-        he = hipGetLastError();
-    }
+    if (const int rc = RA_LDS(nullptr, sdr_project_kernel, lds)) return rc;
+    hipLaunchKernelGGL(sdr_project_kernel, dim3(n), dim3(SDR_THREADS), lds, stream, d_images, d_mean, p, q, d_A, p0, d_B, q0, d_U);
+    const hipError_t he = hipGetLastError();
     return he == hipSuccess ? RA_OK : sdr_launch_error("ra_sdr_project", he);
 }
 
@@ -2951,10 +3031,9 @@ extern "C" int ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result 
         hipLaunchKernelGGL(transform_generic_kernel, dim3(n, std::max(8, std::min((npix + 255) / 256, (2048 + n - 1) / n))), dim3(256), 0, stream,
                            nx, d_in, n, 0, d_params, d_out, (float *)nullptr, (int *)nullptr);
     } else {
-        he = hipFuncSetAttribute((const void *)transform_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (he == hipSuccess)
-            hipLaunchKernelGGL(transform_kernel, dim3(n), dim3(RA_XF_THREADS), lds, stream, nx, d_in, n, 0, d_params, d_out,
-                               (float *)nullptr, (int *)nullptr);
+        if (const int rc = RA_LDS(nullptr, transform_kernel, lds)) return rc;
+        hipLaunchKernelGGL(transform_kernel, dim3(n), dim3(RA_XF_THREADS), lds, stream, nx, d_in, n, 0, d_params, d_out,
+                           (float *)nullptr, (int *)nullptr);
     }
     if (he == hipSuccess) he = hipGetLastError();
     return he == hipSuccess ? RA_OK : sdr_launch_error("ra_rot_shift2d", he);
@@ -2976,10 +3055,9 @@ extern "C" int ra_tsne_knn(const float *d_x, int n, int d, int k, int *d_idx, do
     a.cap = a.C + TSNE_KNN_SLACK;
     a.idx = d_idx; a.dist2 = d_dist2;
     const size_t lds = (size_t)16 * a.C * sizeof(double) + (size_t)16 * TSNE_KNN_TILE * sizeof(float) + (size_t)16 * a.cap * 8;
-    hipError_t he = hipFuncSetAttribute((const void *)tsne_knn_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (he != hipSuccess) return sdr_launch_error("ra_tsne_knn", he);
+    if (const int rc = RA_LDS(nullptr, tsne_knn_kernel, lds)) return rc;
     float *d_nrm = nullptr;
-    he = hipMallocAsync((void **)&d_nrm, (size_t)n * sizeof(float), stream);
+    hipError_t he = hipMallocAsync((void **)&d_nrm, (size_t)n * sizeof(float), stream);
     if (he != hipSuccess) return sdr_launch_error("ra_tsne_knn", he);
     a.nrm = d_nrm;
     hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, d_nrm);
@@ -3471,7 +3549,7 @@ extern "C" int ra_wiener_accumulate(const float *d_images, int n, int nx, const 
     bool fixed = false;
     const void *fk = wn_forward_fn(nx, pad, pl, &fixed);
     const int fgrid = pl.gblk ? pf_gblk_grid(pl, C) : 0;
-    he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
+    if (const int rcl = raise_dynamic_lds(nullptr, fk, "wn_forward_kernel", (size_t)pl.lds)) { release(); return rcl; }
     if (he == hipSuccess) he = hipMallocAsync((void **)&d_al, (size_t)C * npix * sizeof(float), stream);
     if (he == hipSuccess) he = hipMallocAsync((void **)&d_spec, (size_t)C * ph * sizeof(float2), stream);
     if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)fgrid * nx * H * sizeof(float2), stream);
@@ -3518,10 +3596,10 @@ extern "C" int ra_wiener_accumulate(const float *d_images, int n, int nx, const 
 // a finalize kernel's launch: one workgroup per class, or, when the plan keeps its block in global scratch, a grid of scratch
 // blocks that loops over the classes; args(pl_arg, d_gscr) gives the kernel's argument pointers
 template <class Args>
-static hipError_t wn_finalize_launch(const PfPlan &pl, const void *fk, int k, hipStream_t stream, Args args)
+static int wn_finalize_launch(const char *what, const PfPlan &pl, const void *fk, int k, hipStream_t stream, Args args)
 {
-    hipError_t he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-    if (he != hipSuccess) return he;
+    if (const int rc = raise_dynamic_lds(nullptr, fk, what, (size_t)pl.lds)) return rc;
+    hipError_t he = hipSuccess;
     const int grid = pl.gblk ? pf_gblk_grid(pl, k) : k;
     float2 *d_gscr = nullptr;
     if (pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)grid * pl.nx * pl.H * sizeof(float2), stream);
@@ -3532,7 +3610,7 @@ static hipError_t wn_finalize_launch(const PfPlan &pl, const void *fk, int k, hi
         if (he == hipSuccess) he = hipGetLastError();
     }
     if (d_gscr) (void)hipFreeAsync(d_gscr, stream);
-    return he;
+    return he == hipSuccess ? RA_OK : sdr_launch_error(what, he);
 }
 
 extern "C" int ra_wiener_finalize(const float *d_num, const float *d_den, const int *d_counts, int k, int nx, int pad, float snr,
@@ -3549,10 +3627,9 @@ extern "C" int ra_wiener_finalize(const float *d_num, const float *d_den, const 
     const void *fk = pl.gblk ? (const void *)wn_finalize_kernel<true> : (const void *)wn_finalize_kernel<false>;
     const float2 *num = (const float2 *)d_num;
     float inv_snr = 1.0f / snr;
-    const hipError_t he = wn_finalize_launch(pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
+    return wn_finalize_launch("ra_wiener_finalize", pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
         return {&num, &d_den, &d_counts, &k, &inv_snr, &min_count, &d_out, &pl_arg, &d_gscr};
     });
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_finalize", he);
 }
 
 // ---- half-set FRC and SSNR-weighted averages (ralign_wiener.h)
@@ -3604,10 +3681,9 @@ extern "C" int ra_wiener_finalize_ssnr(const float *d_num2, const float *d_den2,
     if (pl.nb < 1) { g_last_error = "ra_wiener_finalize_ssnr: no plan for this box"; return RA_ERR_ARG; }
     const void *fk = pl.gblk ? (const void *)wn_finalize_ssnr_kernel<true> : (const void *)wn_finalize_ssnr_kernel<false>;
     const float2 *num2 = (const float2 *)d_num2;
-    const hipError_t he = wn_finalize_launch(pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
+    return wn_finalize_launch("ra_wiener_finalize_ssnr", pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
         return {&num2, &d_den2, &d_counts2, &d_reg, &k, &min_count, &d_out, &pl_arg, &d_gscr};
     });
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_finalize_ssnr", he);
 }
 
 // ---- per-particle agreement scores (ralign_wiener.h)
@@ -3664,8 +3740,8 @@ extern "C" int ra_wiener_score(const float *d_images, int n, int nx, const ra_re
     bool fixed = false;
     const void *fk = wn_forward_fn(nx, pad, pl, &fixed);
     const int fgrid = pl.gblk ? pf_gblk_grid(pl, C) : 0;
-    hipError_t he = hipFuncSetAttribute(fk, hipFuncAttributeMaxDynamicSharedMemorySize, pl.lds);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_al, (size_t)C * npix * sizeof(float), stream);
+    if (const int rcl = raise_dynamic_lds(nullptr, fk, "wn_forward_kernel", (size_t)pl.lds)) { prep.release(stream); return rcl; }
+    hipError_t he = hipMallocAsync((void **)&d_al, (size_t)C * npix * sizeof(float), stream);
     if (he == hipSuccess) he = hipMallocAsync((void **)&d_spec, (size_t)C * ph * sizeof(float2), stream);
     if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)fgrid * nx * H * sizeof(float2), stream);
     if (he == hipSuccess) he = hipMallocAsync((void **)&d_perm, (size_t)n * sizeof(int), stream);

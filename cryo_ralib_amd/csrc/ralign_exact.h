@@ -42,6 +42,10 @@ namespace ralign {
 #define RA_EXACT_THREADS 256
 #define RA_TIE_EXP 64            // entries of the replayed scan: candidates x copies of their references (more: the first 64)
 #define RA_EXACT_TABLE_BYTES(maxrin) ((size_t)24 * (maxrin))      // refine_winner_kernel: [maxrin] double2 twiddles + [maxrin] double samples
+// static LDS of refine_winner_kernel -- red, redi, cand_inf, cand_b, cand_win, ex_key, ex_ci, ex_mir, ex_ref, ex_bs: 1276 bytes --
+// rounded up to 64: the room the host rules leave beside the kernel's dynamic LDS (1280 bytes, the code object's figure).
+// plan_workspace has no device to ask; setup_refine holds the loaded code object's figure against this one.
+#define RA_EXACT_STATIC_LDS ((size_t)((4 * 8 + 4 * 4 + (RA_TIE_ALTS + 1) * (4 * 4 + 7 * 8) + 4 + RA_TIE_EXP * (8 + 1 + 1) + 2 * 4 + 63) & ~63))
 template <bool GM = false> __device__ __forceinline__ void exact_lds_sync()
 {
     if constexpr (GM) __threadfence_block();

@@ -218,6 +218,17 @@ int  ra_align(ra_engine *e, const float *d_particles, int n, float *d_state,
 int  ra_set_refine(ra_engine *e, float threshold);
 /* particles the last search launch re-evaluated (flat peaks and float ties); synchronises the stream (diagnostics) */
 int  ra_last_refine_count(ra_engine *e);
+/* LDS ledger (diagnostics, tests): one row for every kernel whose dynamic LDS the engine has raised so far -- search kernels
+ * included -- with the static LDS of the loaded code object, the dynamic LDS asked for and the device's limit per workgroup.
+ * Every such request is checked (static + dynamic <= limit) before anything is launched; one that does not fit fails with the
+ * kernel's name and the two numbers in ra_last_error().  Fills up to `cap` rows and returns the number of rows the engine has.
+ * The sub-bin refinement appears as refine_winner_kernel<false> (ring buffers in LDS) or refine_winner_kernel<true> (in
+ * global scratch: large ring sets, or RALIGN_REFINE_GM=1).  Read-only. */
+typedef struct ra_lds_row {
+    char kernel[64];
+    int  static_bytes, dynamic_bytes, limit_bytes;
+} ra_lds_row;
+int  ra_lds_report(const ra_engine *e, ra_lds_row *rows, int cap);
 /* the reference's state round trip: rebuild the shift the next search starts from (d_state [n][2]) from the float32
  * parameters of the previous iteration in d_result -- inverse_transform2(alpha, sx, sy) in RA_MODE_MREF
  * (test_mref_gpu_align.py:1024-1026), combine_params2(alpha, sx, sy, mirror, 0, -cs[0], -cs[1], 0) then

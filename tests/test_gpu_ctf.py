@@ -56,9 +56,16 @@ def test_multiplier_matches_the_reference_ctf_sign(k):
 WORST = {}
 
 
-@pytest.mark.parametrize("nx", [32, 64, 90, 100, 128, 130, 256, 45])
-@pytest.mark.parametrize("pad", [True, False])
-@pytest.mark.parametrize("n", [1, 5])
+# boxes next to a switch of the transform plan (pf_make_plan), with the padding for which the box is the edge.  2x: 90 | 91 two
+# workgroups per CU -> one; 113 | 114 block in LDS (P = 226: a radix-113 stage) -> block in global scratch; 97: P = 2 x 97;
+# 598 | 599 the global-scratch batch drops below its usual size; 1024 the largest box.  1x: 127 one radix-127 stage; 131 | 132 two
+# workgroups per CU -> one; 171 | 172 block in LDS -> global scratch
+PLAN_EDGES = [(n, True, nx) for n in (1, 5) for nx in (91, 113, 114, 97)] + \
+             [(n, False, nx) for n in (1, 5) for nx in (127, 131, 132, 171, 172)] + [(2, True, 599), (2, True, 1024)]
+
+
+@pytest.mark.parametrize("n,pad,nx", [(n, pad, nx) for n in (1, 5) for pad in (True, False) for nx in (32, 64, 90, 100, 128, 130, 256, 45)] +
+                         PLAN_EDGES)
 def test_flip_matches_the_float64_statement(nx, pad, n):
     rng = np.random.default_rng(nx * 10 + n)
     x = rng.standard_normal((n, nx, nx)).astype(np.float32)

@@ -34,7 +34,8 @@ def _device(x, prm, lab, k, tab, snr, pad, flipped, min_count, chunks=None):
     return out.cpu().numpy(), counts.cpu().numpy(), num
 
 
-@pytest.mark.parametrize("nx,pad,n", [(90, True, 60), (64, False, 60), (75, True, 40), (130, True, 24), (256, True, 10)])
+@pytest.mark.parametrize("nx,pad,n", [(90, True, 60), (64, False, 60), (75, True, 40), (130, True, 24), (256, True, 10),
+                                     (91, True, 24), (113, True, 16), (114, True, 16), (171, False, 12), (172, False, 12)])
 def test_device_matches_the_contract(nx, pad, n):
     k = 5
     x, prm, lab, tab = _case(n, nx, k, nx + pad)

@@ -39,7 +39,8 @@ def _host(t):
     return t.cpu().numpy()
 
 
-@pytest.mark.parametrize("nx,pad,n", [(90, True, 60), (64, False, 60), (75, True, 40), (130, True, 24), (256, True, 10)])
+@pytest.mark.parametrize("nx,pad,n", [(90, True, 60), (64, False, 60), (75, True, 40), (130, True, 24), (256, True, 10),
+                                     (91, True, 24), (113, True, 16), (114, True, 16), (171, False, 12), (172, False, 12)])
 def test_device_matches_the_contract(nx, pad, n):
     """classes: k - 3 populated ones, one of a single member, one empty, one of two members (under min_count = 3).  The bar is
     1e-4 on cc and 1e-4 of sqrt(E F) on each sum; the measured maxima are printed"""
@@ -61,9 +62,12 @@ def test_device_matches_the_contract(nx, pad, n):
         assert unscored[np.isin(lab, [k - 2, k - 1])].all() and (~unscored).sum() >= 3
         assert np.isnan(got["cc"][unscored]).all() and np.isnan(want["cc"][unscored]).all()
         assert np.isfinite(got["cc"][~unscored]).all()
-        if loo:                                               # the class of one has nobody to be compared with
-            assert got["sums"][2, 0] == 0 and got["sums"][2, 2] == 0 and got["sums"][2, 1] > 0
-        live = lab != k - 1 if loo else np.ones(n, bool)
+        alone = np.bincount(lab, minlength=k)[lab] == 1       # particle 2 (class k - 1), and whoever the draw of a small n left alone
+        assert alone[2]
+        if loo:                                               # a class of one has nobody to be compared with
+            assert (got["sums"][alone, 0] == 0).all() and (got["sums"][alone, 2] == 0).all() and (got["sums"][alone, 1] > 0).all()
+            assert (want["sums"][alone, 1] * want["sums"][alone, 2] == 0).all()
+        live = ~alone if loo else np.ones(n, bool)
         norm = np.sqrt(want["sums"][live, 1] * want["sums"][live, 2])
         assert (norm > 0).all()
         e_sum = (np.abs(got["sums"][live] - want["sums"][live]).max(1) / norm).max()

@@ -34,7 +34,8 @@ def _host(num2, den2, counts2):
     return n[..., 0] + 1j * n[..., 1], den2.double().cpu().numpy(), counts2.cpu().numpy()
 
 
-GEOMETRIES = [(90, True, 60), (64, False, 60), (75, True, 40), (130, True, 24), (256, True, 10)]
+GEOMETRIES = [(90, True, 60), (64, False, 60), (75, True, 40), (130, True, 24), (256, True, 10),
+              (91, True, 24), (113, True, 16), (114, True, 16), (171, False, 12), (172, False, 12)]
 
 
 @pytest.mark.parametrize("nx,pad,n", GEOMETRIES)
