@@ -1,0 +1,275 @@
+// t-SNE and k-means of 2SDR factors (ralign_tsne.h, ralign_kmeans.h): the engine-less ra_tsne_* and ra_kmeans_* entry points of
+// libralign_hip.so, each on the caller's stream.
+#include "ralign_host.h"
+#include "ralign_kmeans.h"
+
+using namespace ralign;
+
+// ---- t-SNE (ralign_tsne.h)
+
+extern "C" int ra_tsne_knn(const float *d_x, int n, int d, int k, int *d_idx, double *d_dist2, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 2 || n > TSNE_MAX_N || d < 1 || d > TSNE_MAX_D || k < 1 || k > std::min(n - 1, TSNE_MAX_K))
+        return arg_error("ra_tsne_knn: need 2 <= n <= 262144, 1 <= d <= 2048 and 1 <= k <= min(n - 1, 301)");
+    if (!d_x || !d_idx || !d_dist2) return arg_error("ra_tsne_knn: null argument");
+    TsneKnnArgs a;
+    a.x = d_x; a.n = n; a.d = d; a.k = k;
+    a.C = std::min(n - 1, k + TSNE_KNN_MARGIN);
+    a.cap = a.C + TSNE_KNN_SLACK;
+    a.idx = d_idx; a.dist2 = d_dist2;
+    const size_t lds = (size_t)16 * a.C * sizeof(double) + (size_t)16 * TSNE_KNN_TILE * sizeof(float) + (size_t)16 * a.cap * 8;
+    if (const int rc = RA_LDS(nullptr, tsne_knn_kernel, lds)) return rc;
+    StreamScratch scratch(stream);
+    float *d_nrm = scratch.get<float>(n);
+    if (!d_nrm) return hip_error("ra_tsne_knn", scratch.status());
+    a.nrm = d_nrm;
+    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, d_nrm);
+    hipError_t he = hipGetLastError();
+    RA_LAUNCH(he, tsne_knn_kernel, dim3((n + 15) / 16), dim3(TSNE_KNN_THREADS), lds, stream, a);
+    return he == hipSuccess ? RA_OK : hip_error("ra_tsne_knn", he);
+}
+
+extern "C" int ra_tsne_affinity(const double *d_dist2, int n, int k, float perplexity, double *d_pcond, void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 2 || n > TSNE_MAX_N || k < 1 || k > std::min(n - 1, TSNE_MAX_K) || !(perplexity > 0.f && perplexity <= 100.f))
+        return arg_error("ra_tsne_affinity: need 2 <= n <= 262144, 1 <= k <= min(n - 1, 301) and 0 < perplexity <= 100");
+    if (!d_dist2 || !d_pcond) return arg_error("ra_tsne_affinity: null argument");
+    hipLaunchKernelGGL(tsne_affinity_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, d_dist2, n, k, log((double)perplexity), d_pcond);
+    hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_tsne_affinity", he);
+}
+
+// repulsion partials, then the update kernel in the given mode, then (if d_stats) the statistics
+static int tsne_run(const char *what, const float *d_y, float *d_y_out, float *d_update, float *d_gains, float *d_grad, int n,
+                    const int *d_indptr, const int *d_indices, const float *d_p, int nnz, float exaggeration, float momentum,
+                    float learning_rate, int mode, double *d_stats, hipStream_t stream)
+{
+    const int seg = tsne_segment(n), nseg = (n + seg - 1) / seg, nrb = (n + TSNE_REP_ROWS - 1) / TSNE_REP_ROWS;
+    const int nub = (n + TSNE_UPD_THREADS - 1) / TSNE_UPD_THREADS, nz = nseg * nrb;
+    const size_t part_bytes = (size_t)nseg * n * sizeof(float2), z_bytes = (size_t)nz * sizeof(double);
+    const size_t st_bytes = d_stats ? (size_t)nub * 2 * sizeof(double) : 0;
+    StreamScratch owner(stream);
+    unsigned char *scratch = owner.get<unsigned char>(part_bytes + z_bytes + st_bytes);
+    if (!scratch) return hip_error(what, owner.status());
+    float2 *part = (float2 *)scratch;
+    double *zpart = (double *)(scratch + part_bytes), *st = d_stats ? (double *)(scratch + part_bytes + z_bytes) : nullptr;
+    hipLaunchKernelGGL(tsne_repulsion_kernel, dim3(nrb, nseg), dim3(TSNE_REP_THREADS), 0, stream, (const float2 *)d_y, n, seg, part, zpart);
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) {
+        TsneUpdateArgs u;
+        u.y = (const float2 *)d_y; u.y_out = (float2 *)d_y_out; u.update = (float2 *)d_update; u.gains = (float2 *)d_gains;
+        u.grad = (float2 *)d_grad; u.part = part; u.zpart = zpart; u.indptr = d_indptr; u.indices = d_indices; u.p = d_p;
+        u.n = n; u.nseg = nseg; u.nz = nz; u.nnz = nnz; u.mode = mode;
+        u.exaggeration = exaggeration; u.momentum = momentum; u.learning_rate = learning_rate; u.stats_part = st;
+        hipLaunchKernelGGL(tsne_update_kernel, dim3(nub), dim3(TSNE_UPD_THREADS), 0, stream, u);
+        he = hipGetLastError();
+    }
+    if (d_stats) RA_LAUNCH(he, tsne_stats_kernel, dim3(1), dim3(256), 0, stream, st, nub, d_stats);
+    return he == hipSuccess ? RA_OK : hip_error(what, he);
+}
+
+static bool tsne_csr_ok(const char *what, int n, int nnz, const int *d_indptr, const int *d_indices, const float *d_p)
+{
+    if (n < 2 || n > TSNE_MAX_N || nnz < 0 || (long long)nnz > 2LL * n * TSNE_MAX_K) {
+        set_error(std::string(what) + ": need 2 <= n <= 262144 and 0 <= nnz <= 2 n 301");
+        return false;
+    }
+    if (!d_indptr || (nnz > 0 && (!d_indices || !d_p))) { set_error(std::string(what) + ": null argument"); return false; }
+    return true;
+}
+
+extern "C" int ra_tsne_step(const float *d_y, float *d_y_out, float *d_update, float *d_gains, int n, const int *d_indptr,
+                            const int *d_indices, const float *d_p, int nnz, float exaggeration, float momentum, float learning_rate,
+                            double *d_stats, void *hip_stream)
+{
+    if (!tsne_csr_ok("ra_tsne_step", n, nnz, d_indptr, d_indices, d_p)) return RA_ERR_ARG;
+    if (!d_y || !d_y_out || !d_update || !d_gains || d_y_out == d_y)
+        return arg_error("ra_tsne_step: null argument, or d_y_out == d_y (the step reads every y_j while it writes)");
+    if (!std::isfinite(exaggeration) || !std::isfinite(momentum) || !std::isfinite(learning_rate) || !(learning_rate > 0.f))
+        return arg_error("ra_tsne_step: need finite exaggeration and momentum and a finite learning rate > 0");
+    return tsne_run("ra_tsne_step", d_y, d_y_out, d_update, d_gains, nullptr, n, d_indptr, d_indices, d_p, nnz, exaggeration, momentum,
+                    learning_rate, 0, d_stats, (hipStream_t)hip_stream);
+}
+
+extern "C" int ra_tsne_error(const float *d_y, int n, const int *d_indptr, const int *d_indices, const float *d_p, int nnz,
+                             float exaggeration, float *d_grad, double *d_stats, void *hip_stream)
+{
+    if (!tsne_csr_ok("ra_tsne_error", n, nnz, d_indptr, d_indices, d_p)) return RA_ERR_ARG;
+    if (!d_y || (!d_grad && !d_stats) || !std::isfinite(exaggeration))
+        return arg_error("ra_tsne_error: null embedding, neither gradient nor statistics asked for, or a non-finite exaggeration");
+    return tsne_run("ra_tsne_error", d_y, nullptr, nullptr, nullptr, d_grad, n, d_indptr, d_indices, d_p, nnz, exaggeration, 0.f, 0.f, 1,
+                    d_stats, (hipStream_t)hip_stream);
+}
+
+// ---- k-means (ralign_kmeans.h)
+
+static bool km_shape_ok(const char *what, int n, int d, int k)
+{
+    if (n < 1 || n > KM_MAX_N || d < 1 || d > KM_MAX_D || k < 1 || k > std::min(n, KM_MAX_K)) {
+        set_error(std::string(what) + ": need 1 <= n <= 4194304, 1 <= d <= 2048 and 1 <= k <= min(n, 256)");
+        return false;
+    }
+    return true;
+}
+
+// carves aligned pieces out of one stream-ordered allocation
+struct KmScratch {
+    size_t off = 0;
+    unsigned char *base = nullptr;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+    template <class T> T *at(size_t o) { return (T *)(base + o); }
+};
+
+extern "C" int ra_kmeans_sqnorm(const float *d_x, int n, int d, float *d_nrm, void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_sqnorm", n, d, 1)) return RA_ERR_ARG;
+    if (!d_x || !d_nrm) return arg_error("ra_kmeans_sqnorm: null argument");
+    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, d_x, n, d, d_nrm);
+    hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_sqnorm", he);
+}
+
+// the E-step: labels (in place, changed counted into d_changed if non-null) and the double distance of each point to its centre.
+// cf [k][d] / cnrm [k]: scratch of the f32 copy (d > KM_SMALL_D only)
+static hipError_t km_assign(const float *x, int n, int d, const float *nrm, const double *c, int k, int *labels, double *dist,
+                            int *changed, float *cf, float *cnrm, hipStream_t stream)
+{
+    if (d <= KM_SMALL_D) {
+        hipLaunchKernelGGL(km_assign_small_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, n, d, c, k, labels, dist, changed);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(km_prep_kernel, dim3(k), dim3(256), 0, stream, c, d, cf, cnrm);
+    hipError_t he = hipGetLastError();
+    if (he != hipSuccess) return he;
+    KmAssignArgs a;
+    a.x = x; a.nrm = nrm; a.c = c; a.cf = cf; a.cnrm = cnrm; a.n = n; a.d = d; a.k = k;
+    a.labels = labels; a.dist = dist; a.changed = changed;
+    const dim3 grid((n + KM_ROWS - 1) / KM_ROWS), block(64 * KM_WAVES);
+    const int nt = (k + 15) / 16;
+    if (nt <= 1) hipLaunchKernelGGL(km_assign_mfma_kernel<1>, grid, block, 0, stream, a);
+    else if (nt <= 2) hipLaunchKernelGGL(km_assign_mfma_kernel<2>, grid, block, 0, stream, a);
+    else if (nt <= 4) hipLaunchKernelGGL(km_assign_mfma_kernel<4>, grid, block, 0, stream, a);
+    else if (nt <= 8) hipLaunchKernelGGL(km_assign_mfma_kernel<8>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(km_assign_mfma_kernel<16>, grid, block, 0, stream, a);
+    return hipGetLastError();
+}
+
+extern "C" int ra_kmeans_labels(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, int *d_labels,
+                                int assign, double *d_inertia, void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_labels", n, d, k)) return RA_ERR_ARG;
+    if (!d_x || !d_centers || !d_labels || (!assign && !d_inertia))
+        return arg_error("ra_kmeans_labels: null argument, or neither assignment nor inertia asked for");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + 255) / 256;
+    KmScratch S;
+    const size_t o_dist = S.take((size_t)n * 8), o_part = S.take((size_t)nb * 8);
+    const bool big = d > KM_SMALL_D;
+    const size_t o_cf = S.take(big ? (size_t)k * d * 4 : 0), o_cn = S.take(big ? (size_t)k * 4 : 0);
+    const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
+    StreamScratch scratch(stream);
+    if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_labels", scratch.status());
+    hipError_t he = hipSuccess;
+    double *dist = S.at<double>(o_dist);
+    const float *nrm = d_nrm;
+    if (big && !d_nrm) {
+        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
+        he = hipGetLastError();
+        nrm = S.at<float>(o_nrm);
+    }
+    if (he == hipSuccess) {
+        if (assign) {
+            he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, nullptr, S.at<float>(o_cf), S.at<float>(o_cn), stream);
+        } else {
+            hipLaunchKernelGGL(km_point_dist_kernel, dim3(big ? (n + 3) / 4 : nb), dim3(256), 0, stream, d_x, n, d, d_centers, k, d_labels, dist);
+            he = hipGetLastError();
+        }
+    }
+    if (he == hipSuccess && d_inertia) {
+        hipLaunchKernelGGL(km_block_sum_kernel, dim3(nb), dim3(256), 0, stream, dist, n, S.at<double>(o_part));
+        he = hipGetLastError();
+        RA_LAUNCH(he, km_final_sum_kernel, dim3(1), dim3(256), 0, stream, S.at<double>(o_part), nb, d_inertia);
+    }
+    return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_labels", he);
+}
+
+extern "C" int ra_kmeans_lloyd(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, double *d_centers_new,
+                               int *d_labels, double *d_stats, void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_lloyd", n, d, k)) return RA_ERR_ARG;
+    if (!d_x || !d_centers || !d_centers_new || !d_labels || !d_stats || d_centers_new == d_centers)
+        return arg_error("ra_kmeans_lloyd: null argument, or d_centers_new == d_centers");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, L = km_run_len(n), rmax = (n + L - 1) / L + k;
+    const bool big = d > KM_SMALL_D;
+    KmScratch S;
+    const size_t o_dist = S.take((size_t)n * 8), o_ints = S.take(2 * 4), o_bcnt = S.take((size_t)nb * k * 4);
+    const size_t o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4), o_run0 = S.take((size_t)(k + 1) * 4);
+    const size_t o_mem = S.take((size_t)n * 4), o_part = S.take((size_t)rmax * d * 8), o_sums = S.take((size_t)k * d * 8);
+    const size_t o_wt = S.take((size_t)k * 8), o_shift = S.take((size_t)k * 8);
+    const size_t o_cf = S.take(big ? (size_t)k * d * 4 : 0), o_cn = S.take(big ? (size_t)k * 4 : 0);
+    const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
+    StreamScratch scratch(stream);
+    if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_lloyd", scratch.status());
+    int *ints = S.at<int>(o_ints), *bcnt = S.at<int>(o_bcnt), *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start);
+    int *run0 = S.at<int>(o_run0), *mem = S.at<int>(o_mem);
+    double *dist = S.at<double>(o_dist), *part = S.at<double>(o_part), *sums = S.at<double>(o_sums), *wt = S.at<double>(o_wt);
+    double *shift = S.at<double>(o_shift);
+    const float *nrm = d_nrm;
+    hipError_t he = hipMemsetAsync(ints, 0, 2 * sizeof(int), stream);
+    if (he == hipSuccess && big && !d_nrm) {
+        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
+        he = hipGetLastError();
+        nrm = S.at<float>(o_nrm);
+    }
+    if (he == hipSuccess) he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, ints, S.at<float>(o_cf), S.at<float>(o_cn), stream);
+    RA_LAUNCH(he, km_hist_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, bcnt);
+    RA_LAUNCH(he, km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt);
+    RA_LAUNCH(he, km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, run0);
+    RA_LAUNCH(he, km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, (const int *)bcnt, (const int *)start, mem);
+    RA_LAUNCH(he, km_runsum_kernel, dim3(rmax), dim3(256), 0, stream, d_x, n, d, k, L, (const int *)mem, (const int *)cnt, (const int *)start,
+                  (const int *)run0, part);
+    RA_LAUNCH(he, km_combine_kernel, dim3(k), dim3(256), 0, stream, (const double *)part, d, (const int *)cnt, (const int *)run0, sums, wt);
+    RA_LAUNCH(he, km_relocate_kernel, dim3(1), dim3(1024), 0, stream, d_x, n, d, k, (const int *)d_labels, (const double *)dist, (const int *)cnt,
+                  sums, wt, ints + 1);
+    RA_LAUNCH(he, km_update_kernel, dim3(k), dim3(256), 0, stream, (const double *)sums, (const double *)wt, d_centers, d, k, d_centers_new, shift);
+    RA_LAUNCH(he, km_stats_kernel, dim3(1), dim3(256), 0, stream, (const double *)shift, k, (const int *)ints, d_stats);
+    return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_lloyd", he);
+}
+
+extern "C" int ra_kmeans_search(const double *d_w, int n, const double *d_vals, int m, int *d_idx, void *hip_stream)
+{
+    if (n < 1 || n > KM_MAX_N || m < 1 || m > KM_MAX_M) return arg_error("ra_kmeans_search: need 1 <= n <= 4194304 and 1 <= m <= 16");
+    if (!d_w || !d_vals || !d_idx) return arg_error("ra_kmeans_search: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nseg = (n + KM_SEG - 1) / KM_SEG;
+    StreamScratch scratch(stream);
+    double *buf = scratch.get<double>((size_t)3 * nseg);
+    if (!buf) return hip_error("ra_kmeans_search", scratch.status());
+    double *segsum = buf, *base = buf + nseg, *end = buf + 2 * nseg;
+    hipLaunchKernelGGL(km_segsum_kernel, dim3((nseg + 255) / 256), dim3(256), 0, stream, d_w, n, segsum);
+    hipError_t he = hipGetLastError();
+    RA_LAUNCH(he, km_segscan_kernel, dim3(1), dim3(256), 0, stream, (const double *)segsum, nseg, base, end);
+    RA_LAUNCH(he, km_search_kernel, dim3(m), dim3(256), 0, stream, d_w, n, (const double *)base, (const double *)end, nseg, d_vals, d_idx);
+    return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_search", he);
+}
+
+extern "C" int ra_kmeans_seed(const float *d_x, int n, int d, const int *d_cand, int m, double *d_closest, int first, double *d_out,
+                              void *hip_stream)
+{
+    if (!km_shape_ok("ra_kmeans_seed", n, d, 1)) return RA_ERR_ARG;
+    if (m < 1 || m > KM_MAX_M || (first && m != 1)) return arg_error("ra_kmeans_seed: need 1 <= m <= 16 candidates (first centre: m = 1)");
+    if (!d_x || !d_cand || !d_closest || !d_out) return arg_error("ra_kmeans_seed: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + 255) / 256;
+    StreamScratch scratch(stream);
+    double *part = scratch.get<double>((size_t)m * nb);
+    if (!part) return hip_error("ra_kmeans_seed", scratch.status());
+    hipLaunchKernelGGL(km_cand_dist_kernel, dim3(nb, m), dim3(256), 0, stream, d_x, n, d, d_cand, first ? (const double *)nullptr : d_closest, part);
+    hipError_t he = hipGetLastError();
+    RA_LAUNCH(he, km_pick_kernel, dim3(1), dim3(256), 0, stream, (const double *)part, nb, d_cand, m, n, d_out);
+    RA_LAUNCH(he, km_commit_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, (const double *)d_out, first, d_closest);
+    return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_seed", he);
+}

@@ -1,7 +1,8 @@
 // libralign_hip.so -- host side of the MI355X 2-D alignment engine and its C ABI
 // (include/ralign.h).  Owns geometry tables, workspaces and the kernel schedule; exposes
-// the handle-based ra_* API (device pointers in, asynchronous on one HIP stream) and the
-// reference's ctypes surface (cuda/gpu_aln_noref.h:52-113) on top of it.
+// the handle-based ra_* API (device pointers in, asynchronous on one HIP stream).  The
+// reference's ctypes surface (ralign_legacy.hip) and the engine-less entry points
+// (ralign_ctf.hip, ralign_sdr.hip, ralign_embed.hip, ralign_resize.hip) are files of their own.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,16 +24,12 @@
 #include "ralign_pair.h"
 #include "ralign_exact.h"
 #include "ralign_refine.h"
-#include "ralign_ctf.h"
-#include "ralign_sdr.h"
-#include "ralign_tsne.h"
-#include "ralign_kmeans.h"
-#include "ralign_resize.h"
-#include "ralign_wiener.h"
+#include "ralign_host.h"
 
 using namespace ralign;
 
 static thread_local std::string g_last_error;
+void set_error(const std::string &msg) { g_last_error = msg; }
 
 // The size-generic kernels for a geometry the LDS-resident ones cover: RALIGN_GENERIC=1 (A/B runs, tests), or an engine whose
 // options only they implement (ra_create_ex: RA_INTERP_QUADRI).  The option is engine state; the flag below carries it into the
@@ -47,18 +44,6 @@ struct ForceGenericScope {
     explicit ForceGenericScope(bool on) : prev(g_force_generic) { g_force_generic = g_force_generic || on; }
     ~ForceGenericScope() { g_force_generic = prev; }
 };
-
-#define RA_HIP(call)                                                                          \
-    do {                                                                                      \
-        hipError_t err__ = (call);                                                            \
-        if (err__ != hipSuccess) {                                                            \
-            char buf__[512];                                                                  \
-            snprintf(buf__, sizeof(buf__), "%s failed: %s (%s:%d)", #call, hipGetErrorString(err__), \
-                     __FILE__, __LINE__);                                                     \
-            g_last_error = buf__;                                                             \
-            return RA_ERR_HIP;                                                                \
-        }                                                                                     \
-    } while (0)
 
 // device workspace of one engine, shared by ra_create and the size checks of the reference surface
 // (pre_align_size_check / ref_free_alignment_2D_size_check), so that the estimate cannot drift from what is allocated
@@ -168,11 +153,7 @@ struct ra_engine {
     size_t ev_used_ccf = 0, ev_used_polar = 0;
 };
 
-// Every site that raises a kernel's dynamic LDS goes through here.  The host rules that size the dynamic part know nothing of the
-// __shared__ arrays a kernel declares: the static size is read from the loaded code object and the sum compared with what a
-// workgroup of this device can have, BEFORE anything is launched -- a kernel that gains a static array then fails here, by name,
-// instead of in a launch.  Engines keep what was configured (ra_lds_report); e == nullptr: the engine-less entry points.
-static int raise_dynamic_lds(ra_engine *e, const void *fn, const char *name, size_t dyn)
+int raise_dynamic_lds(std::nullptr_t, const void *fn, const char *name, size_t dyn, int *stat_out, int *limit_out)
 {
     int dev = 0, limit = 0;
     hipFuncAttributes fa{};
@@ -191,14 +172,21 @@ static int raise_dynamic_lds(ra_engine *e, const void *fn, const char *name, siz
         g_last_error = std::string("hipFuncSetAttribute(") + name + "): " + hipGetErrorString(he);
         return RA_ERR_HIP;
     }
-    if (e) {
-        auto it = std::find_if(e->lds_rows.begin(), e->lds_rows.end(), [&](const LdsRow &r) { return r.kernel == name; });
-        if (it == e->lds_rows.end()) e->lds_rows.push_back(LdsRow{name, (int)stat, (int)dyn, limit});
-        else { it->stat = (int)stat; it->dyn = (int)dyn; it->limit = limit; }
-    }
+    if (stat_out) *stat_out = (int)stat;
+    if (limit_out) *limit_out = limit;
     return RA_OK;
 }
-#define RA_LDS(e, kernel, dyn) raise_dynamic_lds(e, (const void *)(kernel), #kernel, dyn)
+
+// the engine's form (ralign_host.h has the comment): the same check, then the row of the ledger (ra_lds_report)
+static int raise_dynamic_lds(ra_engine *e, const void *fn, const char *name, size_t dyn)
+{
+    int stat = 0, limit = 0;
+    if (const int rc = raise_dynamic_lds(nullptr, fn, name, dyn, &stat, &limit)) return rc;
+    auto it = std::find_if(e->lds_rows.begin(), e->lds_rows.end(), [&](const LdsRow &r) { return r.kernel == name; });
+    if (it == e->lds_rows.end()) e->lds_rows.push_back(LdsRow{name, stat, (int)dyn, limit});
+    else { it->stat = stat; it->dyn = (int)dyn; it->limit = limit; }
+    return RA_OK;
+}
 
 template <typename T> static int upload(ra_engine *e, const std::vector<T> &h, const T **dptr)
 {
@@ -2428,594 +2416,25 @@ extern "C" int ra_filter_references_dev(ra_engine *e, float *d_imgs, int nimg, c
     return RA_OK;
 }
 
-// ============================================================================================
-// reference-compatible surface (cuda/gpu_aln_noref.h:52-113): one process-global engine,
-// synchronous calls, print + abort on failure like the reference (gpu_aln_common.cu:89-103).
+// ---- what the reference-compatible surface (ralign_legacy.hip) needs of an engine without seeing the struct (ralign_host.h)
 
-namespace {
-struct Legacy {
-    ra_engine *eng = nullptr;
-    AlignConfig cfg{};
-    unsigned num_particles = 0;
-    int device = -1;
-    AlignParam *h_param = nullptr;       // pinned, caller reads / writes in place
-    float *d_sbj = nullptr, *d_ref = nullptr, *d_aligned = nullptr, *d_state = nullptr, *d_sums = nullptr;
-    int *d_counts = nullptr;
-    ra_result *d_res = nullptr, *h_res = nullptr;
-    float *h_stage = nullptr, *h_state = nullptr, *h_sums = nullptr;
-    int *h_counts = nullptr;
-    size_t stage_imgs = 0;
-    unsigned sbj_loaded = 0;
-    // class-resident (ISAC) mode: particles sorted by class, one reference per class
-    bool isac = false;
-    std::vector<unsigned> cid_idx;       // [ref_num + 1] first particle of every class
-    unsigned *d_cid_idx = nullptr;
-    int *d_cls = nullptr;                // [sbj_num] class of every particle (class-resident single launch)
-} L;
-
-void die(const char *what)
+void ra_engine_switch_mode(ra_engine *e, int mode)
 {
-    fprintf(stderr, "libralign_hip: %s: %s\n", what, ra_last_error());
-    exit(EXIT_FAILURE);
-}
-void hip_or_die(hipError_t e, const char *what)
-{
-    if (e != hipSuccess) { fprintf(stderr, "libralign_hip: %s: %s\n", what, hipGetErrorString(e)); exit(EXIT_FAILURE); }
+    e->cfg.mode = mode; e->dg.mode = mode; e->dg.norm_ring = mode == RA_MODE_MREF ? 1 : 0;
+    e->dg.win_ring = mode == RA_MODE_MREF ? e->geo.last_ring : e->geo.numr[3 * (e->geo.nring - 1)];      // (Normalize_ring follows the entry point: multiref_polar_ali_2d | ormq)
 }
 
-ra_config legacy_config(const AlignConfig *c, unsigned device, int mode)
+size_t ra_planned_workspace_bytes(const ra_config *rc)
 {
-    ra_config rc{};
-    rc.nx = (int)c->img_dim; rc.first_ring = 1; rc.last_ring = (int)c->ring_num; rc.ring_skip = 1;
-    rc.xrng = c->shift_rng_x; rc.yrng = c->shift_rng_y; rc.step = c->shift_step;
-    rc.nref = (int)c->ref_num; rc.mode = mode; rc.device = (int)device; rc.chunk = 0;
-    return rc;
-}
-
-size_t legacy_bytes(unsigned num_particles, const AlignConfig *c)
-{
-    // everything pre_align_init takes from the device: the engine's workspace (same plan as ra_create) plus the
-    // resident batch (particles, aligned images, state, results), the references and the class sums
     Geometry g;
-    if (c->img_dim < 8 || c->ref_num < 1 || !build_rings(g, (int)c->img_dim, 1, (int)c->ring_num, 1) ||
-        !build_shifts(g, c->shift_rng_x, c->shift_rng_y, c->shift_step))
+    if (!build_rings(g, rc->nx, rc->first_ring, rc->last_ring, rc->ring_skip) || !build_shifts(g, rc->xrng, rc->yrng, rc->step))
         return (size_t)-1;
-    ra_config rc = legacy_config(c, 0, RA_MODE_MREF);
-    rc.chunk = (int)std::min<unsigned>(8192, std::max(2u, c->sbj_num));
-    const bool generic = !fits_specialised_kernels(g, rc);
+    const bool generic = !fits_specialised_kernels(g, *rc);
     if (generic && g.maxrin <= 1024) align_ring_quads(g);      // as ra_create: the panel size follows the layout
-    const WorkspacePlan wp = plan_workspace(g, rc, generic);
-    const size_t npix = (size_t)c->img_dim * c->img_dim, B = c->sbj_num, R = c->ref_num;
-    const size_t batch = B * npix * 4 * 2 + B * (2 * sizeof(float) + sizeof(ra_result)) + R * npix * 4 * 3 + R * 4;
-    (void)num_particles;     // the AlignParam array lives in pinned host memory
-    return wp.bytes + batch + (size_t)8 * (2 << 20);
+    return plan_workspace(g, *rc, generic).bytes;
 }
 
-void run_search(int start, int stop, int mode)
-{
-    if (!L.eng) { fprintf(stderr, "libralign_hip: *_run before pre_align_init\n"); exit(EXIT_FAILURE); }
-    const int n = stop - start;
-    if (n <= 0 || (unsigned)n > L.cfg.sbj_num || (unsigned)stop > L.num_particles) {
-        fprintf(stderr, "libralign_hip: bad index range [%d,%d)\n", start, stop);
-        exit(EXIT_FAILURE);
-    }
-    L.eng->cfg.mode = mode; L.eng->dg.mode = mode; L.eng->dg.norm_ring = mode == RA_MODE_MREF ? 1 : 0;
-    L.eng->dg.win_ring = mode == RA_MODE_MREF ? L.eng->geo.last_ring : L.eng->geo.numr[3 * (L.eng->geo.nring - 1)];      // (Normalize_ring follows the entry point: multiref_polar_ali_2d | ormq)
-    for (int i = 0; i < n; i++) { L.h_state[2 * i] = L.h_param[start + i].shift_x; L.h_state[2 * i + 1] = L.h_param[start + i].shift_y; }
-    hip_or_die(hipMemcpy(L.d_state, L.h_state, sizeof(float) * 2 * n, hipMemcpyHostToDevice), "state upload");
-    if (ra_align(L.eng, L.d_sbj, n, L.d_state, L.d_res, nullptr)) die("ra_align");
-}
-
-void fetch_results(int start, int stop)
-{
-    const int n = stop - start;
-    if (ra_sync(L.eng)) die("sync");
-    hip_or_die(hipMemcpy(L.h_res, L.d_res, sizeof(ra_result) * n, hipMemcpyDeviceToHost), "result download");
-    hip_or_die(hipMemcpy(L.h_state, L.d_state, sizeof(float) * 2 * n, hipMemcpyDeviceToHost), "state download");
-    for (int i = 0; i < n; i++) {
-        AlignParam &a = L.h_param[start + i];
-        a.ref_id = L.h_res[i].ref_id;
-        a.shift_x = L.h_state[2 * i]; a.shift_y = L.h_state[2 * i + 1];
-        a.angle = L.h_res[i].alpha;
-        a.mirror = L.h_res[i].mirror != 0;
-    }
-}
-}  // namespace
-
-extern "C" void print_gpu_info(const unsigned int device_idx)
-{
-    hipDeviceProp_t p;
-    if (hipGetDeviceProperties(&p, (int)device_idx) != hipSuccess) { printf("GPU[%u]: not available\n", device_idx); return; }
-    size_t fr = 0, tot = 0;
-    (void)hipSetDevice((int)device_idx);
-    (void)hipMemGetInfo(&fr, &tot);
-    printf("GPU[%u]: %s (%s), %d CUs, %.1f GiB total, %.1f GiB free, LDS/CU %zu KB, wave %d\n", device_idx, p.name,
-           p.gcnArchName, p.multiProcessorCount, tot / 1073741824.0, fr / 1073741824.0,
-           (size_t)p.maxSharedMemoryPerMultiProcessor / 1024, p.warpSize);
-}
-
-extern "C" void gpu_clear(void)
-{
-    if (L.eng) { ra_destroy(L.eng); L.eng = nullptr; }
-    if (L.h_param) (void)hipHostFree(L.h_param);
-    if (L.h_stage) (void)hipHostFree(L.h_stage);
-    if (L.h_state) (void)hipHostFree(L.h_state);
-    if (L.h_sums) (void)hipHostFree(L.h_sums);
-    if (L.h_counts) (void)hipHostFree(L.h_counts);
-    if (L.h_res) (void)hipHostFree(L.h_res);
-    for (void *p : {(void *)L.d_sbj, (void *)L.d_ref, (void *)L.d_aligned, (void *)L.d_state, (void *)L.d_sums,
-                    (void *)L.d_counts, (void *)L.d_res, (void *)L.d_cid_idx, (void *)L.d_cls})
-        if (p) (void)hipFree(p);
-    int dev = L.device;
-    L = Legacy();
-    L.device = dev;   // the reference pins the process to one device id (gpu_aln_noref.cu:105)
-}
-
-extern "C" AlignParam *pre_align_init(const unsigned int num_particles, const AlignConfig *aln_cfg,
-                                      const unsigned int device_id)
-{
-    if (!aln_cfg) { fprintf(stderr, "libralign_hip: pre_align_init: null config\n"); exit(EXIT_FAILURE); }
-    if (L.device != -1 && L.device != (int)device_id) {
-        fprintf(stderr, "libralign_hip: device id may not change within a process\n");
-        exit(EXIT_FAILURE);
-    }
-    if (L.eng) gpu_clear();
-    L.device = (int)device_id;
-    L.cfg = *aln_cfg;
-    L.num_particles = num_particles;
-    ra_config rc = legacy_config(aln_cfg, device_id, RA_MODE_MREF);
-    rc.chunk = (int)std::min<unsigned>(8192, std::max(2u, aln_cfg->sbj_num));
-    if (ra_create(&L.eng, &rc)) die("pre_align_init");
-    const size_t npix = (size_t)aln_cfg->img_dim * aln_cfg->img_dim;
-    const size_t B = aln_cfg->sbj_num, R = aln_cfg->ref_num;
-    hip_or_die(hipHostMalloc((void **)&L.h_param, sizeof(AlignParam) * std::max(1u, num_particles)), "param alloc");
-    for (unsigned i = 0; i < num_particles; i++) {
-        L.h_param[i].sbj_id = -1; L.h_param[i].ref_id = 0; L.h_param[i].shift_x = 0; L.h_param[i].shift_y = 0;
-        L.h_param[i].angle = 0; L.h_param[i].mirror = false;
-    }
-    L.stage_imgs = std::max(B, R);
-    hip_or_die(hipHostMalloc((void **)&L.h_stage, L.stage_imgs * npix * sizeof(float)), "stage alloc");
-    hip_or_die(hipHostMalloc((void **)&L.h_state, B * 2 * sizeof(float)), "state alloc");
-    hip_or_die(hipHostMalloc((void **)&L.h_res, B * sizeof(ra_result)), "res alloc");
-    hip_or_die(hipHostMalloc((void **)&L.h_sums, R * 2 * npix * sizeof(float)), "sums alloc");
-    hip_or_die(hipHostMalloc((void **)&L.h_counts, R * sizeof(int)), "counts alloc");
-    hip_or_die(hipMalloc((void **)&L.d_sbj, B * npix * sizeof(float)), "sbj alloc");
-    hip_or_die(hipMalloc((void **)&L.d_aligned, B * npix * sizeof(float)), "aligned alloc");
-    hip_or_die(hipMalloc((void **)&L.d_ref, R * npix * sizeof(float)), "ref alloc");
-    hip_or_die(hipMalloc((void **)&L.d_state, B * 2 * sizeof(float)), "state alloc");
-    hip_or_die(hipMalloc((void **)&L.d_res, B * sizeof(ra_result)), "res alloc");
-    hip_or_die(hipMalloc((void **)&L.d_sums, R * 2 * npix * sizeof(float)), "sums alloc");
-    hip_or_die(hipMalloc((void **)&L.d_counts, R * sizeof(int)), "counts alloc");
-    hip_or_die(hipMemset(L.d_res, 0, B * sizeof(ra_result)), "res clear");
-    return L.h_param;
-}
-
-extern "C" bool pre_align_size_check(const unsigned int num_particles, const AlignConfig *cfg,
-                                     const unsigned int device_id, const float request, const bool verbose)
-{
-    if (!cfg) return false;
-    if (hipSetDevice((int)device_id) != hipSuccess) return false;
-    size_t need = legacy_bytes(num_particles, cfg);
-    size_t fr = 0, tot = 0;
-    if (need == (size_t)-1 || hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
-    if (verbose)
-        printf("GPU[%u] SIZE CHECK: need %zu MB of %zu MB free (request %.2f)\n", device_id, need >> 20, fr >> 20, request);
-    return (double)need <= (double)fr * request;
-}
-
-extern "C" void pre_align_fetch(const float **img_data, const unsigned int img_num, const char *batch_type)
-{
-    if (!L.eng) { fprintf(stderr, "libralign_hip: pre_align_fetch before pre_align_init\n"); exit(EXIT_FAILURE); }
-    const size_t npix = (size_t)L.cfg.img_dim * L.cfg.img_dim;
-    const bool is_sbj = batch_type && strcmp(batch_type, "sbj_batch") == 0;
-    const bool is_ref = batch_type && strcmp(batch_type, "ref_batch") == 0;
-    if (!is_sbj && !is_ref) {
-        // same message and behaviour as gpu_aln_noref.cu:373-376
-        printf("ERROR! fetch_data() :: Unknown batch type '%s' specified.\n", batch_type ? batch_type : "(null)");
-        return;
-    }
-    const unsigned cap = is_sbj ? L.cfg.sbj_num : L.cfg.ref_num;
-    if (img_num > cap || !img_data) { fprintf(stderr, "libralign_hip: pre_align_fetch: %u images exceed the batch (%u)\n", img_num, cap); exit(EXIT_FAILURE); }
-    // gather into one pinned block and ship with a single copy
-    for (unsigned i = 0; i < img_num; i++) memcpy(L.h_stage + (size_t)i * npix, img_data[i], npix * sizeof(float));
-    float *dst = is_sbj ? L.d_sbj : L.d_ref;
-    hip_or_die(hipMemcpy(dst, L.h_stage, (size_t)img_num * npix * sizeof(float), hipMemcpyHostToDevice), "image upload");
-    if (is_sbj) L.sbj_loaded = img_num;
-    else if (ra_set_references(L.eng, L.d_ref)) die("ra_set_references");
-}
-
-extern "C" void pre_align_run(const int start_idx, const int stop_idx)
-{
-    run_search(start_idx, stop_idx, RA_MODE_REFFREE);
-    fetch_results(start_idx, stop_idx);
-}
-
-extern "C" void *pre_align_run_m(const int start_idx, const int stop_idx)
-{
-    run_search(start_idx, stop_idx, RA_MODE_REFFREE);
-    if (ra_transform_accumulate(L.eng, L.d_sbj, stop_idx - start_idx, start_idx, L.d_res, L.d_aligned, nullptr, nullptr)) die("transform");
-    fetch_results(start_idx, stop_idx);
-    return L.d_aligned;
-}
-
-extern "C" void *mref_align_run(const int start_idx, const int stop_idx)
-{
-    run_search(start_idx, stop_idx, RA_MODE_MREF);
-    if (ra_transform_accumulate(L.eng, L.d_sbj, stop_idx - start_idx, start_idx, L.d_res, L.d_aligned, nullptr, nullptr)) die("transform");
-    fetch_results(start_idx, stop_idx);
-    return L.d_aligned;
-}
-
-extern "C" float *mref_align_run_m(const int start_idx, const int stop_idx)
-{
-    const size_t npix = (size_t)L.cfg.img_dim * L.cfg.img_dim, R = L.cfg.ref_num;
-    run_search(start_idx, stop_idx, RA_MODE_MREF);
-    hip_or_die(hipMemsetAsync(L.d_sums, 0, R * 2 * npix * sizeof(float), L.eng->stream), "sums clear");
-    hip_or_die(hipMemsetAsync(L.d_counts, 0, R * sizeof(int), L.eng->stream), "counts clear");
-    if (ra_transform_accumulate(L.eng, L.d_sbj, stop_idx - start_idx, start_idx, L.d_res, L.d_aligned, L.d_sums, L.d_counts)) die("transform");
-    fetch_results(start_idx, stop_idx);
-    // reference layout: all even averages, then all odd ones (test_mref_cheng_yu_bdb_cuda.py:550-551)
-    std::vector<float> tmp(R * 2 * npix);
-    hip_or_die(hipMemcpy(tmp.data(), L.d_sums, tmp.size() * sizeof(float), hipMemcpyDeviceToHost), "sums download");
-    for (size_t r = 0; r < R; r++) {
-        memcpy(L.h_sums + r * npix, tmp.data() + (r * 2) * npix, npix * sizeof(float));
-        memcpy(L.h_sums + (R + r) * npix, tmp.data() + (r * 2 + 1) * npix, npix * sizeof(float));
-    }
-    hip_or_die(hipMemcpy(L.h_counts, L.d_counts, R * sizeof(int), hipMemcpyDeviceToHost), "counts download");
-    return L.h_sums;
-}
-
-extern "C" int *get_num_ref(void) { return L.h_counts; }
-
-extern "C" void reset_shifts(const float shift_range, const float shift_step)
-{
-    if (!L.eng) { fprintf(stderr, "libralign_hip: reset_shifts before pre_align_init\n"); exit(EXIT_FAILURE); }
-    if (ra_reset_shifts(L.eng, shift_range, shift_range, shift_step)) die("reset_shifts");
-}
-
-// ---------------------------------------------------------------------------------------------
-// class-resident reference-free alignment (cuda/gpu_aln_noref.h:94-109, gpu_aln_noref.cu:559-782; SURVEY.md
-// section 8 row f-3): particles arrive sorted by class, every particle is aligned to the average of its own class
-// (single-reference search with sp_alignment.ormq semantics), transformed, and the class averages are rebuilt
-// on the device from the aligned images; ref_free_alignment_2D_filter_references applies the tangent low-pass.
-
-// mean of the aligned images of the contiguous class range [cid_idx[r], cid_idx[r+1]) in particle order
-// (cu_average_batch, gpu_aln_noref.cu:1199-1229); an empty class keeps its previous reference
-__global__ __launch_bounds__(256) void class_mean_kernel(int npix, const float *__restrict__ aligned,
-                                                         const unsigned *__restrict__ cid_idx, float *__restrict__ refs)
-{
-    const int r = blockIdx.x;
-    const unsigned b = cid_idx[r], e = cid_idx[r + 1];
-    if (e <= b) return;
-    for (int pix = blockIdx.y * blockDim.x + threadIdx.x; pix < npix; pix += gridDim.y * blockDim.x) {
-        float avg = 0.f;
-        for (unsigned i = b; i < e; i++) avg += aligned[(size_t)i * npix + pix];
-        refs[(size_t)r * npix + pix] = avg / (float)(e - b);
-    }
-}
-
-static size_t isac_bytes(const AlignConfig *c)
-{
-    AlignConfig one = *c;
-    one.ref_num = 1;
-    const size_t npix = (size_t)c->img_dim * c->img_dim;
-    size_t need = legacy_bytes(c->sbj_num, &one);
-    if (need == (size_t)-1) return need;
-    return need + (size_t)c->ref_num * npix * 4 + ((size_t)c->ref_num + 1) * 4;
-}
-
-extern "C" AlignParam *ref_free_alignment_2D_init(const AlignConfig *aln_cfg, const float **sbj_data_list,
-                                                  const float **ref_data_list, const int *sbj_cid_list,
-                                                  const unsigned int device_id)
-{
-    if (!aln_cfg || !sbj_data_list || !ref_data_list || !sbj_cid_list) {
-        fprintf(stderr, "libralign_hip: ref_free_alignment_2D_init: null argument\n");
-        exit(EXIT_FAILURE);
-    }
-    if (L.device != -1 && L.device != (int)device_id) {
-        fprintf(stderr, "libralign_hip: device id may not change within a process\n");
-        exit(EXIT_FAILURE);
-    }
-    if (L.eng) gpu_clear();
-    L.device = (int)device_id;
-    L.cfg = *aln_cfg;
-    L.num_particles = aln_cfg->sbj_num;
-    L.isac = true;
-    const size_t npix = (size_t)aln_cfg->img_dim * aln_cfg->img_dim;
-    const size_t B = aln_cfg->sbj_num, R = aln_cfg->ref_num;
-    // class index list as the reference builds it (gpu_aln_noref.cu:611-620): a new class starts where the id changes
-    L.cid_idx.assign(R + 1, (unsigned)B);
-    {
-        int cid = -1; size_t idx = 0;
-        for (size_t i = 0; i < B; i++)
-            if (sbj_cid_list[i] != cid) {
-                if (idx >= R) { fprintf(stderr, "libralign_hip: ref_free_alignment_2D_init: more class runs than references\n"); exit(EXIT_FAILURE); }
-                L.cid_idx[idx++] = (unsigned)i; cid = sbj_cid_list[i];
-            }
-    }
-    ra_config rc = legacy_config(aln_cfg, device_id, RA_MODE_REFFREE);
-    rc.nref = 1;
-    rc.chunk = (int)std::min<unsigned>(8192, std::max(2u, aln_cfg->sbj_num));
-    if (ra_create(&L.eng, &rc)) die("ref_free_alignment_2D_init");
-    hip_or_die(hipHostMalloc((void **)&L.h_param, sizeof(AlignParam) * std::max<size_t>(1, B)), "param alloc");
-    for (size_t i = 0; i < B; i++) {
-        L.h_param[i].sbj_id = -1; L.h_param[i].ref_id = sbj_cid_list[i]; L.h_param[i].shift_x = 0; L.h_param[i].shift_y = 0;
-        L.h_param[i].angle = 0; L.h_param[i].mirror = false;
-    }
-    L.stage_imgs = std::max(B, R);
-    hip_or_die(hipHostMalloc((void **)&L.h_stage, L.stage_imgs * npix * sizeof(float)), "stage alloc");
-    hip_or_die(hipHostMalloc((void **)&L.h_state, B * 2 * sizeof(float)), "state alloc");
-    hip_or_die(hipHostMalloc((void **)&L.h_res, B * sizeof(ra_result)), "res alloc");
-    hip_or_die(hipMalloc((void **)&L.d_sbj, B * npix * sizeof(float)), "sbj alloc");
-    hip_or_die(hipMalloc((void **)&L.d_aligned, B * npix * sizeof(float)), "aligned alloc");
-    hip_or_die(hipMalloc((void **)&L.d_ref, R * npix * sizeof(float)), "ref alloc");
-    hip_or_die(hipMalloc((void **)&L.d_state, B * 2 * sizeof(float)), "state alloc");
-    hip_or_die(hipMalloc((void **)&L.d_res, B * sizeof(ra_result)), "res alloc");
-    hip_or_die(hipMalloc((void **)&L.d_cid_idx, (R + 1) * sizeof(unsigned)), "cid alloc");
-    hip_or_die(hipMemset(L.d_res, 0, B * sizeof(ra_result)), "res clear");
-    hip_or_die(hipMemcpy(L.d_cid_idx, L.cid_idx.data(), (R + 1) * sizeof(unsigned), hipMemcpyHostToDevice), "cid upload");
-    {
-        std::vector<int> cls(B);
-        for (unsigned r = 0; r < R; r++)
-            for (unsigned i = L.cid_idx[r]; i < L.cid_idx[r + 1]; i++) cls[i] = (int)r;
-        hip_or_die(hipMalloc((void **)&L.d_cls, B * sizeof(int)), "class index alloc");
-        hip_or_die(hipMemcpy(L.d_cls, cls.data(), B * sizeof(int), hipMemcpyHostToDevice), "class index upload");
-    }
-    for (size_t i = 0; i < B; i++) memcpy(L.h_stage + i * npix, sbj_data_list[i], npix * sizeof(float));
-    hip_or_die(hipMemcpy(L.d_sbj, L.h_stage, B * npix * sizeof(float), hipMemcpyHostToDevice), "image upload");
-    for (size_t i = 0; i < R; i++) memcpy(L.h_stage + i * npix, ref_data_list[i], npix * sizeof(float));
-    hip_or_die(hipMemcpy(L.d_ref, L.h_stage, R * npix * sizeof(float), hipMemcpyHostToDevice), "reference upload");
-    L.sbj_loaded = (unsigned)B;
-    return L.h_param;
-}
-
-extern "C" bool ref_free_alignment_2D_size_check(const AlignConfig *cfg, const unsigned int device_id, const float request,
-                                                 const bool verbose)
-{
-    if (!cfg) return false;
-    if (hipSetDevice((int)device_id) != hipSuccess) return false;
-    const size_t need = isac_bytes(cfg);
-    size_t fr = 0, tot = 0;
-    if (need == (size_t)-1 || hipMemGetInfo(&fr, &tot) != hipSuccess) return false;
-    if (verbose)
-        printf("GPU[%u] SIZE CHECK: need %zu MB of %zu MB free (request %.2f)\n", device_id, need >> 20, fr >> 20, request);
-    return (double)need <= (double)fr * request;
-}
-
-extern "C" void ref_free_alignment_2D(void)
-{
-    if (!L.eng || !L.isac) { fprintf(stderr, "libralign_hip: ref_free_alignment_2D before ref_free_alignment_2D_init\n"); exit(EXIT_FAILURE); }
-    const size_t npix = (size_t)L.cfg.img_dim * L.cfg.img_dim;
-    const unsigned B = L.cfg.sbj_num, R = L.cfg.ref_num;
-    for (unsigned i = 0; i < B; i++) { L.h_state[2 * i] = L.h_param[i].shift_x; L.h_state[2 * i + 1] = L.h_param[i].shift_y; }
-    hip_or_die(hipMemcpy(L.d_state, L.h_state, sizeof(float) * 2 * B, hipMemcpyHostToDevice), "state upload");
-    // all classes in one launch where the fused search kernel covers the geometry, class by class otherwise
-    if (ra_set_class_references(L.eng, L.d_ref, (int)R) == RA_OK) {
-        if (ra_align_classes(L.eng, L.d_sbj, (int)B, L.d_state, L.d_res, L.d_cls)) die("ra_align_classes");
-    } else {
-        for (unsigned r = 0; r < R; r++) {
-            const unsigned b = L.cid_idx[r], e = L.cid_idx[r + 1];
-            if (e <= b) continue;
-            if (ra_set_references(L.eng, L.d_ref + (size_t)r * npix)) die("ra_set_references");
-            if (ra_align(L.eng, L.d_sbj + (size_t)b * npix, (int)(e - b), L.d_state + 2 * (size_t)b, L.d_res + b, nullptr)) die("ra_align");
-        }
-    }
-    if (ra_transform_accumulate(L.eng, L.d_sbj, (int)B, 0, L.d_res, L.d_aligned, nullptr, nullptr)) die("transform");
-    hipLaunchKernelGGL(class_mean_kernel, dim3(R, 8), dim3(256), 0, L.eng->stream, (int)npix, L.d_aligned, L.d_cid_idx, L.d_ref);
-    hip_or_die(hipGetLastError(), "class_mean_kernel");
-    if (ra_sync(L.eng)) die("sync");
-    hip_or_die(hipMemcpy(L.h_res, L.d_res, sizeof(ra_result) * B, hipMemcpyDeviceToHost), "result download");
-    hip_or_die(hipMemcpy(L.h_state, L.d_state, sizeof(float) * 2 * B, hipMemcpyDeviceToHost), "state download");
-    for (unsigned i = 0; i < B; i++) {      // ref_id keeps the class id given at init (gpu_aln_noref.cu:607-608)
-        AlignParam &a = L.h_param[i];
-        a.shift_x = L.h_state[2 * i]; a.shift_y = L.h_state[2 * i + 1];
-        a.angle = L.h_res[i].alpha;
-        a.mirror = L.h_res[i].mirror != 0;
-    }
-}
-
-extern "C" void ref_free_alignment_2D_filter_references(const float cutoff_freq, const float falloff)
-{
-    if (!L.eng || !L.isac) { fprintf(stderr, "libralign_hip: filter_references before ref_free_alignment_2D_init\n"); exit(EXIT_FAILURE); }
-    if (ra_filter_references(L.eng, L.d_ref, (int)L.cfg.ref_num, cutoff_freq, falloff, 0, nullptr, 0, nullptr)) die("ra_filter_references");
-    if (ra_sync(L.eng)) die("sync");
-}
-
-// extension (not in the reference header): copy the current class averages [ref_num][nx][nx] to host memory
-extern "C" int ra_isac_get_references(float *h_out)
-{
-    if (!L.eng || !L.isac || !h_out) { g_last_error = "class-resident mode is not initialised"; return RA_ERR_STATE; }
-    const size_t npix = (size_t)L.cfg.img_dim * L.cfg.img_dim;
-    RA_HIP(hipMemcpy(h_out, L.d_ref, (size_t)L.cfg.ref_num * npix * sizeof(float), hipMemcpyDeviceToHost));
-    return RA_OK;
-}
-
-// diagnostic: the device-memory estimate behind pre_align_size_check, in bytes ((size_t)-1 = bad geometry)
-extern "C" size_t ra_legacy_bytes(const unsigned int num_particles, const AlignConfig *cfg)
-{
-    return cfg ? legacy_bytes(num_particles, cfg) : (size_t)-1;
-}
-
-// ---- CTF phase flip (ralign_ctf.h)
-
-#define PF_GBLK_BYTES ((size_t)512 << 20)      // global scratch of the large-box route: the grid is sized to stay within it
-
-// the [n][9] CTF rows (host memory) within the ranges the flip and the Wiener averages accept; sets g_last_error naming the row
-static bool pf_rows_ok(const char *what, const float *ctf, int n)
-{
-    for (int i = 0; i < n; i++) {
-        const float *c = ctf + (size_t)i * 9;
-        bool finite = true;
-        for (int j = 0; j < 9; j++) finite = finite && std::isfinite(c[j]);
-        if (!finite || c[0] <= 0.f || c[1] <= 0.f || c[5] <= 0.f || c[7] < 0.f || c[7] >= 1.f) {
-            char buf[256];
-            snprintf(buf, sizeof(buf), "%s: CTF row %d out of range (needs finite values, D > 0, Apix > 0, "
-                     "voltage > 0, 0 <= w < 1)", what, i);
-            g_last_error = buf;
-            return false;
-        }
-    }
-    return true;
-}
-
-// workgroups of the global-block route: as many as fit on the chip at this LDS size (256 CUs), within PF_GBLK_BYTES of scratch
-static int pf_gblk_grid(const PfPlan &pl, int n)
-{
-    const size_t blk_bytes = (size_t)pl.nx * pl.H * sizeof(float2);
-    const size_t resident = (size_t)256 * std::max(1, std::min(4, (int)((size_t)160 * 1024 / pl.lds)));     // <= 32 waves per CU
-    return (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(resident, PF_GBLK_BYTES / blk_bytes)));
-}
-
-extern "C" int ra_phase_flip(float *d_images, int n, int nx, const float *ctf, int pad, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 0 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1)) {
-        g_last_error = "ra_phase_flip: need n >= 0, 2 <= nx <= 1024 and pad 0 or 1";
-        return RA_ERR_ARG;
-    }
-    if (n == 0) return RA_OK;
-    if (!d_images || !ctf) { g_last_error = "ra_phase_flip: null argument"; return RA_ERR_ARG; }
-    if (!pf_rows_ok("ra_phase_flip", ctf, n)) return RA_ERR_ARG;
-    const PfPlan pl = pf_make_plan(nx, pad);
-    if (pl.nb < 1) { g_last_error = "ra_phase_flip: no plan for this box"; return RA_ERR_ARG; }
-    // the common boxes run a kernel specialised for their plan; any other box the kernel that takes the plan as an argument
-    const void *fk = nullptr;
-    switch (nx * 2 + pad) {
-    case 90 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<90, 1>; break;
-    case 90 * 2: fk = (const void *)phase_flip_fixed_kernel<90, 0>; break;
-    case 100 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<100, 1>; break;
-    case 128 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<128, 1>; break;
-    case 130 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<130, 1>; break;
-    case 256 * 2 + 1: fk = (const void *)phase_flip_fixed_kernel<256, 1>; break;
-    default: break;
-    }
-    const bool fixed = fk != nullptr;
-    if (!fixed) fk = pl.gblk ? (const void *)phase_flip_kernel<true> : (const void *)phase_flip_kernel<false>;
-    if (const int rc = raise_dynamic_lds(nullptr, fk, fixed ? "phase_flip_fixed_kernel" : "phase_flip_kernel", (size_t)pl.lds)) return rc;
-    const size_t blk_bytes = (size_t)nx * pl.H * sizeof(float2);
-    const int grid = pl.gblk ? pf_gblk_grid(pl, n) : n;
-    float *d_ctf = nullptr;
-    float2 *d_scr = nullptr;
-    RA_HIP(hipMallocAsync((void **)&d_ctf, (size_t)n * 9 * sizeof(float), stream));
-    // the table is pageable host memory of the caller: hipMemcpyAsync stages such a copy before it returns, so the caller may free
-    // it as soon as this call returns (a caller passing PINNED memory must keep it alive until the stream has run the copy)
-    hipError_t he = hipMemcpyAsync(d_ctf, ctf, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_scr, (size_t)grid * blk_bytes, stream);
-    if (he == hipSuccess) {
-        void *args_fixed[] = {&d_images, &n, &d_ctf, &d_scr};
-        PfPlan pl_arg = pl;
-        void *args_plan[] = {&d_images, &n, &d_ctf, &pl_arg, &d_scr};
-        he = hipLaunchKernel(fk, dim3(grid), dim3(PF_THREADS), fixed ? args_fixed : args_plan, pl.lds, stream);
-        if (he == hipSuccess) he = hipGetLastError();
-    }
-    if (d_scr) (void)hipFreeAsync(d_scr, stream);
-    (void)hipFreeAsync(d_ctf, stream);
-    if (he != hipSuccess) {
-        g_last_error = std::string("ra_phase_flip: ") + hipGetErrorString(he);
-        return RA_ERR_HIP;
-    }
-    return RA_OK;
-}
-
-// ---- two-stage dimension reduction (ralign_sdr.h) and rot_shift2D without an engine
-
-static int sdr_launch_error(const char *what, hipError_t he)
-{
-    g_last_error = std::string(what) + ": " + hipGetErrorString(he);
-    return RA_ERR_HIP;
-}
-
-extern "C" int ra_sdr_mean(const float *d_images, int n, int p, int q, float *d_mean, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 1 || p < 1 || p > 256 || q < 1 || q > (p == 1 ? 2048 : 256)) {
-        g_last_error = "ra_sdr_mean: need n >= 1 and 1 <= p, q <= 256 (p == 1: q <= 2048)";
-        return RA_ERR_ARG;
-    }
-    if (!d_images || !d_mean) { g_last_error = "ra_sdr_mean: null argument"; return RA_ERR_ARG; }
-    const int npix = p * q, nch = (n + SDR_MEAN_RUN - 1) / SDR_MEAN_RUN;
-    double *d_part = nullptr;
-    hipError_t he = hipMallocAsync((void **)&d_part, (size_t)nch * npix * sizeof(double), stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_sdr_mean", he);
-    hipLaunchKernelGGL(sdr_mean_partial_kernel, dim3((npix + 255) / 256, nch), dim3(256), 0, stream, d_images, n, npix, d_part);
-    he = hipGetLastError();
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(sdr_mean_combine_kernel, dim3((npix + 63) / 64), dim3(64 * SDR_COMBINE_WAVES), 0, stream, d_part, nch, npix, n, d_mean);
-        he = hipGetLastError();
-    }
-    (void)hipFreeAsync(d_part, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_sdr_mean", he);
-}
-
-extern "C" int ra_sdr_gram(const float *d_images, int n, int p, int q, const float *d_mean, int form, const float *d_proj, int k,
-                           double *d_gram, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (form < 0 || form > 2 || n < 1 || p < 1 || p > 256 || q < 1 || q > (form == 0 && p == 1 ? 2048 : 256)) {
-        g_last_error = "ra_sdr_gram: need form 0, 1 or 2, n >= 1, 1 <= p, q <= 256 (form 0 with p == 1: q <= 2048)";
-        return RA_ERR_ARG;
-    }
-    if (form != 0 && (k < 1 || k > 64 || k > (form == 1 ? q : p) || !d_proj)) {
-        g_last_error = "ra_sdr_gram: forms 1 and 2 need a projector with 1 <= k <= 64 columns and k <= q (form 1) or k <= p (form 2)";
-        return RA_ERR_ARG;
-    }
-    if (!d_images || !d_gram) { g_last_error = "ra_sdr_gram: null argument"; return RA_ERR_ARG; }
-    SdrGramArgs g;
-    g.x = d_images; g.mean = d_mean; g.proj = form ? d_proj : nullptr;
-    g.n = n; g.p = p; g.q = q; g.k = form ? k : 0;
-    g.d = form == 1 ? p : q;
-    g.nb = (g.d + 127) / 128;
-    g.ns = ((g.d + g.nb - 1) / g.nb + 15) / 16;
-    g.ntile = g.nb * (g.nb + 1) / 2;
-    g.kt = form ? (k + 15) / 16 : 1;
-    g.run = form ? SDR_RUN_IMAGES : std::max(1, SDR_RUN0_ROWS / p);
-    const int nrun = (n + g.run - 1) / g.run, TD = 16 * g.ns;
-    const size_t lds = (size_t)16 * g.kt * (2 * TD + 16) * sizeof(float);
-    const void *fk = form == 0 ? (const void *)sdr_gram_kernel<0> : form == 1 ? (const void *)sdr_gram_kernel<1> : (const void *)sdr_gram_kernel<2>;
-    if (const int rc = raise_dynamic_lds(nullptr, fk, "sdr_gram_kernel", lds)) return rc;
-    hipError_t he = hipMallocAsync((void **)&g.part, (size_t)nrun * g.ntile * TD * TD * sizeof(float), stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_sdr_gram", he);
-    void *args[] = {&g};
-    he = hipLaunchKernel(fk, dim3(nrun, g.ntile), dim3(SDR_THREADS), args, lds, stream);
-    if (he == hipSuccess) he = hipGetLastError();
-    if (he == hipSuccess) {
-        const size_t nel = (size_t)g.d * g.d;
-        hipLaunchKernelGGL(sdr_gram_combine_kernel, dim3((unsigned)((nel + 63) / 64)), dim3(64 * SDR_COMBINE_WAVES), 0, stream, g.part, nrun,
-                           g.ntile, g.nb, g.ns, g.d, d_gram);
-        he = hipGetLastError();
-    }
-    (void)hipFreeAsync(g.part, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_sdr_gram", he);
-}
-
-extern "C" int ra_sdr_project(const float *d_images, int n, int p, int q, const float *d_mean, const float *d_A, int p0, const float *d_B,
-                              int q0, float *d_U, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 1 || p < 1 || p > 256 || q < 1 || q > 256 || p0 < 1 || p0 > std::min(p, 64) || q0 < 1 || q0 > std::min(q, 64) || p0 * q0 > 2048) {
-        g_last_error = "ra_sdr_project: need n >= 1, 1 <= p, q <= 256, 1 <= p0 <= min(p, 64), 1 <= q0 <= min(q, 64) and p0 q0 <= 2048";
-        return RA_ERR_ARG;
-    }
-    if (!d_images || !d_A || !d_B || !d_U) { g_last_error = "ra_sdr_project: null argument"; return RA_ERR_ARG; }
-    const size_t lds = (size_t)16 * ((q0 + 15) / 16) * (16 * ((p + 15) / 16) + 4) * sizeof(float);
-    if (const int rc = RA_LDS(nullptr, sdr_project_kernel, lds)) return rc;
-    hipLaunchKernelGGL(sdr_project_kernel, dim3(n), dim3(SDR_THREADS), lds, stream, d_images, d_mean, p, q, d_A, p0, d_B, q0, d_U);
-    const hipError_t he = hipGetLastError();
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_sdr_project", he);
-}
-
-extern "C" int ra_sdr_factors(const float *d_U, int n, int m, const float *d_G, int r, float *d_F, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 1 || m < 1 || m > 2048 || r < 1 || r > std::min(256, m)) {
-        g_last_error = "ra_sdr_factors: need n >= 1, 1 <= m <= 2048 and 1 <= r <= min(256, m)";
-        return RA_ERR_ARG;
-    }
-    if (!d_U || !d_G || !d_F) { g_last_error = "ra_sdr_factors: null argument"; return RA_ERR_ARG; }
-    hipLaunchKernelGGL(sdr_factors_kernel, dim3((n + 63) / 64, (r + 63) / 64), dim3(SDR_THREADS), 0, stream, d_U, n, m, d_G, r, d_F);
-    hipError_t he = hipGetLastError();
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_sdr_factors", he);
-}
+// ---- rot_shift2D without an engine (it launches the engine's transform kernels)
 
 extern "C" int ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result *d_params, float *d_out, void *hip_stream)
 {
@@ -3036,739 +2455,5 @@ extern "C" int ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result 
                            (float *)nullptr, (int *)nullptr);
     }
     if (he == hipSuccess) he = hipGetLastError();
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_rot_shift2d", he);
-}
-
-// ---- t-SNE (ralign_tsne.h)
-
-extern "C" int ra_tsne_knn(const float *d_x, int n, int d, int k, int *d_idx, double *d_dist2, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 2 || n > TSNE_MAX_N || d < 1 || d > TSNE_MAX_D || k < 1 || k > std::min(n - 1, TSNE_MAX_K)) {
-        g_last_error = "ra_tsne_knn: need 2 <= n <= 262144, 1 <= d <= 2048 and 1 <= k <= min(n - 1, 301)";
-        return RA_ERR_ARG;
-    }
-    if (!d_x || !d_idx || !d_dist2) { g_last_error = "ra_tsne_knn: null argument"; return RA_ERR_ARG; }
-    TsneKnnArgs a;
-    a.x = d_x; a.n = n; a.d = d; a.k = k;
-    a.C = std::min(n - 1, k + TSNE_KNN_MARGIN);
-    a.cap = a.C + TSNE_KNN_SLACK;
-    a.idx = d_idx; a.dist2 = d_dist2;
-    const size_t lds = (size_t)16 * a.C * sizeof(double) + (size_t)16 * TSNE_KNN_TILE * sizeof(float) + (size_t)16 * a.cap * 8;
-    if (const int rc = RA_LDS(nullptr, tsne_knn_kernel, lds)) return rc;
-    float *d_nrm = nullptr;
-    hipError_t he = hipMallocAsync((void **)&d_nrm, (size_t)n * sizeof(float), stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_tsne_knn", he);
-    a.nrm = d_nrm;
-    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, d_nrm);
-    he = hipGetLastError();
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(tsne_knn_kernel, dim3((n + 15) / 16), dim3(TSNE_KNN_THREADS), lds, stream, a);
-        he = hipGetLastError();
-    }
-    (void)hipFreeAsync(d_nrm, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_tsne_knn", he);
-}
-
-extern "C" int ra_tsne_affinity(const double *d_dist2, int n, int k, float perplexity, double *d_pcond, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 2 || n > TSNE_MAX_N || k < 1 || k > std::min(n - 1, TSNE_MAX_K) || !(perplexity > 0.f && perplexity <= 100.f)) {
-        g_last_error = "ra_tsne_affinity: need 2 <= n <= 262144, 1 <= k <= min(n - 1, 301) and 0 < perplexity <= 100";
-        return RA_ERR_ARG;
-    }
-    if (!d_dist2 || !d_pcond) { g_last_error = "ra_tsne_affinity: null argument"; return RA_ERR_ARG; }
-    hipLaunchKernelGGL(tsne_affinity_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, d_dist2, n, k, log((double)perplexity), d_pcond);
-    hipError_t he = hipGetLastError();
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_tsne_affinity", he);
-}
-
-// repulsion partials, then the update kernel in the given mode, then (if d_stats) the statistics
-static int tsne_run(const char *what, const float *d_y, float *d_y_out, float *d_update, float *d_gains, float *d_grad, int n,
-                    const int *d_indptr, const int *d_indices, const float *d_p, int nnz, float exaggeration, float momentum,
-                    float learning_rate, int mode, double *d_stats, hipStream_t stream)
-{
-    const int seg = tsne_segment(n), nseg = (n + seg - 1) / seg, nrb = (n + TSNE_REP_ROWS - 1) / TSNE_REP_ROWS;
-    const int nub = (n + TSNE_UPD_THREADS - 1) / TSNE_UPD_THREADS, nz = nseg * nrb;
-    const size_t part_bytes = (size_t)nseg * n * sizeof(float2), z_bytes = (size_t)nz * sizeof(double);
-    const size_t st_bytes = d_stats ? (size_t)nub * 2 * sizeof(double) : 0;
-    unsigned char *scratch = nullptr;
-    hipError_t he = hipMallocAsync((void **)&scratch, part_bytes + z_bytes + st_bytes, stream);
-    if (he != hipSuccess) return sdr_launch_error(what, he);
-    float2 *part = (float2 *)scratch;
-    double *zpart = (double *)(scratch + part_bytes), *st = d_stats ? (double *)(scratch + part_bytes + z_bytes) : nullptr;
-    hipLaunchKernelGGL(tsne_repulsion_kernel, dim3(nrb, nseg), dim3(TSNE_REP_THREADS), 0, stream, (const float2 *)d_y, n, seg, part, zpart);
-    he = hipGetLastError();
-    if (he == hipSuccess) {
-        TsneUpdateArgs u;
-        u.y = (const float2 *)d_y; u.y_out = (float2 *)d_y_out; u.update = (float2 *)d_update; u.gains = (float2 *)d_gains;
-        u.grad = (float2 *)d_grad; u.part = part; u.zpart = zpart; u.indptr = d_indptr; u.indices = d_indices; u.p = d_p;
-        u.n = n; u.nseg = nseg; u.nz = nz; u.nnz = nnz; u.mode = mode;
-        u.exaggeration = exaggeration; u.momentum = momentum; u.learning_rate = learning_rate; u.stats_part = st;
-        hipLaunchKernelGGL(tsne_update_kernel, dim3(nub), dim3(TSNE_UPD_THREADS), 0, stream, u);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess && d_stats) {
-        hipLaunchKernelGGL(tsne_stats_kernel, dim3(1), dim3(256), 0, stream, st, nub, d_stats);
-        he = hipGetLastError();
-    }
-    (void)hipFreeAsync(scratch, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error(what, he);
-}
-
-static bool tsne_csr_ok(const char *what, int n, int nnz, const int *d_indptr, const int *d_indices, const float *d_p)
-{
-    if (n < 2 || n > TSNE_MAX_N || nnz < 0 || (long long)nnz > 2LL * n * TSNE_MAX_K) {
-        g_last_error = std::string(what) + ": need 2 <= n <= 262144 and 0 <= nnz <= 2 n 301";
-        return false;
-    }
-    if (!d_indptr || (nnz > 0 && (!d_indices || !d_p))) { g_last_error = std::string(what) + ": null argument"; return false; }
-    return true;
-}
-
-extern "C" int ra_tsne_step(const float *d_y, float *d_y_out, float *d_update, float *d_gains, int n, const int *d_indptr,
-                            const int *d_indices, const float *d_p, int nnz, float exaggeration, float momentum, float learning_rate,
-                            double *d_stats, void *hip_stream)
-{
-    if (!tsne_csr_ok("ra_tsne_step", n, nnz, d_indptr, d_indices, d_p)) return RA_ERR_ARG;
-    if (!d_y || !d_y_out || !d_update || !d_gains || d_y_out == d_y) {
-        g_last_error = "ra_tsne_step: null argument, or d_y_out == d_y (the step reads every y_j while it writes)";
-        return RA_ERR_ARG;
-    }
-    if (!std::isfinite(exaggeration) || !std::isfinite(momentum) || !std::isfinite(learning_rate) || !(learning_rate > 0.f)) {
-        g_last_error = "ra_tsne_step: need finite exaggeration and momentum and a finite learning rate > 0";
-        return RA_ERR_ARG;
-    }
-    return tsne_run("ra_tsne_step", d_y, d_y_out, d_update, d_gains, nullptr, n, d_indptr, d_indices, d_p, nnz, exaggeration, momentum,
-                    learning_rate, 0, d_stats, (hipStream_t)hip_stream);
-}
-
-extern "C" int ra_tsne_error(const float *d_y, int n, const int *d_indptr, const int *d_indices, const float *d_p, int nnz,
-                             float exaggeration, float *d_grad, double *d_stats, void *hip_stream)
-{
-    if (!tsne_csr_ok("ra_tsne_error", n, nnz, d_indptr, d_indices, d_p)) return RA_ERR_ARG;
-    if (!d_y || (!d_grad && !d_stats) || !std::isfinite(exaggeration)) {
-        g_last_error = "ra_tsne_error: null embedding, neither gradient nor statistics asked for, or a non-finite exaggeration";
-        return RA_ERR_ARG;
-    }
-    return tsne_run("ra_tsne_error", d_y, nullptr, nullptr, nullptr, d_grad, n, d_indptr, d_indices, d_p, nnz, exaggeration, 0.f, 0.f, 1,
-                    d_stats, (hipStream_t)hip_stream);
-}
-
-// ---- k-means (ralign_kmeans.h)
-
-static bool km_shape_ok(const char *what, int n, int d, int k)
-{
-    if (n < 1 || n > KM_MAX_N || d < 1 || d > KM_MAX_D || k < 1 || k > std::min(n, KM_MAX_K)) {
-        g_last_error = std::string(what) + ": need 1 <= n <= 4194304, 1 <= d <= 2048 and 1 <= k <= min(n, 256)";
-        return false;
-    }
-    return true;
-}
-
-// carves aligned pieces out of one stream-ordered allocation
-struct KmScratch {
-    size_t off = 0;
-    unsigned char *base = nullptr;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-    template <class T> T *at(size_t o) { return (T *)(base + o); }
-};
-
-extern "C" int ra_kmeans_sqnorm(const float *d_x, int n, int d, float *d_nrm, void *hip_stream)
-{
-    if (!km_shape_ok("ra_kmeans_sqnorm", n, d, 1)) return RA_ERR_ARG;
-    if (!d_x || !d_nrm) { g_last_error = "ra_kmeans_sqnorm: null argument"; return RA_ERR_ARG; }
-    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)hip_stream, d_x, n, d, d_nrm);
-    hipError_t he = hipGetLastError();
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_sqnorm", he);
-}
-
-// the E-step: labels (in place, changed counted into d_changed if non-null) and the double distance of each point to its centre.
-// cf [k][d] / cnrm [k]: scratch of the f32 copy (d > KM_SMALL_D only)
-static hipError_t km_assign(const float *x, int n, int d, const float *nrm, const double *c, int k, int *labels, double *dist,
-                            int *changed, float *cf, float *cnrm, hipStream_t stream)
-{
-    if (d <= KM_SMALL_D) {
-        hipLaunchKernelGGL(km_assign_small_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, n, d, c, k, labels, dist, changed);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(km_prep_kernel, dim3(k), dim3(256), 0, stream, c, d, cf, cnrm);
-    hipError_t he = hipGetLastError();
-    if (he != hipSuccess) return he;
-    KmAssignArgs a;
-    a.x = x; a.nrm = nrm; a.c = c; a.cf = cf; a.cnrm = cnrm; a.n = n; a.d = d; a.k = k;
-    a.labels = labels; a.dist = dist; a.changed = changed;
-    const dim3 grid((n + KM_ROWS - 1) / KM_ROWS), block(64 * KM_WAVES);
-    const int nt = (k + 15) / 16;
-    if (nt <= 1) hipLaunchKernelGGL(km_assign_mfma_kernel<1>, grid, block, 0, stream, a);
-    else if (nt <= 2) hipLaunchKernelGGL(km_assign_mfma_kernel<2>, grid, block, 0, stream, a);
-    else if (nt <= 4) hipLaunchKernelGGL(km_assign_mfma_kernel<4>, grid, block, 0, stream, a);
-    else if (nt <= 8) hipLaunchKernelGGL(km_assign_mfma_kernel<8>, grid, block, 0, stream, a);
-    else hipLaunchKernelGGL(km_assign_mfma_kernel<16>, grid, block, 0, stream, a);
-    return hipGetLastError();
-}
-
-extern "C" int ra_kmeans_labels(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, int *d_labels,
-                                int assign, double *d_inertia, void *hip_stream)
-{
-    if (!km_shape_ok("ra_kmeans_labels", n, d, k)) return RA_ERR_ARG;
-    if (!d_x || !d_centers || !d_labels || (!assign && !d_inertia)) {
-        g_last_error = "ra_kmeans_labels: null argument, or neither assignment nor inertia asked for";
-        return RA_ERR_ARG;
-    }
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int nb = (n + 255) / 256;
-    KmScratch S;
-    const size_t o_dist = S.take((size_t)n * 8), o_part = S.take((size_t)nb * 8);
-    const bool big = d > KM_SMALL_D;
-    const size_t o_cf = S.take(big ? (size_t)k * d * 4 : 0), o_cn = S.take(big ? (size_t)k * 4 : 0);
-    const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
-    hipError_t he = hipMallocAsync((void **)&S.base, S.off, stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_labels", he);
-    double *dist = S.at<double>(o_dist);
-    const float *nrm = d_nrm;
-    if (big && !d_nrm) {
-        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
-        he = hipGetLastError();
-        nrm = S.at<float>(o_nrm);
-    }
-    if (he == hipSuccess) {
-        if (assign) {
-            he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, nullptr, S.at<float>(o_cf), S.at<float>(o_cn), stream);
-        } else {
-            hipLaunchKernelGGL(km_point_dist_kernel, dim3(big ? (n + 3) / 4 : nb), dim3(256), 0, stream, d_x, n, d, d_centers, k, d_labels, dist);
-            he = hipGetLastError();
-        }
-    }
-    if (he == hipSuccess && d_inertia) {
-        hipLaunchKernelGGL(km_block_sum_kernel, dim3(nb), dim3(256), 0, stream, dist, n, S.at<double>(o_part));
-        he = hipGetLastError();
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(km_final_sum_kernel, dim3(1), dim3(256), 0, stream, S.at<double>(o_part), nb, d_inertia);
-            he = hipGetLastError();
-        }
-    }
-    (void)hipFreeAsync(S.base, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_labels", he);
-}
-
-extern "C" int ra_kmeans_lloyd(const float *d_x, int n, int d, const float *d_nrm, const double *d_centers, int k, double *d_centers_new,
-                               int *d_labels, double *d_stats, void *hip_stream)
-{
-    if (!km_shape_ok("ra_kmeans_lloyd", n, d, k)) return RA_ERR_ARG;
-    if (!d_x || !d_centers || !d_centers_new || !d_labels || !d_stats || d_centers_new == d_centers) {
-        g_last_error = "ra_kmeans_lloyd: null argument, or d_centers_new == d_centers";
-        return RA_ERR_ARG;
-    }
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, L = km_run_len(n), rmax = (n + L - 1) / L + k;
-    const bool big = d > KM_SMALL_D;
-    KmScratch S;
-    const size_t o_dist = S.take((size_t)n * 8), o_ints = S.take(2 * 4), o_bcnt = S.take((size_t)nb * k * 4);
-    const size_t o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4), o_run0 = S.take((size_t)(k + 1) * 4);
-    const size_t o_mem = S.take((size_t)n * 4), o_part = S.take((size_t)rmax * d * 8), o_sums = S.take((size_t)k * d * 8);
-    const size_t o_wt = S.take((size_t)k * 8), o_shift = S.take((size_t)k * 8);
-    const size_t o_cf = S.take(big ? (size_t)k * d * 4 : 0), o_cn = S.take(big ? (size_t)k * 4 : 0);
-    const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
-    hipError_t he = hipMallocAsync((void **)&S.base, S.off, stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_lloyd", he);
-    int *ints = S.at<int>(o_ints), *bcnt = S.at<int>(o_bcnt), *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start);
-    int *run0 = S.at<int>(o_run0), *mem = S.at<int>(o_mem);
-    double *dist = S.at<double>(o_dist), *part = S.at<double>(o_part), *sums = S.at<double>(o_sums), *wt = S.at<double>(o_wt);
-    double *shift = S.at<double>(o_shift);
-    const float *nrm = d_nrm;
-    he = hipMemsetAsync(ints, 0, 2 * sizeof(int), stream);
-    if (he == hipSuccess && big && !d_nrm) {
-        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
-        he = hipGetLastError();
-        nrm = S.at<float>(o_nrm);
-    }
-    if (he == hipSuccess) he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, ints, S.at<float>(o_cf), S.at<float>(o_cn), stream);
-#define KM_LAUNCH(...) if (he == hipSuccess) { hipLaunchKernelGGL(__VA_ARGS__); he = hipGetLastError(); }
-    KM_LAUNCH(km_hist_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, bcnt)
-    KM_LAUNCH(km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt)
-    KM_LAUNCH(km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, run0)
-    KM_LAUNCH(km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, (const int *)bcnt, (const int *)start, mem)
-    KM_LAUNCH(km_runsum_kernel, dim3(rmax), dim3(256), 0, stream, d_x, n, d, k, L, (const int *)mem, (const int *)cnt, (const int *)start,
-              (const int *)run0, part)
-    KM_LAUNCH(km_combine_kernel, dim3(k), dim3(256), 0, stream, (const double *)part, d, (const int *)cnt, (const int *)run0, sums, wt)
-    KM_LAUNCH(km_relocate_kernel, dim3(1), dim3(1024), 0, stream, d_x, n, d, k, (const int *)d_labels, (const double *)dist, (const int *)cnt,
-              sums, wt, ints + 1)
-    KM_LAUNCH(km_update_kernel, dim3(k), dim3(256), 0, stream, (const double *)sums, (const double *)wt, d_centers, d, k, d_centers_new, shift)
-    KM_LAUNCH(km_stats_kernel, dim3(1), dim3(256), 0, stream, (const double *)shift, k, (const int *)ints, d_stats)
-#undef KM_LAUNCH
-    (void)hipFreeAsync(S.base, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_lloyd", he);
-}
-
-extern "C" int ra_kmeans_search(const double *d_w, int n, const double *d_vals, int m, int *d_idx, void *hip_stream)
-{
-    if (n < 1 || n > KM_MAX_N || m < 1 || m > KM_MAX_M) {
-        g_last_error = "ra_kmeans_search: need 1 <= n <= 4194304 and 1 <= m <= 16";
-        return RA_ERR_ARG;
-    }
-    if (!d_w || !d_vals || !d_idx) { g_last_error = "ra_kmeans_search: null argument"; return RA_ERR_ARG; }
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int nseg = (n + KM_SEG - 1) / KM_SEG;
-    double *buf = nullptr;
-    hipError_t he = hipMallocAsync((void **)&buf, (size_t)3 * nseg * sizeof(double), stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_search", he);
-    double *segsum = buf, *base = buf + nseg, *end = buf + 2 * nseg;
-    hipLaunchKernelGGL(km_segsum_kernel, dim3((nseg + 255) / 256), dim3(256), 0, stream, d_w, n, segsum);
-    he = hipGetLastError();
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(km_segscan_kernel, dim3(1), dim3(256), 0, stream, (const double *)segsum, nseg, base, end);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(km_search_kernel, dim3(m), dim3(256), 0, stream, d_w, n, (const double *)base, (const double *)end, nseg, d_vals, d_idx);
-        he = hipGetLastError();
-    }
-    (void)hipFreeAsync(buf, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_search", he);
-}
-
-extern "C" int ra_kmeans_seed(const float *d_x, int n, int d, const int *d_cand, int m, double *d_closest, int first, double *d_out,
-                              void *hip_stream)
-{
-    if (!km_shape_ok("ra_kmeans_seed", n, d, 1)) return RA_ERR_ARG;
-    if (m < 1 || m > KM_MAX_M || (first && m != 1)) {
-        g_last_error = "ra_kmeans_seed: need 1 <= m <= 16 candidates (first centre: m = 1)";
-        return RA_ERR_ARG;
-    }
-    if (!d_x || !d_cand || !d_closest || !d_out) { g_last_error = "ra_kmeans_seed: null argument"; return RA_ERR_ARG; }
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const int nb = (n + 255) / 256;
-    double *part = nullptr;
-    hipError_t he = hipMallocAsync((void **)&part, (size_t)m * nb * sizeof(double), stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_kmeans_seed", he);
-    hipLaunchKernelGGL(km_cand_dist_kernel, dim3(nb, m), dim3(256), 0, stream, d_x, n, d, d_cand, first ? (const double *)nullptr : d_closest, part);
-    he = hipGetLastError();
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(km_pick_kernel, dim3(1), dim3(256), 0, stream, (const double *)part, nb, d_cand, m, n, d_out);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(km_commit_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, (const double *)d_out, first, d_closest);
-        he = hipGetLastError();
-    }
-    (void)hipFreeAsync(part, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_kmeans_seed", he);
-}
-
-// ---- Fourier resizing (ralign_resize.h)
-
-extern "C" int ra_fourier_resize(const float *d_in, int n, int nx, int m, float *d_out, void *hip_stream)
-{
-    if (n < 0 || nx < 1 || nx > RS_MAX_BOX || m < 1 || m > RS_MAX_BOX) {
-        g_last_error = "ra_fourier_resize: need n >= 0 and 1 <= nx, m <= 1024";
-        return RA_ERR_ARG;
-    }
-    if (n == 0) return RA_OK;
-    if (!d_in || !d_out) { g_last_error = "ra_fourier_resize: null argument"; return RA_ERR_ARG; }
-    const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)n * nx * nx * sizeof(float);
-    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)n * m * m * sizeof(float);
-    if (i0 < o1 && o0 < i1) { g_last_error = "ra_fourier_resize: d_in and d_out overlap"; return RA_ERR_ARG; }
-    hipStream_t stream = (hipStream_t)hip_stream;
-    const RsPlan pl = rs_make_plan(nx, m);
-    const void *fk = nullptr;
-    switch (pl.bt / 16) {
-    case 1: fk = (const void *)resize_kernel<1>; break;
-    case 2: fk = (const void *)resize_kernel<2>; break;
-    case 3: fk = (const void *)resize_kernel<3>; break;
-    case 4: fk = (const void *)resize_kernel<4>; break;
-    case 5: fk = (const void *)resize_kernel<5>; break;
-    case 6: fk = (const void *)resize_kernel<6>; break;
-    case 7: fk = (const void *)resize_kernel<7>; break;
-    default: fk = (const void *)resize_kernel<8>; break;
-    }
-    float *Ap = nullptr;
-    const size_t na = (size_t)pl.mp * pl.nxp;
-    hipError_t he = hipMallocAsync((void **)&Ap, na * sizeof(float), stream);
-    if (he != hipSuccess) return sdr_launch_error("ra_fourier_resize", he);
-    hipLaunchKernelGGL(resize_operator_kernel, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, stream, Ap, nx, m, pl.mp, pl.nxp);
-    he = hipGetLastError();
-    // one workgroup per (image, tile); launches of at most 2^30 workgroups
-    const int tiles = pl.nt * pl.nt, per = (1 << 30) / tiles;
-    int nt = pl.nt, nxp = pl.nxp, xvec = (nx % 4 == 0) && (i0 % 16 == 0);
-    for (int lo = 0; lo < n && he == hipSuccess; lo += per) {
-        const int cnt = std::min(per, n - lo);
-        const float *src = d_in + (size_t)lo * nx * nx;
-        float *dst = d_out + (size_t)lo * m * m;
-        int nx_ = nx, m_ = m;
-        void *args[] = {&src, &dst, &nx_, &m_, &nt, &Ap, &nxp, &xvec};
-        he = hipLaunchKernel(fk, dim3((unsigned)cnt * tiles), dim3(RS_THREADS), args, 0, stream);
-        if (he == hipSuccess) he = hipGetLastError();
-    }
-    (void)hipFreeAsync(Ap, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_fourier_resize", he);
-}
-
-// ---- CTF-corrected (Wiener) class averages (ralign_wiener.h)
-
-// the forward kernel of a box: specialised for the boxes the benchmarks know, else the one that takes the plan as an argument
-static const void *wn_forward_fn(int nx, int pad, const PfPlan &pl, bool *fixed)
-{
-    const void *fk = nullptr;
-    switch (nx * 2 + pad) {
-    case 90 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<90, 1>; break;
-    case 90 * 2: fk = (const void *)wn_forward_fixed_kernel<90, 0>; break;
-    case 100 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<100, 1>; break;
-    case 128 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<128, 1>; break;
-    case 130 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<130, 1>; break;
-    case 256 * 2 + 1: fk = (const void *)wn_forward_fixed_kernel<256, 1>; break;
-    default: break;
-    }
-    *fixed = fk != nullptr;
-    if (!fk) fk = pl.gblk ? (const void *)wn_forward_kernel<true> : (const void *)wn_forward_kernel<false>;
-    return fk;
-}
-
-// step 1 of ra_wiener_accumulate / ra_wiener_score: the table and the particles' classes, finiteness and CTF constants on the
-// device; the verdict and the classes come back (a stream synchronisation) before the caller launches anything else
-struct WnPrep {
-    float *d_ctf = nullptr;
-    WnCtf *d_cst = nullptr;
-    int *d_lab = nullptr;
-    std::vector<int> lab;           // [n] classes, then the lowest offending index (n: none)
-    void release(hipStream_t stream)
-    {
-        if (d_lab) (void)hipFreeAsync(d_lab, stream);
-        if (d_cst) (void)hipFreeAsync(d_cst, stream);
-        if (d_ctf) (void)hipFreeAsync(d_ctf, stream);
-        d_lab = nullptr; d_cst = nullptr; d_ctf = nullptr;
-    }
-};
-
-// RA_OK with w filled (the caller releases it), else the error with w released
-static int wn_prepare(const char *fn, const ra_result *d_params, const float *h_ctf, int n, int nx, int P, int k, hipStream_t stream,
-                      WnPrep &w)
-{
-    w.lab.assign((size_t)n + 1, 0);
-    hipError_t he = hipMallocAsync((void **)&w.d_ctf, (size_t)n * 9 * sizeof(float), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&w.d_cst, (size_t)n * sizeof(WnCtf), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&w.d_lab, ((size_t)n + 1) * sizeof(int), stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(w.d_ctf, h_ctf, (size_t)n * 9 * sizeof(float), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = hipMemsetD32Async((hipDeviceptr_t)(w.d_lab + n), n, 1, stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(wn_prep_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_params, (const float *)w.d_ctf, n, nx, P, k,
-                           w.d_cst, w.d_lab, w.d_lab + n);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) he = hipMemcpyAsync(w.lab.data(), w.d_lab, ((size_t)n + 1) * sizeof(int), hipMemcpyDeviceToHost, stream);
-    if (he == hipSuccess) he = hipStreamSynchronize(stream);
-    if (he != hipSuccess) { w.release(stream); return sdr_launch_error(fn, he); }
-    if (w.lab[n] < n) {
-        const int i = w.lab[n];
-        char buf[256];
-        if (w.lab[i] < 0 || w.lab[i] >= k)
-            snprintf(buf, sizeof(buf), "%s: particle %d has class label %d outside 0 .. %d", fn, i, w.lab[i], k - 1);
-        else
-            snprintf(buf, sizeof(buf), "%s: particle %d has non-finite params (alpha, sx, sy)", fn, i);
-        g_last_error = buf;
-        w.release(stream);
-        return RA_ERR_ARG;
-    }
-    return RA_OK;
-}
-
-// particles per chunk of ra_wiener_accumulate / ra_wiener_score: the spectra and aligned images of one chunk fit the scratch budget
-static int wn_chunk(int n, size_t ph, int npix)
-{
-    return (int)std::max<size_t>(1, std::min<size_t>((size_t)n, WN_SCRATCH_BYTES / (ph * sizeof(float2) + (size_t)npix * sizeof(float))));
-}
-
-extern "C" int ra_wiener_accumulate(const float *d_images, int n, int nx, const ra_result *d_params, const float *h_ctf, int pad,
-                                    int flipped, int k, float *d_num, float *d_den, int *d_counts, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 0 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || (flipped != 0 && flipped != 1) || k < 1 || k > 1024) {
-        g_last_error = "ra_wiener_accumulate: need n >= 0, 2 <= nx <= 1024, pad and flipped 0 or 1, 1 <= k <= 1024";
-        return RA_ERR_ARG;
-    }
-    if (n == 0) return RA_OK;
-    if (!d_images || !d_params || !h_ctf || !d_num || !d_den || !d_counts) {
-        g_last_error = "ra_wiener_accumulate: null argument";
-        return RA_ERR_ARG;
-    }
-    if (!pf_rows_ok("ra_wiener_accumulate", h_ctf, n)) return RA_ERR_ARG;
-    const PfPlan pl = pf_make_plan(nx, pad);
-    if (pl.nb < 1) { g_last_error = "ra_wiener_accumulate: no plan for this box"; return RA_ERR_ARG; }
-    const int P = pl.P, H = pl.H, npix = nx * nx;
-    const size_t ph = (size_t)P * H;
-
-    // 1. classes, finiteness and CTF constants on the device; the verdict and the classes come back before anything is summed
-    WnPrep prep;
-    const int prc = wn_prepare("ra_wiener_accumulate", d_params, h_ctf, n, nx, P, k, stream, prep);
-    if (prc != RA_OK) return prc;
-    const std::vector<int> &lab = prep.lab;
-    WnCtf *d_cst = prep.d_cst;
-    auto release = [&]() { prep.release(stream); };
-    hipError_t he = hipSuccess;
-
-    // 2. chunks within the scratch budget; per chunk the members of every class in particle order, cut into runs so that the
-    //    reduce has enough workgroups (element blocks x runs ~ WN_BLOCKS_TARGET); a class of several runs gets partial slots
-    const int eblk = (int)((ph + WN_THREADS - 1) / WN_THREADS);
-    const int T = std::max(1, std::min(WN_MAX_RUNS, WN_BLOCKS_TARGET / eblk));
-    const int C = wn_chunk(n, ph, npix);
-    std::vector<int> perm(n);
-    std::vector<WnRun> runs;
-    std::vector<int4> segs;
-    std::vector<int> run0, seg0;        // per chunk: first run / seg
-    std::vector<int> start(k + 1);
-    int slots = 0;
-    for (int c0 = 0; c0 < n; c0 += C) {
-        const int cnt = std::min(C, n - c0), L = (cnt + T - 1) / T;
-        run0.push_back((int)runs.size());
-        seg0.push_back((int)segs.size());
-        std::fill(start.begin(), start.end(), 0);
-        for (int i = 0; i < cnt; i++) start[lab[c0 + i] + 1]++;
-        for (int j = 0; j < k; j++) start[j + 1] += start[j];
-        std::vector<int> fill(start.begin(), start.end() - 1);
-        for (int i = 0; i < cnt; i++) perm[c0 + fill[lab[c0 + i]]++] = i;
-        int slot = 0;
-        for (int j = 0; j < k; j++) {
-            const int b = start[j], e = start[j + 1], s = e - b;
-            if (s == 0) continue;
-            if (s <= L) { runs.push_back(WnRun{j, b, e, -1}); continue; }
-            const int s0 = slot;
-            for (int r = b; r < e; r += L) runs.push_back(WnRun{j, r, std::min(e, r + L), slot++});
-            segs.push_back(make_int4(j, s0, slot, s));
-        }
-        slots = std::max(slots, slot);
-    }
-    run0.push_back((int)runs.size());
-    seg0.push_back((int)segs.size());
-
-    // 3. per chunk: rot_shift2D, forward transforms, reduce, combine
-    float *d_al = nullptr, *d_pden = nullptr;
-    float2 *d_spec = nullptr, *d_gscr = nullptr, *d_pnum = nullptr;
-    int *d_perm = nullptr;
-    WnRun *d_runs = nullptr;
-    int4 *d_segs = nullptr;
-    bool fixed = false;
-    const void *fk = wn_forward_fn(nx, pad, pl, &fixed);
-    const int fgrid = pl.gblk ? pf_gblk_grid(pl, C) : 0;
-    if (const int rcl = raise_dynamic_lds(nullptr, fk, "wn_forward_kernel", (size_t)pl.lds)) { release(); return rcl; }
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_al, (size_t)C * npix * sizeof(float), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_spec, (size_t)C * ph * sizeof(float2), stream);
-    if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)fgrid * nx * H * sizeof(float2), stream);
-    if (he == hipSuccess && slots) he = hipMallocAsync((void **)&d_pnum, (size_t)slots * ph * sizeof(float2), stream);
-    if (he == hipSuccess && slots) he = hipMallocAsync((void **)&d_pden, (size_t)slots * ph * sizeof(float), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_perm, (size_t)n * sizeof(int), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_runs, runs.size() * sizeof(WnRun), stream);
-    if (he == hipSuccess && !segs.empty()) he = hipMallocAsync((void **)&d_segs, segs.size() * sizeof(int4), stream);
-    // pageable host sources: hipMemcpyAsync stages them before it returns
-    if (he == hipSuccess) he = hipMemcpyAsync(d_perm, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess) he = hipMemcpyAsync(d_runs, runs.data(), runs.size() * sizeof(WnRun), hipMemcpyHostToDevice, stream);
-    if (he == hipSuccess && !segs.empty()) he = hipMemcpyAsync(d_segs, segs.data(), segs.size() * sizeof(int4), hipMemcpyHostToDevice, stream);
-    int rc = RA_OK;
-    for (int c = 0, c0 = 0; c0 < n && he == hipSuccess && rc == RA_OK; c++, c0 += C) {
-        int cnt = std::min(C, n - c0);
-        rc = ra_rot_shift2d(d_images + (size_t)c0 * npix, cnt, nx, d_params + c0, d_al, stream);
-        if (rc != RA_OK) break;
-        const float *al = d_al;
-        void *args_fixed[] = {&al, &cnt, &d_spec, &d_gscr};
-        PfPlan pl_arg = pl;
-        void *args_plan[] = {&al, &cnt, &d_spec, &pl_arg, &d_gscr};
-        he = hipLaunchKernel(fk, dim3(pl.gblk ? std::min(fgrid, cnt) : cnt), dim3(PF_THREADS), fixed ? args_fixed : args_plan, pl.lds, stream);
-        if (he == hipSuccess) he = hipGetLastError();
-        const int nrun = run0[c + 1] - run0[c], nseg = seg0[c + 1] - seg0[c];
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(wn_reduce_kernel, dim3(eblk, nrun), dim3(WN_THREADS), 0, stream, (const float2 *)d_spec, P, H,
-                               (const WnRun *)(d_runs + run0[c]), (const int *)(d_perm + c0), (const WnCtf *)(d_cst + c0), flipped,
-                               (float2 *)d_num, d_den, d_counts, d_pnum, d_pden);
-            he = hipGetLastError();
-        }
-        if (he == hipSuccess && nseg) {
-            hipLaunchKernelGGL(wn_combine_kernel, dim3(eblk, nseg), dim3(WN_THREADS), 0, stream, P, H, (const int4 *)(d_segs + seg0[c]),
-                               (const float2 *)d_pnum, (const float *)d_pden, (float2 *)d_num, d_den, d_counts);
-            he = hipGetLastError();
-        }
-    }
-    for (void *p : {(void *)d_segs, (void *)d_runs, (void *)d_perm, (void *)d_pden, (void *)d_pnum, (void *)d_gscr, (void *)d_spec, (void *)d_al})
-        if (p) (void)hipFreeAsync(p, stream);
-    release();
-    if (rc != RA_OK) return rc;
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_accumulate", he);
-}
-
-// a finalize kernel's launch: one workgroup per class, or, when the plan keeps its block in global scratch, a grid of scratch
-// blocks that loops over the classes; args(pl_arg, d_gscr) gives the kernel's argument pointers
-template <class Args>
-static int wn_finalize_launch(const char *what, const PfPlan &pl, const void *fk, int k, hipStream_t stream, Args args)
-{
-    if (const int rc = raise_dynamic_lds(nullptr, fk, what, (size_t)pl.lds)) return rc;
-    hipError_t he = hipSuccess;
-    const int grid = pl.gblk ? pf_gblk_grid(pl, k) : k;
-    float2 *d_gscr = nullptr;
-    if (pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)grid * pl.nx * pl.H * sizeof(float2), stream);
-    if (he == hipSuccess) {
-        PfPlan pl_arg = pl;
-        std::vector<void *> a = args(pl_arg, d_gscr);
-        he = hipLaunchKernel(fk, dim3(grid), dim3(PF_THREADS), a.data(), pl.lds, stream);
-        if (he == hipSuccess) he = hipGetLastError();
-    }
-    if (d_gscr) (void)hipFreeAsync(d_gscr, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error(what, he);
-}
-
-extern "C" int ra_wiener_finalize(const float *d_num, const float *d_den, const int *d_counts, int k, int nx, int pad, float snr,
-                                  int min_count, float *d_out, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (k < 1 || k > 1024 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || !(snr > 0.f) || !std::isfinite(snr)) {
-        g_last_error = "ra_wiener_finalize: need 1 <= k <= 1024, 2 <= nx <= 1024, pad 0 or 1 and a finite snr > 0";
-        return RA_ERR_ARG;
-    }
-    if (!d_num || !d_den || !d_counts || !d_out) { g_last_error = "ra_wiener_finalize: null argument"; return RA_ERR_ARG; }
-    const PfPlan pl = pf_make_plan(nx, pad);
-    if (pl.nb < 1) { g_last_error = "ra_wiener_finalize: no plan for this box"; return RA_ERR_ARG; }
-    const void *fk = pl.gblk ? (const void *)wn_finalize_kernel<true> : (const void *)wn_finalize_kernel<false>;
-    const float2 *num = (const float2 *)d_num;
-    float inv_snr = 1.0f / snr;
-    return wn_finalize_launch("ra_wiener_finalize", pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
-        return {&num, &d_den, &d_counts, &k, &inv_snr, &min_count, &d_out, &pl_arg, &d_gscr};
-    });
-}
-
-// ---- half-set FRC and SSNR-weighted averages (ralign_wiener.h)
-
-extern "C" int ra_wiener_frc(const float *d_num2, const float *d_den2, const int *d_counts2, int k, int nx, int pad, float snr,
-                             int min_count, float ssnr_floor, double *d_frc, float *d_reg, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (k < 1 || k > 512 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || !(snr > 0.f) || !std::isfinite(snr) ||
-        !(ssnr_floor > 0.f) || !std::isfinite(ssnr_floor)) {
-        g_last_error = "ra_wiener_frc: need 1 <= k <= 512, 2 <= nx <= 1024, pad 0 or 1, a finite snr > 0 and a finite ssnr_floor > 0";
-        return RA_ERR_ARG;
-    }
-    if (!d_num2 || !d_den2 || !d_counts2 || !d_frc || !d_reg) { g_last_error = "ra_wiener_frc: null argument"; return RA_ERR_ARG; }
-    const int P = pad ? 2 * nx : nx, S = P / 2 + 1;
-    // row blocks of `rows` rows, about WN_FRC_BLOCKS workgroups over all classes, none of them empty
-    const int want = std::max(1, std::min(std::min(P, WN_FRC_MAX_ROW_BLOCKS), WN_FRC_BLOCKS / k));
-    const int rows = (P + want - 1) / want, nb = (P + rows - 1) / rows;
-    const int threads = std::min(WN_THREADS, (S + 63) / 64 * 64);
-    double *d_part = nullptr;
-    hipError_t he = hipMallocAsync((void **)&d_part, (size_t)k * nb * 5 * S * sizeof(double), stream);
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(wn_frc_rows_kernel, dim3(nb, k), dim3(threads), 0, stream, (const float2 *)d_num2, d_den2, P, rows,
-                           1.0 / (double)snr, d_part);
-        he = hipGetLastError();
-    }
-    if (he == hipSuccess) {
-        hipLaunchKernelGGL(wn_frc_combine_kernel, dim3((S + WN_THREADS - 1) / WN_THREADS, k), dim3(WN_THREADS), 0, stream,
-                           (const double *)d_part, nb, S, d_counts2, min_count, ssnr_floor, d_frc, d_reg);
-        he = hipGetLastError();
-    }
-    if (d_part) (void)hipFreeAsync(d_part, stream);
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_frc", he);
-}
-
-extern "C" int ra_wiener_finalize_ssnr(const float *d_num2, const float *d_den2, const int *d_counts2, const float *d_reg, int k, int nx,
-                                       int pad, int min_count, float *d_out, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (k < 1 || k > 512 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1)) {
-        g_last_error = "ra_wiener_finalize_ssnr: need 1 <= k <= 512, 2 <= nx <= 1024 and pad 0 or 1";
-        return RA_ERR_ARG;
-    }
-    if (!d_num2 || !d_den2 || !d_counts2 || !d_reg || !d_out) {
-        g_last_error = "ra_wiener_finalize_ssnr: null argument";
-        return RA_ERR_ARG;
-    }
-    const PfPlan pl = pf_make_plan(nx, pad);
-    if (pl.nb < 1) { g_last_error = "ra_wiener_finalize_ssnr: no plan for this box"; return RA_ERR_ARG; }
-    const void *fk = pl.gblk ? (const void *)wn_finalize_ssnr_kernel<true> : (const void *)wn_finalize_ssnr_kernel<false>;
-    const float2 *num2 = (const float2 *)d_num2;
-    return wn_finalize_launch("ra_wiener_finalize_ssnr", pl, fk, k, stream, [&](PfPlan &pl_arg, float2 *&d_gscr) -> std::vector<void *> {
-        return {&num2, &d_den2, &d_counts2, &d_reg, &k, &min_count, &d_out, &pl_arg, &d_gscr};
-    });
-}
-
-// ---- per-particle agreement scores (ralign_wiener.h)
-
-extern "C" int ra_wiener_score(const float *d_images, int n, int nx, const ra_result *d_params, const float *h_ctf, int pad, int flipped,
-                               int k, const float *d_num, const float *d_den, const int *d_counts, float snr, const float *d_reg,
-                               int leave_one_out, int s_lo, int s_hi, double *d_sums, void *hip_stream)
-{
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 0 || nx < 2 || nx > 1024 || (pad != 0 && pad != 1) || (flipped != 0 && flipped != 1) || k < 1 || k > 1024 ||
-        (leave_one_out != 0 && leave_one_out != 1)) {
-        g_last_error = "ra_wiener_score: need n >= 0, 2 <= nx <= 1024, pad, flipped and leave_one_out 0 or 1, 1 <= k <= 1024";
-        return RA_ERR_ARG;
-    }
-    if (s_lo < 0 || s_lo > s_hi || s_hi > (pad ? 2 * nx : nx) / 2) {
-        g_last_error = "ra_wiener_score: need 0 <= s_lo <= s_hi <= P/2";
-        return RA_ERR_ARG;
-    }
-    if (d_reg ? k > 512 : (!(snr > 0.f) || !std::isfinite(snr))) {
-        g_last_error = "ra_wiener_score: need a finite snr > 0, or a per-shell term with k <= 512";
-        return RA_ERR_ARG;
-    }
-    if (n == 0) return RA_OK;
-    if (!d_images || !d_params || !h_ctf || !d_num || !d_den || !d_counts || !d_sums) {
-        g_last_error = "ra_wiener_score: null argument";
-        return RA_ERR_ARG;
-    }
-    if (!pf_rows_ok("ra_wiener_score", h_ctf, n)) return RA_ERR_ARG;
-    const PfPlan pl = pf_make_plan(nx, pad);
-    if (pl.nb < 1) { g_last_error = "ra_wiener_score: no plan for this box"; return RA_ERR_ARG; }
-    const int P = pl.P, H = pl.H, npix = nx * nx;
-    const size_t ph = (size_t)P * H;
-
-    // 1. as ra_wiener_accumulate: the verdict on labels and params before anything is written
-    WnPrep prep;
-    const int prc = wn_prepare("ra_wiener_score", d_params, h_ctf, n, nx, P, k, stream, prep);
-    if (prc != RA_OK) return prc;
-
-    // 2. the accumulate's chunks; in each the particles in class order (stable), so that a class's sums are read while they are hot
-    const int C = wn_chunk(n, ph, npix);
-    std::vector<int> perm(n), start(k + 1);
-    for (int c0 = 0; c0 < n; c0 += C) {
-        const int cnt = std::min(C, n - c0);
-        std::fill(start.begin(), start.end(), 0);
-        for (int i = 0; i < cnt; i++) start[prep.lab[c0 + i] + 1]++;
-        for (int j = 0; j < k; j++) start[j + 1] += start[j];
-        for (int i = 0; i < cnt; i++) perm[c0 + start[prep.lab[c0 + i]]++] = i;
-    }
-
-    // 3. per chunk: rot_shift2D, forward transforms, scores
-    float *d_al = nullptr;
-    float2 *d_spec = nullptr, *d_gscr = nullptr;
-    int *d_perm = nullptr;
-    bool fixed = false;
-    const void *fk = wn_forward_fn(nx, pad, pl, &fixed);
-    const int fgrid = pl.gblk ? pf_gblk_grid(pl, C) : 0;
-    if (const int rcl = raise_dynamic_lds(nullptr, fk, "wn_forward_kernel", (size_t)pl.lds)) { prep.release(stream); return rcl; }
-    hipError_t he = hipMallocAsync((void **)&d_al, (size_t)C * npix * sizeof(float), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_spec, (size_t)C * ph * sizeof(float2), stream);
-    if (he == hipSuccess && pl.gblk) he = hipMallocAsync((void **)&d_gscr, (size_t)fgrid * nx * H * sizeof(float2), stream);
-    if (he == hipSuccess) he = hipMallocAsync((void **)&d_perm, (size_t)n * sizeof(int), stream);
-    // pageable host source: hipMemcpyAsync stages it before it returns
-    if (he == hipSuccess) he = hipMemcpyAsync(d_perm, perm.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, stream);
-    const double tau = d_reg ? 0.0 : 1.0 / (double)snr;
-    int rc = RA_OK;
-    for (int c0 = 0; c0 < n && he == hipSuccess && rc == RA_OK; c0 += C) {
-        int cnt = std::min(C, n - c0);
-        rc = ra_rot_shift2d(d_images + (size_t)c0 * npix, cnt, nx, d_params + c0, d_al, stream);
-        if (rc != RA_OK) break;
-        const float *al = d_al;
-        void *args_fixed[] = {&al, &cnt, &d_spec, &d_gscr};
-        PfPlan pl_arg = pl;
-        void *args_plan[] = {&al, &cnt, &d_spec, &pl_arg, &d_gscr};
-        he = hipLaunchKernel(fk, dim3(pl.gblk ? std::min(fgrid, cnt) : cnt), dim3(PF_THREADS), fixed ? args_fixed : args_plan, pl.lds, stream);
-        if (he == hipSuccess) he = hipGetLastError();
-        if (he == hipSuccess) {
-            hipLaunchKernelGGL(wn_score_kernel, dim3(cnt), dim3(WN_THREADS), 0, stream, (const float2 *)d_spec, P, H,
-                               (const int *)(d_perm + c0), (const int *)(prep.d_lab + c0), (const WnCtf *)(prep.d_cst + c0), flipped,
-                               (const float2 *)d_num, d_den, d_counts, tau, d_reg, leave_one_out, s_lo, s_hi, d_sums + (size_t)c0 * 3);
-            he = hipGetLastError();
-        }
-    }
-    for (void *p : {(void *)d_perm, (void *)d_gscr, (void *)d_spec, (void *)d_al})
-        if (p) (void)hipFreeAsync(p, stream);
-    prep.release(stream);
-    if (rc != RA_OK) return rc;
-    return he == hipSuccess ? RA_OK : sdr_launch_error("ra_wiener_score", he);
+    return he == hipSuccess ? RA_OK : hip_error("ra_rot_shift2d", he);
 }

@@ -6,8 +6,7 @@ cd "$(dirname "$0")/../.."
 root=$(pwd)
 export TMPDIR=/tmp
 mkdir -p gpurun_out
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DRALIGN_PROFILE_SWITCHES -Iinclude \
-    -o gpurun_out/libralign_prof.so cryo_ralib_amd/csrc/ralign_engine.hip || exit 1
+python3 -m cryo_ralib_amd.build -DRALIGN_PROFILE_SWITCHES -o $_/libralign_prof.so || exit 1      # $_: the directory made above
 export RALIGN_LIB=$PWD/gpurun_out/libralign_prof.so
 for m in ${MASKS:-0 4 8 16 20}; do
     export RALIGN_DEBUG=$m

@@ -4,7 +4,7 @@
 set -e
 cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DRALIGN_PROFILE_SWITCHES -Iinclude -o gpurun_out/libralign_prof.so cryo_ralib_amd/csrc/ralign_engine.hip
+python3 -m cryo_ralib_amd.build -DRALIGN_PROFILE_SWITCHES -o $_/libralign_prof.so      # $_: the directory made above
 for w in 8 4 6; do
   for m in 0 1; do       # RALIGN_DEBUG=1: no inverse transforms (contraction alone)
     echo "waves $w, RALIGN_DEBUG=$m"

@@ -3,7 +3,7 @@
 set -e
 cd "$(dirname "$0")/../.."
 mkdir -p gpurun_out
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DRALIGN_PROFILE_SWITCHES -Iinclude -o gpurun_out/libralign_prof.so cryo_ralib_amd/csrc/ralign_engine.hip
+python3 -m cryo_ralib_amd.build -DRALIGN_PROFILE_SWITCHES -o $_/libralign_prof.so      # $_: the directory made above
 for c in ${CHUNKS:-4 2 1 8 16}; do
     echo "chunks $c"
     RALIGN_ZONE_CHUNKS=$c RALIGN_LIB=$PWD/gpurun_out/libralign_prof.so python bench.py --workload largebox --steps 2 --warmup 1 --particles 2640 --no-cpu-baseline --no-parity --no-pcie --function none 2>&1 | tail -1 |

@@ -5,8 +5,7 @@
 set -e
 root=$(cd "$(dirname "$0")/.." && pwd)
 mkdir -p $root/gpurun_out
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DRALIGN_PROFILE_SWITCHES -I$root/include \
-    -o $root/gpurun_out/libralign_prof.so $root/cryo_ralib_amd/csrc/ralign_engine.hip
+PYTHONPATH=$root python3 -m cryo_ralib_amd.build -DRALIGN_PROFILE_SWITCHES -o $_/libralign_prof.so      # $_: the directory made above
 export TMPDIR=/tmp RALIGN_LIB=$root/gpurun_out/libralign_prof.so
 cd /tmp
 for m in 0 16 2 4; do

@@ -5,8 +5,7 @@ set -e
 cd "$(dirname "$0")/.."
 root=$PWD
 mkdir -p gpurun_out
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DRALIGN_PROFILE_SWITCHES -Iinclude \
-    -o gpurun_out/libralign_prof.so cryo_ralib_amd/csrc/ralign_engine.hip
+python3 -m cryo_ralib_amd.build -DRALIGN_PROFILE_SWITCHES -o $_/libralign_prof.so      # $_: the directory made above
 export TMPDIR=/tmp
 export RALIGN_LIB=$root/gpurun_out/libralign_prof.so
 cd /tmp
