@@ -80,6 +80,7 @@ EXPORTED_SYMBOLS = [
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
+    "ra_kmeans_silhouette", "ra_kmeans_dispersion",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
 ]
 
@@ -202,6 +203,8 @@ def load_library(path=None):
     L.ra_kmeans_lloyd.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, vp]
     L.ra_kmeans_search.argtypes = [vp, ci, vp, ci, vp, vp]
     L.ra_kmeans_seed.argtypes = [vp, ci, ci, vp, ci, vp, ci, vp, vp]
+    L.ra_kmeans_silhouette.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
+    L.ra_kmeans_dispersion.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -340,6 +343,42 @@ def kmeans(X, n_clusters, **kw):
     """k-means of X [n][d] (kmeans.kmeans): KMeansResult with labels, centers, inertia, n_iter, init_indices."""
     from . import kmeans as _kmeans
     return _kmeans.kmeans(X, n_clusters, **kw)
+
+
+def silhouette_samples(X, labels, **kw):
+    """Silhouette coefficient of every sample, float64 [n] (kmeans.silhouette_samples)."""
+    from . import kmeans as _kmeans
+    return _kmeans.silhouette_samples(X, labels, **kw)
+
+
+def silhouette_score(X, labels, **kw):
+    """Mean silhouette coefficient, optionally of sklearn's subsample (kmeans.silhouette_score)."""
+    from . import kmeans as _kmeans
+    return _kmeans.silhouette_score(X, labels, **kw)
+
+
+def calinski_harabasz_score(X, labels, **kw):
+    """Calinski-Harabasz index (kmeans.calinski_harabasz_score)."""
+    from . import kmeans as _kmeans
+    return _kmeans.calinski_harabasz_score(X, labels, **kw)
+
+
+def davies_bouldin_score(X, labels, **kw):
+    """Davies-Bouldin index (kmeans.davies_bouldin_score)."""
+    from . import kmeans as _kmeans
+    return _kmeans.davies_bouldin_score(X, labels, **kw)
+
+
+def validity(X, labels, **kw):
+    """Silhouette (overall and per class), Calinski-Harabasz, Davies-Bouldin and cluster sizes (kmeans.validity)."""
+    from . import kmeans as _kmeans
+    return _kmeans.validity(X, labels, **kw)
+
+
+def kmeans_sweep(X, ks, **kw):
+    """k-means and the validity scores for every k of ks on one device copy of X (kmeans.sweep)."""
+    from . import kmeans as _kmeans
+    return _kmeans.sweep(X, ks, **kw)
 
 
 def _check(rc, what):

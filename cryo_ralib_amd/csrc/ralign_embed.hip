@@ -1,7 +1,8 @@
-// t-SNE and k-means of 2SDR factors (ralign_tsne.h, ralign_kmeans.h): the engine-less ra_tsne_* and ra_kmeans_* entry points of
-// libralign_hip.so, each on the caller's stream.
+// t-SNE, k-means and cluster validity of 2SDR factors (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h): the engine-less
+// ra_tsne_* and ra_kmeans_* entry points of libralign_hip.so, each on the caller's stream.
 #include "ralign_host.h"
 #include "ralign_kmeans.h"
+#include "ralign_validity.h"
 
 using namespace ralign;
 
@@ -272,4 +273,73 @@ extern "C" int ra_kmeans_seed(const float *d_x, int n, int d, const int *d_cand,
     RA_LAUNCH(he, km_pick_kernel, dim3(1), dim3(256), 0, stream, (const double *)part, nb, d_cand, m, n, d_out);
     RA_LAUNCH(he, km_commit_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, (const double *)d_out, first, d_closest);
     return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_seed", he);
+}
+
+// ---- cluster validity (ralign_validity.h)
+
+// the stable member lists of the labels: count [k], start [k], run0 [k + 1] (runs of L members), members [n]
+static hipError_t km_member_lists(const int *labels, int n, int k, int L, int *bcnt, int *cnt, int *start, int *run0, int *mem, hipStream_t stream)
+{
+    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK;
+    hipLaunchKernelGGL(km_hist_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, labels, n, k, bcnt);
+    hipError_t he = hipGetLastError();
+    RA_LAUNCH(he, km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt);
+    RA_LAUNCH(he, km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, run0);
+    RA_LAUNCH(he, km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, labels, n, k, (const int *)bcnt, (const int *)start, mem);
+    return he;
+}
+
+extern "C" int ra_kmeans_silhouette(const float *d_x, int n, int d, const int *d_labels, int k, double *d_out, int *d_nearest, void *hip_stream)
+{
+    if (n < 3 || n > VAL_MAX_N || d < 1 || d > KM_MAX_D || k < 2 || k > KM_MAX_K)
+        return arg_error("ra_kmeans_silhouette: need 3 <= n <= 262144, 1 <= d <= 2048 and 2 <= k <= 256");
+    if (!d_x || !d_labels || !d_out || !d_nearest) return arg_error("ra_kmeans_silhouette: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, cap = n + k * VAL_TC;
+    KmScratch S;
+    const size_t o_bcnt = S.take((size_t)nb * k * 4), o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4);
+    const size_t o_run0 = S.take((size_t)(k + 1) * 4), o_mem = S.take((size_t)n * 4), o_pstart = S.take((size_t)(k + 1) * 4);
+    const size_t o_cols = S.take((size_t)cap * 4);
+    StreamScratch scratch(stream);
+    if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_silhouette", scratch.status());
+    int *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start), *mem = S.at<int>(o_mem), *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols);
+    hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);          // every column invalid (-1) until a member lands on it
+    if (he == hipSuccess) he = km_member_lists(d_labels, n, k, km_run_len(n), S.at<int>(o_bcnt), cnt, start, S.at<int>(o_run0), mem, stream);
+    RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, pstart);
+    RA_LAUNCH(he, val_cols_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt,
+              (const int *)pstart, n, k, cap, cols);
+    ValSilArgs a;
+    a.x = d_x; a.labels = d_labels; a.cols = cols; a.count = cnt; a.pstart = pstart; a.n = n; a.d = d; a.k = k;
+    a.out = d_out; a.nearest = d_nearest;
+    RA_LAUNCH(he, val_silhouette_kernel, dim3((n + VAL_TR - 1) / VAL_TR), dim3(256), 0, stream, a);
+    return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_silhouette", he);
+}
+
+extern "C" int ra_kmeans_dispersion(const float *d_x, int n, int d, const int *d_labels, int k, double *d_centroids, int *d_counts, double *d_sq,
+                                    double *d_abs, void *hip_stream)
+{
+    if (n < 1 || n > KM_MAX_N || d < 1 || d > KM_MAX_D || k < 1 || k > KM_MAX_K)
+        return arg_error("ra_kmeans_dispersion: need 1 <= n <= 4194304, 1 <= d <= 2048 and 1 <= k <= 256");
+    if (!d_x || !d_labels || !d_centroids || !d_counts || !d_sq || !d_abs) return arg_error("ra_kmeans_dispersion: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, L = km_run_len(n), rmax = (n + L - 1) / L + k;
+    KmScratch S;
+    const size_t o_bcnt = S.take((size_t)nb * k * 4), o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4);
+    const size_t o_run0 = S.take((size_t)(k + 1) * 4), o_mem = S.take((size_t)n * 4), o_part = S.take((size_t)rmax * d * 8);
+    const size_t o_sums = S.take((size_t)k * d * 8), o_wt = S.take((size_t)k * 8), o_dist = S.take((size_t)n * 8);
+    StreamScratch scratch(stream);
+    if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_dispersion", scratch.status());
+    int *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start), *run0 = S.at<int>(o_run0), *mem = S.at<int>(o_mem);
+    double *part = S.at<double>(o_part), *sums = S.at<double>(o_sums), *dist = S.at<double>(o_dist);
+    hipError_t he = km_member_lists(d_labels, n, k, L, S.at<int>(o_bcnt), cnt, start, run0, mem, stream);
+    RA_LAUNCH(he, km_runsum_kernel, dim3(rmax), dim3(256), 0, stream, d_x, n, d, k, L, (const int *)mem, (const int *)cnt, (const int *)start,
+              (const int *)run0, part);
+    RA_LAUNCH(he, km_combine_kernel, dim3(k), dim3(256), 0, stream, (const double *)part, d, (const int *)cnt, (const int *)run0, sums,
+              S.at<double>(o_wt));
+    RA_LAUNCH(he, val_centroid_kernel, dim3(k), dim3(256), 0, stream, (const double *)sums, (const int *)cnt, d, d_centroids, d_counts);
+    RA_LAUNCH(he, km_point_dist_kernel, dim3(d > KM_SMALL_D ? (n + 3) / 4 : (n + 255) / 256), dim3(256), 0, stream, d_x, n, d,
+              (const double *)d_centroids, k, d_labels, dist);
+    RA_LAUNCH(he, val_disp_kernel, dim3(k), dim3(256), 0, stream, (const double *)dist, (const int *)mem, (const int *)cnt, (const int *)start, n,
+              d_sq, d_abs);
+    return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_dispersion", he);
 }

@@ -3,6 +3,7 @@
     python -m cryo_ralib_amd.kmeans IN OUT.npz --k K [--key factors] [--init k-means++|random|FILE.npy] [--n_init auto|N]
                                     [--max_iter 300] [--tol 1e-4] [--seed S] [--backend device|numpy] [--truth FILE]
                                     [--stack STACK --params PARAMS --ou R --averages REFS.{hdf,mrcs,npy}]
+                                    [--scores] [--sweep K1,K2,...|LO:HI[:STEP]] [--sample_size N]
 
 IN is the OUT.npz of the sdr tool (--key factors) or of the tsne tool (--key embedding), or an [n][d] .npy.  --truth takes an int
 .npy or a params.txt (its class column); OUT.npz then also holds purity, c_purity and contingency.  --averages writes the k class
@@ -29,6 +30,16 @@ Every distance, sum and update runs in the HIP kernels behind ra_kmeans_* (csrc/
 count and the centre shift once per iteration and the potential once per seeded centre.  backend="numpy" runs the same loop in
 float64 numpy: it is the CPU checker.  contingency_matrix, purity_score and c_purity_score restate the reference's utils_ralib
 (sklearn is not a run-time dependency).
+
+Cluster validity without ground truth (sklearn.metrics with metric="euclidean"): silhouette_samples,
+silhouette_score (with sklearn's sample_size / random_state subsample), calinski_harabasz_score, davies_bouldin_score, validity
+(all of them and the per-class silhouette) and sweep (k-means and the scores for every k of a list; best_k is the largest
+silhouette, the smaller k on ties).  Only clusters with members count; their number m must satisfy 2 <= m <= n - 1 (ValueError
+with sklearn's message otherwise).  The silhouette's n^2 distances come from ra_kmeans_silhouette (f32 differences, double sums),
+the centroids and dispersions from ra_kmeans_dispersion; the silhouette takes 3 <= n <= 262144 and 2 <= k <= 256, more points
+only with sample_size <= 262144.  --scores adds silhouette, class_silhouette, silhouette_samples (nan outside the sample),
+calinski_harabasz and davies_bouldin to OUT.npz and prints one line per class; --sweep makes --k optional, prints the table
+k / inertia / silhouette / CH / DB, stores it as sweep (and best_k) and writes the result of best_k, or of --k if given.
 
 Domain: 1 <= k <= min(256, n), 1 <= n <= 4194304, 1 <= d <= 2048, max_iter >= 1, tol >= 0, finite input.  Anything else raises
 KMeansError before anything is launched.
@@ -451,6 +462,292 @@ def c_purity_score(y_true, y_pred):
     return float(np.sum(np.amax(M, axis=1)) / np.sum(M))
 
 
+# ---- cluster validity without ground truth (sklearn.metrics silhouette_*, calinski_harabasz_score, davies_bouldin_score)
+
+SIL_MAX_N = 262144      # rows of one silhouette evaluation (n^2 pair distances); larger n needs sample_size
+
+
+class ValidityResult:
+    """silhouette (mean of the evaluated samples), class_silhouette float64 [k] (mean per cluster, nan for an id without evaluated
+    members), calinski_harabasz, davies_bouldin, counts int64 [k] (of all n points), samples float64 [n] (s_i; nan for rows outside
+    the sample) and sample_indices (None without sample_size)"""
+
+    def __init__(self, silhouette, class_silhouette, calinski_harabasz, davies_bouldin, counts, samples, sample_indices):
+        self.silhouette, self.class_silhouette, self.calinski_harabasz = silhouette, class_silhouette, calinski_harabasz
+        self.davies_bouldin, self.counts, self.samples, self.sample_indices = davies_bouldin, counts, samples, sample_indices
+
+
+class SweepRow:
+    """one k of a sweep: k, inertia, n_iter, silhouette, calinski_harabasz, davies_bouldin, labels int32 [n], centers float64 [k][d]"""
+
+    def __init__(self, k, fit, val):
+        self.k, self.inertia, self.n_iter, self.labels, self.centers = int(k), fit.inertia, fit.n_iter, fit.labels, fit.centers
+        self.fit, self.validity = fit, val
+        self.silhouette, self.calinski_harabasz, self.davies_bouldin = val.silhouette, val.calinski_harabasz, val.davies_bouldin
+        self.class_silhouette, self.counts = val.class_silhouette, val.counts
+
+
+class SweepResult:
+    """rows (one SweepRow per k, in the order of ks) and best_k: the k of the largest silhouette, the smaller k on ties"""
+
+    def __init__(self, rows):
+        self.rows = rows
+        best = rows[0]
+        for r in rows[1:]:
+            if r.silhouette > best.silhouette or (r.silhouette == best.silhouette and r.k < best.k):
+                best = r
+        self.best_k = best.k
+
+    def row(self, k):
+        return next(r for r in self.rows if r.k == k)
+
+    def table(self):
+        """float64 [len(ks)][5]: k, inertia, silhouette, calinski_harabasz, davies_bouldin"""
+        return np.array([[r.k, r.inertia, r.silhouette, r.calinski_harabasz, r.davies_bouldin] for r in self.rows], np.float64).reshape(-1, 5)
+
+
+def check_number_of_labels(m, n):
+    """sklearn's check: 2 <= m <= n - 1 clusters with members"""
+    if not 1 < m < n:
+        raise ValueError("Number of labels is %d. Valid values are 2 to n_samples - 1 (inclusive)" % m)
+
+
+def _as_labels(labels, n, k):
+    """(int64 [n] labels on the host, k): values in 0 .. k - 1, k = max + 1 when not given"""
+    lab = labels.detach().cpu().numpy() if hasattr(labels, "detach") else np.asarray(labels)
+    if lab.shape != (n,) or not np.issubdtype(lab.dtype, np.integer):
+        raise KMeansError("labels are [%d] integers, got %s %s" % (n, lab.dtype, lab.shape))
+    lab = lab.astype(np.int64)
+    if k is None:
+        k = int(lab.max()) + 1
+    if not (_is_int(k) and 1 <= k <= MAX_K):
+        raise KMeansError("need 1 <= k <= %d, got %r" % (MAX_K, k))
+    if lab.min() < 0 or lab.max() >= k:
+        raise KMeansError("labels are integers in 0 .. k - 1 = %d, got %d .. %d" % (k - 1, lab.min(), lab.max()))
+    return lab, int(k)
+
+
+def _validity_input(X, labels, k, backend):
+    X = _as_input(X, backend)
+    n, d = (int(s) for s in X.shape)
+    if not (1 <= n <= MAX_N and 1 <= d <= MAX_D):
+        raise KMeansError("need 1 <= n <= %d points of 1 <= d <= %d features, got %d x %d" % (MAX_N, MAX_D, n, d))
+    lab, k = _as_labels(labels, n, k)
+    return X, lab, k, n, d
+
+
+def _sample(n, sample_size, random_state):
+    """sklearn's silhouette_score subsample: check_random_state(rs).permutation(n)[:sample_size]; None without sample_size"""
+    if sample_size is None:
+        return None
+    if not (_is_int(sample_size) and 1 <= sample_size):
+        raise KMeansError("sample_size is None or an integer >= 1, got %r" % (sample_size,))
+    return check_random_state(random_state).permutation(n)[:sample_size]
+
+
+def _check_silhouette_domain(n, d, k, lab):
+    if not (3 <= n <= SIL_MAX_N):
+        raise KMeansError("the silhouette takes 3 <= n <= %d points (pass sample_size <= %d for more), got %d" % (SIL_MAX_N, SIL_MAX_N, n))
+    if not (2 <= k <= MAX_K):
+        raise KMeansError("the silhouette takes 2 <= k <= %d, got %d" % (MAX_K, k))
+    check_number_of_labels(int(np.count_nonzero(np.bincount(lab, minlength=k))), n)
+
+
+def _silhouette_numpy(X, lab, k):
+    """(s, a, b, nearest) in float64 from differences: the CPU checker"""
+    X = np.asarray(X, np.float64)
+    n, d = X.shape
+    cnt = np.bincount(lab, minlength=k)
+    H = np.zeros((n, k))
+    H[np.arange(n), lab] = 1.0
+    D = np.empty((n, k))
+    ch = max(1, (1 << 22) // max(1, n * d))
+    for s0 in range(0, n, ch):
+        df = X[s0:s0 + ch, None, :] - X[None, :, :]
+        D[s0:s0 + ch] = np.sqrt(np.sum(df * df, axis=2)) @ H
+    rows = np.arange(n)
+    no = cnt[lab]
+    a = np.where(no > 1, D[rows, lab] / np.maximum(no - 1, 1), 0.0)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        M = np.where(cnt[None, :] > 0, D / cnt[None, :], np.inf)
+    M[rows, lab] = np.inf
+    nearest = np.argmin(M, axis=1)
+    b = M[rows, nearest]
+    mx = np.maximum(a, b)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        sv = np.where((no > 1) & (mx > 0), (b - a) / mx, 0.0)
+    return sv, a, b, nearest.astype(np.int32)
+
+
+def _device_labels(X, lab):
+    import torch
+    return torch.from_numpy(np.ascontiguousarray(lab, np.int32)).to(X.device)
+
+
+def _silhouette_device(X, lab, k):
+    import torch
+    from . import api
+    lib = api.load_library()
+    n, d = (int(s) for s in X.shape)
+    with torch.cuda.device(X.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+        labels = _device_labels(X, lab)
+        out = torch.empty((n, 3), dtype=torch.float64, device=X.device)
+        near = torch.empty(n, dtype=torch.int32, device=X.device)
+        api._check(lib.ra_kmeans_silhouette(_ptr(X), n, d, _ptr(labels), k, _ptr(out), _ptr(near), stream), "ra_kmeans_silhouette")
+        o = out.cpu().numpy()
+        return o[:, 0].copy(), o[:, 1].copy(), o[:, 2].copy(), near.cpu().numpy()
+
+
+def _take(X, idx, backend):
+    if backend == "device":
+        import torch
+        return X.index_select(0, torch.as_tensor(np.asarray(idx, np.int64), device=X.device)).contiguous()
+    return X[idx]
+
+
+def _silhouette(X, lab, k, backend):
+    n, d = (int(s) for s in X.shape)
+    _check_silhouette_domain(n, d, k, lab)
+    _check_finite(X, backend)
+    return _silhouette_device(X, lab, k) if backend == "device" else _silhouette_numpy(X, lab, k)
+
+
+def silhouette_samples(X, labels, k=None, backend="device", details=False):
+    """sklearn's silhouette_samples(metric="euclidean"): float64 [n]; details=True: (s, a, b, nearest) with a the mean distance to
+    the own cluster's other members (0 for a singleton), b the least mean distance to another cluster and nearest its id"""
+    X, lab, k, n, d = _validity_input(X, labels, k, backend)
+    sv, a, b, near = _silhouette(X, lab, k, backend)
+    return (sv, a, b, near) if details else sv
+
+
+def _sampled_silhouette(X, lab, k, sample_size, random_state, backend):
+    """(s of the evaluated rows, their indices or None)"""
+    idx = _sample(int(X.shape[0]), sample_size, random_state)
+    if idx is None:
+        return _silhouette(X, lab, k, backend)[0], None
+    return _silhouette(_take(X, idx, backend), lab[idx], k, backend)[0], idx
+
+
+def silhouette_score(X, labels, k=None, sample_size=None, random_state=None, backend="device"):
+    """sklearn's silhouette_score(metric="euclidean"): the mean of silhouette_samples, over sklearn's subsample when sample_size is
+    given (the cluster-count check then runs on the sample)"""
+    X, lab, k, n, d = _validity_input(X, labels, k, backend)
+    return float(np.mean(_sampled_silhouette(X, lab, k, sample_size, random_state, backend)[0]))
+
+
+def _dispersion(X, lab, k, backend):
+    """(centroids [k][d], counts [k], sum |x - mu_c|^2 [k], sum |x - mu_c| [k]) from the labels, float64"""
+    n, d = (int(s) for s in X.shape)
+    check_number_of_labels(int(np.count_nonzero(np.bincount(lab, minlength=k))), n)
+    _check_finite(X, backend)
+    if backend == "numpy":
+        Xd = np.asarray(X, np.float64)
+        cnt = np.bincount(lab, minlength=k)
+        sums = np.zeros((k, d))
+        np.add.at(sums, lab, Xd)
+        cen = sums / np.maximum(cnt, 1)[:, None]
+        dist = np.sum((Xd - cen[lab]) ** 2, axis=1)
+        return cen, cnt, np.bincount(lab, weights=dist, minlength=k), np.bincount(lab, weights=np.sqrt(dist), minlength=k)
+    import torch
+    from . import api
+    lib = api.load_library()
+    with torch.cuda.device(X.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+        labels = _device_labels(X, lab)
+        cen = torch.empty((k, d), dtype=torch.float64, device=X.device)
+        cnt = torch.empty(k, dtype=torch.int32, device=X.device)
+        sq = torch.empty(k, dtype=torch.float64, device=X.device)
+        ab = torch.empty(k, dtype=torch.float64, device=X.device)
+        api._check(lib.ra_kmeans_dispersion(_ptr(X), n, d, _ptr(labels), k, _ptr(cen), _ptr(cnt), _ptr(sq), _ptr(ab), stream),
+                   "ra_kmeans_dispersion")
+        return cen.cpu().numpy(), cnt.cpu().numpy().astype(np.int64), sq.cpu().numpy(), ab.cpu().numpy()
+
+
+def _ch_db(cen, cnt, sq, ab, n):
+    """(Calinski-Harabasz, Davies-Bouldin) in float64 from the dispersion pass, as sklearn forms them"""
+    nz = cnt > 0
+    m = int(np.count_nonzero(nz))
+    cen, cnt, sq, ab = cen[nz], cnt[nz].astype(np.float64), sq[nz], ab[nz]
+    mu = np.sum(cen * cnt[:, None], axis=0) / n
+    extra, intra = float(np.sum(cnt * np.sum((cen - mu) ** 2, axis=1))), float(np.sum(sq))
+    ch = 1.0 if intra == 0.0 else extra * (n - m) / (intra * (m - 1.0))
+    S = ab / cnt
+    df = cen[:, None, :] - cen[None, :, :]
+    cd = np.sqrt(np.sum(df * df, axis=2))
+    if np.allclose(S, 0) or np.allclose(cd, 0):
+        return ch, 0.0
+    cd[cd == 0] = np.inf
+    return ch, float(np.mean(np.max((S[:, None] + S[None, :]) / cd, axis=1)))
+
+
+def calinski_harabasz_score(X, labels, k=None, backend="device"):
+    """sklearn's calinski_harabasz_score: between- over within-cluster dispersion of the label-derived centroids"""
+    X, lab, k, n, d = _validity_input(X, labels, k, backend)
+    return _ch_db(*_dispersion(X, lab, k, backend), n)[0]
+
+
+def davies_bouldin_score(X, labels, k=None, backend="device"):
+    """sklearn's davies_bouldin_score: mean over the clusters of the worst (S_c + S_c') / |mu_c - mu_c'|"""
+    X, lab, k, n, d = _validity_input(X, labels, k, backend)
+    return _ch_db(*_dispersion(X, lab, k, backend), n)[1]
+
+
+def validity(X, labels, k=None, sample_size=None, random_state=None, backend="device"):
+    """ValidityResult of the labels: the silhouette (over sklearn's subsample when sample_size is given), its mean per cluster,
+    the Calinski-Harabasz and Davies-Bouldin indices (always of all n points) and the cluster sizes"""
+    X, lab, k, n, d = _validity_input(X, labels, k, backend)
+    sv, idx = _sampled_silhouette(X, lab, k, sample_size, random_state, backend)
+    ch, db = _ch_db(*_dispersion(X, lab, k, backend), n)
+    sl = lab if idx is None else lab[idx]
+    ne = np.bincount(sl, minlength=k)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        cls = np.bincount(sl, weights=sv, minlength=k) / ne
+    cls[ne == 0] = np.nan
+    samples = sv
+    if idx is not None:
+        samples = np.full(n, np.nan)
+        samples[idx] = sv
+    return ValidityResult(float(np.mean(sv)), cls, ch, db, np.bincount(lab, minlength=k), samples, idx)
+
+
+def parse_sweep(text):
+    """the ks of 'K1,K2,...' or 'LO:HI[:STEP]' (HI included): strictly increasing integers >= 2"""
+    try:
+        if ":" in text:
+            p = [int(v) for v in text.split(":")]
+            if len(p) not in (2, 3):
+                raise ValueError(text)
+            step = p[2] if len(p) == 3 else 1
+            ks = list(range(p[0], p[1] + 1, step)) if step >= 1 else []
+        else:
+            ks = [int(v) for v in text.split(",")]
+    except ValueError:
+        raise KMeansError("a sweep is K1,K2,... or LO:HI[:STEP], got %r" % (text,))
+    if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 2:
+        raise KMeansError("a sweep needs increasing k >= 2, got %r" % (text,))
+    return ks
+
+
+def sweep(X, ks, sample_size=None, random_state=None, backend="device", **kmeans_kwargs):
+    """kmeans(X, k, random_state=random_state, **kmeans_kwargs) and validity() for every k of ks on one device copy of X:
+    SweepResult(rows, best_k)"""
+    ks = [int(v) for v in ks]
+    if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 2:
+        raise KMeansError("a sweep needs increasing k >= 2, got %r" % (ks,))
+    X = _as_input(X, backend)
+    n, d = (int(s) for s in X.shape)
+    for k in ks:
+        check_domain(n, d, k)
+    if n > SIL_MAX_N and not (_is_int(sample_size) and sample_size <= SIL_MAX_N):
+        raise KMeansError("more than %d points need sample_size <= %d for the silhouette" % (SIL_MAX_N, SIL_MAX_N))
+    rows = []
+    for k in ks:
+        fit = kmeans(X, k, random_state=random_state, backend=backend, **kmeans_kwargs)
+        rows.append(SweepRow(k, fit, validity(X, fit.labels, k, sample_size, random_state, backend)))
+    return SweepResult(rows)
+
+
 # ---- class averages through the engine
 
 def class_averages(images, params, labels, k, ou, min_count=1, preprocess=True, device=0):
@@ -540,7 +837,12 @@ def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cryo_ralib_amd.kmeans")
     ap.add_argument("input", help="OUT.npz of the sdr or tsne tool, or an [n][d] .npy")
     ap.add_argument("output", help="OUT.npz")
-    ap.add_argument("--k", type=int, required=True, help="number of clusters")
+    ap.add_argument("--k", type=int, default=None, help="number of clusters (optional with --sweep)")
+    ap.add_argument("--scores", action="store_true", help="silhouette (overall, per class, per sample), Calinski-Harabasz and "
+                    "Davies-Bouldin of the result in OUT.npz, and one line per class")
+    ap.add_argument("--sweep", default=None, help="K1,K2,... or LO:HI[:STEP]: k-means and the three scores for every k; the "
+                    "result written is that of --k if given, else of the largest silhouette")
+    ap.add_argument("--sample_size", type=int, default=None, help="evaluate the silhouette on sklearn's random subsample of this size")
     ap.add_argument("--key", default="factors", help="array of an .npz input (default factors; embedding for the tsne tool)")
     ap.add_argument("--init", default="k-means++", help="k-means++, random or a [k][d] .npy")
     ap.add_argument("--n_init", default="auto", help="'auto' or an integer")
@@ -555,12 +857,27 @@ def main(argv=None):
     ap.add_argument("--averages", default=None, help="REFS.{hdf,mrcs,npy}: the k class averages")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    ks = None
+    if args.sample_size is not None and not (args.scores or args.sweep is not None):
+        ap.error("--sample_size needs --scores or --sweep")
+    if args.k is None and args.sweep is None:
+        ap.error("one of --k and --sweep is needed")
+    if args.sweep is not None:
+        try:
+            ks = parse_sweep(args.sweep)
+        except KMeansError as e:
+            ap.error(str(e))
     try:
         X = read_input(args.input, args.key)
         n, d = X.shape
         n_init = args.n_init if args.n_init == "auto" else int(args.n_init)
         init = args.init if args.init in ("k-means++", "random") else np.load(args.init)
-        check_domain(n, d, args.k, args.max_iter, args.tol, n_init)
+        for kk in (ks or []) + ([args.k] if args.k is not None else []):
+            check_domain(n, d, kk, args.max_iter, args.tol, n_init)
+        if args.sample_size is not None and args.sample_size < 1:
+            raise KMeansError("--sample_size is an integer >= 1")
+        if (args.scores or ks) and n > SIL_MAX_N and not (args.sample_size and args.sample_size <= SIL_MAX_N):
+            raise KMeansError("more than %d points need --sample_size <= %d for the silhouette" % (SIL_MAX_N, SIL_MAX_N))
         truth = read_truth(args.truth, n) if args.truth else None
         if args.averages and not (args.stack and args.params and args.ou):
             raise KMeansError("--averages needs --stack, --params and --ou")
@@ -570,15 +887,24 @@ def main(argv=None):
         import torch
         if not torch.cuda.is_available():
             raise SystemExit("no GPU visible: use --backend numpy for the CPU checker (--averages needs the GPU)")
+    swept = val = None
     try:
+        Xb = X
         if args.backend == "device":
             import torch
             dev = torch.device("cuda", args.device)
-            with torch.cuda.device(dev):
-                res = kmeans(torch.from_numpy(X).to(dev), args.k, init, n_init, args.max_iter, args.tol, args.seed)
+            Xb = torch.from_numpy(X).to(dev)
+        if ks:
+            swept = sweep(Xb, ks, args.sample_size, args.seed, args.backend, init=init, n_init=n_init, max_iter=args.max_iter, tol=args.tol)
+            if args.k is None:
+                args.k = swept.best_k
+        if swept is not None and args.k in ks:
+            res, val = swept.row(args.k).fit, swept.row(args.k).validity
         else:
-            res = kmeans(X, args.k, init, n_init, args.max_iter, args.tol, args.seed, backend="numpy")
-    except KMeansError as e:
+            res = kmeans(Xb, args.k, init, n_init, args.max_iter, args.tol, args.seed, backend=args.backend)
+        if args.scores and val is None:
+            val = validity(Xb, res.labels, args.k, args.sample_size, args.seed, args.backend)
+    except (KMeansError, ValueError) as e:
         raise SystemExit("error: %s" % e)
     out = dict(labels=res.labels, centers=res.centers, inertia=np.float64(res.inertia), n_iter=np.int64(res.n_iter),
                init_indices=res.init_indices if res.init_indices is not None else np.zeros(0, np.int64), k=np.int64(args.k),
@@ -600,6 +926,18 @@ def main(argv=None):
             raise SystemExit("error: %s" % e)
         stackio.write_stack(args.averages, refs)
         msg += ", averages -> %s" % args.averages
+    if swept is not None:
+        out["sweep"], out["best_k"] = swept.table(), np.int64(swept.best_k)
+        print("%5s %14s %11s %14s %11s" % ("k", "inertia", "silhouette", "CH", "DB"))
+        for r in swept.rows:
+            print("%5d %14.6g %11.6f %14.6g %11.6f%s" % (r.k, r.inertia, r.silhouette, r.calinski_harabasz, r.davies_bouldin,
+                                                          "  <- best" if r.k == swept.best_k else ""))
+    if args.scores:
+        out["silhouette"], out["class_silhouette"], out["silhouette_samples"] = np.float64(val.silhouette), val.class_silhouette, val.samples
+        out["calinski_harabasz"], out["davies_bouldin"] = np.float64(val.calinski_harabasz), np.float64(val.davies_bouldin)
+        for c in range(args.k):
+            print("class %3d: %7d members, silhouette %8.4f" % (c, val.counts[c], val.class_silhouette[c]))
+        msg += ", silhouette %.4f, CH %.6g, DB %.4f" % (val.silhouette, val.calinski_harabasz, val.davies_bouldin)
     np.savez(args.output, **out)
     print(msg)
     return 0

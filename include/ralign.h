@@ -464,6 +464,24 @@ int  ra_kmeans_search(const double *d_w, int n, const double *d_vals, int m, int
 int  ra_kmeans_seed(const float *d_x, int n, int d, const int *d_cand, int m, double *d_closest, int first, double *d_out,
                     void *hip_stream);
 
+/* Cluster validity of labels d_labels [n] (int, values clamped to 0 .. k - 1; some of the k ids may be unused) on X [n][d] in device
+ * memory, after scikit-learn 1.7's sklearn.metrics with metric="euclidean" (DESIGN.md section 4.13).  Same conventions as the
+ * k-means entries above: asynchronous on hip_stream, scratch allocated and freed on that stream, bitwise reproducible call to
+ * call and across streams, RA_ERR_ARG with nothing launched outside the documented domain.
+ *   ra_kmeans_silhouette  d_out [n][3] (double) = {s_i, a_i, b_i}, d_nearest [n] = the other cluster of least mean distance (the
+ *                         first one on ties; -1, with b = s = 0, when no other cluster has members).  |x_i - x_j| is
+ *                         sqrt(sum_t (x_it - x_jt)^2) from differences in float32; every sum over j is double, in member-list
+ *                         order.  a_i = D(i, own) / (n_own - 1), b_i = min over the other non-empty clusters of D(i, c) / n_c,
+ *                         s_i = (b_i - a_i) / max(a_i, b_i), 0 for a singleton cluster (a_i = 0 then) and for 0 / 0.
+ *                         3 <= n <= 262144, 1 <= d <= 2048, 2 <= k <= 256.
+ *   ra_kmeans_dispersion  the label-derived centroids d_centroids [k][d] (double; 0 for an unused id), d_counts [k] (int),
+ *                         d_sq [k] = sum over the cluster of |x - mu_c|^2 and d_abs [k] = sum of |x - mu_c|, all in double in
+ *                         member-list order: what the Calinski-Harabasz and Davies-Bouldin indices are formed from.
+ *                         1 <= n <= 4194304, 1 <= d <= 2048, 1 <= k <= 256. */
+int  ra_kmeans_silhouette(const float *d_x, int n, int d, const int *d_labels, int k, double *d_out, int *d_nearest, void *hip_stream);
+int  ra_kmeans_dispersion(const float *d_x, int n, int d, const int *d_labels, int k, double *d_centroids, int *d_counts, double *d_sq,
+                          double *d_abs, void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
