@@ -80,7 +80,7 @@ EXPORTED_SYMBOLS = [
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
-    "ra_kmeans_silhouette", "ra_kmeans_dispersion",
+    "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
 ]
 
@@ -205,6 +205,8 @@ def load_library(path=None):
     L.ra_kmeans_seed.argtypes = [vp, ci, ci, vp, ci, vp, ci, vp, vp]
     L.ra_kmeans_silhouette.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     L.ra_kmeans_dispersion.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]
+    L.ra_gmm_estep.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ra_gmm_mstep.argtypes = [vp, ci, ci, ci, ci, vp, ci, ctypes.c_double, vp, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -379,6 +381,24 @@ def kmeans_sweep(X, ks, **kw):
     """k-means and the validity scores for every k of ks on one device copy of X (kmeans.sweep)."""
     from . import kmeans as _kmeans
     return _kmeans.sweep(X, ks, **kw)
+
+
+def gmm(X, n_components, **kw):
+    """Gaussian mixture of X [n][d] (gmm.gmm): GmmResult with weights, means, covariances, precisions_cholesky, labels, ..."""
+    from . import gmm as _gmm
+    return _gmm.gmm(X, n_components, **kw)
+
+
+def gmm_predict_proba(X, model, **kw):
+    """Posterior probabilities [n][k] of a fitted mixture (gmm.predict_proba)."""
+    from . import gmm as _gmm
+    return _gmm.predict_proba(X, model, **kw)
+
+
+def gmm_sweep(X, ks, **kw):
+    """A mixture and its BIC / AIC for every k of ks on one device copy of X (gmm.sweep)."""
+    from . import gmm as _gmm
+    return _gmm.sweep(X, ks, **kw)
 
 
 def _check(rc, what):

@@ -482,6 +482,28 @@ int  ra_kmeans_silhouette(const float *d_x, int n, int d, const int *d_labels, i
 int  ra_kmeans_dispersion(const float *d_x, int n, int d, const int *d_labels, int k, double *d_centroids, int *d_counts, double *d_sq,
                           double *d_abs, void *hip_stream);
 
+/* One E-step and one M-step of a Gaussian mixture on X [n][d] (float32, device memory), after scikit-learn 1.7's GaussianMixture
+ * with covariance_type "full" or "diag" (DESIGN.md section 4.14).  All arithmetic is float64; x - mu is formed in double before it
+ * is multiplied.  Same conventions as the k-means entries: asynchronous on hip_stream, scratch allocated and freed on that stream,
+ * no floating-point atomics, every sum over i in an order fixed by (n, d, k) (bitwise reproducible call to call and across
+ * streams), RA_ERR_ARG with nothing launched outside the domain: 1 <= k <= 256, k <= n <= 4194304, n k <= 2^28, 1 <= d <= 256
+ * (full) or 2048 (diag).
+ *   ra_gmm_estep  log p_ic = d_offset_c - |(x_i - mu_c)^T PC_c|^2 / 2 (diag: sum_t ((x_it - mu_ct) PC_ct)^2), where the caller
+ *                 folds log w_c + log det PC_c - d/2 log 2 pi into d_offset [k].  d_prec_chol: full [k][d][d] row-major, upper
+ *                 triangular (16 x 16 tiles below the diagonal are skipped, so the lower triangle must hold zeros); diag [k][d].
+ *                 d_log_prob [n] = logsumexp_c log p_ic (max-subtracted), d_log_resp [n][k] = log p - d_log_prob (may be NULL),
+ *                 d_labels [n] = argmax_c, the first index on ties (may be NULL), d_sum [1] = sum_i d_log_prob_i.
+ *   ra_gmm_mstep  d_resp [n][k] are responsibilities (log_domain != 0: their logarithms, exp() is applied).  d_nk [k] =
+ *                 sum_i r_ic + 10 eps, d_means [k][d] = sum_i r_ic x_i / nk_c, d_cov full [k][d][d] = sum_i r_ic (x_i - mu_c)
+ *                 (x_i - mu_c)^T / nk_c + reg_covar I (exactly symmetric), diag [k][d] = sum_i r_ic x_i^2 / nk_c - mu_c^2 +
+ *                 reg_covar.  reg_covar >= 0. */
+#define RA_GMM_FULL 0
+#define RA_GMM_DIAG 1
+int  ra_gmm_estep(const float *d_x, int n, int d, int k, int cov_type, const double *d_means, const double *d_prec_chol,
+                  const double *d_offset, double *d_log_resp, double *d_log_prob, int *d_labels, double *d_sum, void *hip_stream);
+int  ra_gmm_mstep(const float *d_x, int n, int d, int k, int cov_type, const double *d_resp, int log_domain, double reg_covar,
+                  double *d_nk, double *d_means, double *d_cov, void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
