@@ -80,7 +80,7 @@ EXPORTED_SYMBOLS = [
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
-    "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep",
+    "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
 ]
 
@@ -207,6 +207,8 @@ def load_library(path=None):
     L.ra_kmeans_dispersion.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp, vp, vp]
     L.ra_gmm_estep.argtypes = [vp, ci, ci, ci, ci, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ra_gmm_mstep.argtypes = [vp, ci, ci, ci, ci, vp, ci, ctypes.c_double, vp, vp, vp, vp]
+    L.ra_dbscan_count.argtypes = [vp, ci, ci, ctypes.c_double, ci, vp, vp, vp]
+    L.ra_dbscan_step.argtypes = [vp, ci, ci, ctypes.c_double, vp, ci, vp, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -399,6 +401,18 @@ def gmm_sweep(X, ks, **kw):
     """A mixture and its BIC / AIC for every k of ks on one device copy of X (gmm.sweep)."""
     from . import gmm as _gmm
     return _gmm.sweep(X, ks, **kw)
+
+
+def dbscan(X, eps, **kw):
+    """DBSCAN of X [n][d] (dbscan.dbscan): DbscanResult with labels (-1 for noise), core_mask, core_sample_indices, n_clusters, ..."""
+    from . import dbscan as _dbscan
+    return _dbscan.dbscan(X, eps, **kw)
+
+
+def dbscan_kdistances(X, min_samples, **kw):
+    """For every point the least eps at which it is a core point, float64 [n] (dbscan.kdistances)."""
+    from . import dbscan as _dbscan
+    return _dbscan.kdistances(X, min_samples, **kw)
 
 
 def _check(rc, what):

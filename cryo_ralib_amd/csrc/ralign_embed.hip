@@ -1,8 +1,9 @@
-// t-SNE, k-means and cluster validity of 2SDR factors (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h): the engine-less
-// ra_tsne_* and ra_kmeans_* entry points of libralign_hip.so, each on the caller's stream.
+// t-SNE, k-means, cluster validity and DBSCAN of 2SDR factors (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h, ralign_dbscan.h):
+// the engine-less ra_tsne_*, ra_kmeans_* and ra_dbscan_* entry points of libralign_hip.so, each on the caller's stream.
 #include "ralign_host.h"
 #include "ralign_kmeans.h"
 #include "ralign_validity.h"
+#include "ralign_dbscan.h"
 
 using namespace ralign;
 
@@ -342,4 +343,58 @@ extern "C" int ra_kmeans_dispersion(const float *d_x, int n, int d, const int *d
     RA_LAUNCH(he, val_disp_kernel, dim3(k), dim3(256), 0, stream, (const double *)dist, (const int *)mem, (const int *)cnt, (const int *)start, n,
               d_sq, d_abs);
     return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_dispersion", he);
+}
+
+// ---- DBSCAN (ralign_dbscan.h)
+
+static bool dbs_domain_ok(const char *what, int n, int d, double eps, int min_samples)
+{
+    if (n < 1 || n > DBS_MAX_N || d < 1 || d > DBS_MAX_D || !std::isfinite(eps) || !(eps > 0.0) || min_samples < 1) {
+        set_error(std::string(what) + ": need 1 <= n <= 262144, 1 <= d <= 2048, a finite eps > 0 and min_samples >= 1");
+        return false;
+    }
+    return true;
+}
+
+extern "C" int ra_dbscan_count(const float *d_x, int n, int d, double eps, int min_samples, int *d_count, int *d_label, void *hip_stream)
+{
+    if (!dbs_domain_ok("ra_dbscan_count", n, d, eps, min_samples)) return RA_ERR_ARG;
+    if (!d_x || !d_count || !d_label) return arg_error("ra_dbscan_count: null argument");
+    hipLaunchKernelGGL(dbs_count_kernel, dim3((n + DBS_TR - 1) / DBS_TR), dim3(256), 0, (hipStream_t)hip_stream, d_x, n, d, eps * eps,
+                       min_samples, d_count, d_label);
+    hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_dbscan_count", he);
+}
+
+extern "C" int ra_dbscan_step(const float *d_x, int n, int d, double eps, const int *d_count, int min_samples, const int *d_label,
+                              int *d_label_out, int *d_changed, void *hip_stream)
+{
+    if (!dbs_domain_ok("ra_dbscan_step", n, d, eps, min_samples)) return RA_ERR_ARG;
+    if (!d_x || !d_count || !d_label || !d_label_out || !d_changed || d_label_out == d_label)
+        return arg_error("ra_dbscan_step: null argument, or d_label_out == d_label");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, nt = (n + 255) / 256, cap = n + 2 * DBS_TC;
+    KmScratch S;
+    const size_t o_flag = S.take((size_t)n * 4), o_bcnt = S.take((size_t)nb * 2 * 4), o_cnt = S.take(2 * 4), o_start = S.take(2 * 4);
+    const size_t o_run0 = S.take(3 * 4), o_mem = S.take((size_t)n * 4), o_pstart = S.take(3 * 4), o_cols = S.take((size_t)cap * 4);
+    const size_t o_m = S.take((size_t)n * 4), o_p = S.take((size_t)n * 4);
+    StreamScratch scratch(stream);
+    if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_dbscan_step", scratch.status());
+    int *flag = S.at<int>(o_flag), *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start), *mem = S.at<int>(o_mem);
+    int *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols), *m = S.at<int>(o_m), *P = S.at<int>(o_p);
+    // the core points in index order: the member list of "cluster" 0 of the flags, padded to the column tile with -1
+    hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);
+    if (he == hipSuccess) he = hipMemsetAsync(d_changed, 0, sizeof(int), stream);
+    RA_LAUNCH(he, dbs_flag_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, flag);
+    if (he == hipSuccess) he = km_member_lists(flag, n, 2, km_run_len(n), S.at<int>(o_bcnt), cnt, start, S.at<int>(o_run0), mem, stream);
+    RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, 2, pstart);
+    RA_LAUNCH(he, val_cols_kernel, dim3(nt), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt, (const int *)pstart,
+              n, 2, cap, cols);
+    RA_LAUNCH(he, dbs_min_kernel, dim3((n + DBS_TR - 1) / DBS_TR), dim3(256), 0, stream, d_x, n, d, eps * eps, (const int *)cols,
+              (const int *)pstart, d_label, m);
+    if (he == hipSuccess) he = hipMemcpyAsync(P, d_label, (size_t)n * 4, hipMemcpyDeviceToDevice, stream);
+    RA_LAUNCH(he, dbs_hook_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, d_label, (const int *)m, P);
+    RA_LAUNCH(he, dbs_compress_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, d_label, (const int *)m, (const int *)P,
+              d_label_out, d_changed);
+    return he == hipSuccess ? RA_OK : hip_error("ra_dbscan_step", he);
 }

@@ -504,6 +504,24 @@ int  ra_gmm_estep(const float *d_x, int n, int d, int k, int cov_type, const dou
 int  ra_gmm_mstep(const float *d_x, int n, int d, int k, int cov_type, const double *d_resp, int log_domain, double reg_covar,
                   double *d_nk, double *d_means, double *d_cov, void *hip_stream);
 
+/* DBSCAN of X [n][d] (float32, device memory), after scikit-learn 1.7's DBSCAN(eps, min_samples, metric="euclidean") (DESIGN.md
+ * section 4.15).  D2(i, j) = sum_t (x_it - x_jt)^2 in double from differences, the features in order (exactly symmetric, 0 on the
+ * diagonal); j is a neighbour of i iff D2(i, j) <= eps * eps (the double product), i included.  Every pass recomputes its
+ * distances: nothing of size n^2 is stored.  Same conventions as the k-means entries: asynchronous on hip_stream, scratch
+ * allocated and freed on that stream, integer atomics only (bitwise reproducible call to call and across streams), RA_ERR_ARG
+ * with nothing launched outside the domain: 1 <= n <= 262144, 1 <= d <= 2048, finite eps > 0, min_samples >= 1.
+ *   ra_dbscan_count  d_count [n] = the number of neighbours, d_label [n] = i for a core point (count >= min_samples), -1 otherwise.
+ *   ra_dbscan_step   one round of component merging over the core points (d_count as ra_dbscan_count left it): m_i = the least
+ *                    d_label of i's core neighbours; every core i with m_i < label_i hooks P[label_i] and P[i] down to m_i (P a
+ *                    copy of the labels, integer atomicMin); then, in a launch of its own, a core i follows P to its fixed point
+ *                    r and d_label_out [n] (!= d_label) gets r; a non-core i gets m_i, or -1 without a core neighbour.
+ *                    d_changed [1] = the number of core points whose label moved.  Repeated from ra_dbscan_count's labels until
+ *                    d_changed is 0, d_label_out holds for a core point the lowest core index of its component, for a border
+ *                    point the least such index among its core neighbours, and -1 for noise.  The loop is cryo_ralib_amd/dbscan.py. */
+int  ra_dbscan_count(const float *d_x, int n, int d, double eps, int min_samples, int *d_count, int *d_label, void *hip_stream);
+int  ra_dbscan_step(const float *d_x, int n, int d, double eps, const int *d_count, int min_samples, const int *d_label,
+                    int *d_label_out, int *d_changed, void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
