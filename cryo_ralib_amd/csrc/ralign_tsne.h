@@ -6,7 +6,8 @@
 //                           by squared distances computed in double from x_i - x_j; writes the k best by (distance, index).
 //   tsne_affinity_kernel    sklearn's _binary_search_perplexity on the k neighbours of a row (one wave per row, double).
 //   tsne_repulsion_kernel   all-pairs partials over one block of rows x one segment of columns: sum_j w_ij^2 (y_i - y_j) per row
-//                           and sum w_ij over the block (self pairs included, removed exactly by the update), w = 1 / (1 + d^2).
+//                           and sum_{j != i} w_ij over the block, w = 1 / (1 + d^2).  The self pair (w = 1) is left out of the
+//                           float sum: a row whose other w are small would lose them against it.
 //   tsne_update_kernel      Z from the block partials, the row's repulsion from its segment partials, the sparse attraction over
 //                           its CSR row, the gradient, then sklearn's gains / momentum update (or the gradient alone).
 //   tsne_stats_kernel       KL error and squared gradient norm from the update's per-workgroup partials.
@@ -18,6 +19,8 @@
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include <type_traits>
 
 namespace ralign {
 
@@ -274,7 +277,7 @@ __global__ __launch_bounds__(256) void tsne_affinity_kernel(const double *__rest
 }
 
 // grid (row blocks, segments). Partials part[s][i] = sum over segment s of w^2 (y_i - y_j); zpart[s * nrb + rb] = sum of w over
-// the block's rows and the segment's columns (self pairs included: one each, 1.0 exactly).
+// the block's rows and the segment's columns, self pairs left out.
 __global__ __launch_bounds__(TSNE_REP_THREADS) void tsne_repulsion_kernel(const float2 *__restrict__ y, int n, int seg,
                                                                           float2 *__restrict__ part, double *__restrict__ zpart)
 {
@@ -288,25 +291,31 @@ __global__ __launch_bounds__(TSNE_REP_THREADS) void tsne_repulsion_kernel(const 
         const float2 v = i < n ? y[i] : float2{0.f, 0.f};
         yx[r] = v.x; yy[r] = v.y; fx[r] = 0.f; fy[r] = 0.f; z[r] = 0.f;
     }
-    const int j0 = s * seg, j1 = min(n, j0 + seg);
+    const int j0 = s * seg, j1 = min(n, j0 + seg), i0 = rb * TSNE_REP_ROWS;
     for (int jt = j0; jt < j1; jt += TSNE_REP_CHUNK) {
         const int c = min(TSNE_REP_CHUNK, j1 - jt);
         __syncthreads();
         for (int t = tid; t < c; t += TSNE_REP_THREADS) ys[t] = y[jt + t];
         __syncthreads();
+        // own: the chunk holds rows of this block, whose self pairs stay out of z (their force term is zero as it is)
+        auto pairs = [&](auto own) {
 #pragma unroll 4
-        for (int j = 0; j < c; j++) {
-            const float2 v = ys[j];
+            for (int j = 0; j < c; j++) {
+                const float2 v = ys[j];
 #pragma unroll
-            for (int r = 0; r < TSNE_REP_R; r++) {
-                const float dx = yx[r] - v.x, dy = yy[r] - v.y;
-                const float w = __builtin_amdgcn_rcpf(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, 1.f)));
-                const float w2 = w * w;
-                z[r] += w;
-                fx[r] = __builtin_fmaf(w2, dx, fx[r]);
-                fy[r] = __builtin_fmaf(w2, dy, fy[r]);
+                for (int r = 0; r < TSNE_REP_R; r++) {
+                    const float dx = yx[r] - v.x, dy = yy[r] - v.y;
+                    const float w = __builtin_amdgcn_rcpf(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, 1.f)));
+                    const float w2 = w * w;
+                    if (decltype(own)::value) z[r] += jt + j == i0 + r * TSNE_REP_THREADS + tid ? 0.f : w;
+                    else z[r] += w;
+                    fx[r] = __builtin_fmaf(w2, dx, fx[r]);
+                    fy[r] = __builtin_fmaf(w2, dy, fy[r]);
+                }
             }
-        }
+        };
+        if (jt < i0 + TSNE_REP_ROWS && jt + c > i0) pairs(std::true_type{});
+        else pairs(std::false_type{});
     }
     double zs = 0.0;
 #pragma unroll
@@ -340,8 +349,8 @@ __global__ __launch_bounds__(TSNE_UPD_THREADS) void tsne_update_kernel(TsneUpdat
     const int tid = threadIdx.x, i = blockIdx.x * TSNE_UPD_THREADS + tid;
     double zs = 0.0;
     for (int t = tid; t < a.nz; t += TSNE_UPD_THREADS) zs += a.zpart[t];
-    // every workgroup forms the same Z; the n self pairs come out exactly (each added 1.0); sklearn floors sum_Q at eps
-    const double Z = fmax(tsne_block_sum<TSNE_UPD_THREADS>(zs, red) - (double)a.n, 2.220446049250313e-16);
+    // every workgroup forms the same Z (the partials hold no self pairs); sklearn floors sum_Q at eps
+    const double Z = fmax(tsne_block_sum<TSNE_UPD_THREADS>(zs, red), 2.220446049250313e-16);
     double err = 0.0, gn = 0.0;
     if (i < a.n) {
         double rx = 0.0, ry = 0.0;
