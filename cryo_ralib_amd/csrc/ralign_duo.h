@@ -45,9 +45,9 @@ inline SoloLds duo_lds_plan(int N, int rows, int pst, int sbuf, int n_qtab, int 
 }
 
 // plan: build_solo_plan's, with the tile size cut to what the ring buffer holds for two offsets
-inline bool build_duo_plan(const Geometry &g, int nref, int n_qtab, int n_inst, int n_job, FusedPlanHost &out)
+inline bool build_duo_plan(const Geometry &g, int nref, int n_qtab, int n_inst, int n_job, bool crop_allowed, FusedPlanHost &out)
 {
-    if (!build_solo_plan(g, nref, n_qtab, n_inst, n_job, out)) return false;
+    if (!build_solo_plan(g, nref, n_qtab, n_inst, n_job, crop_allowed, out)) return false;
     FusedGeom &f = out.f;
     const int zstride = 2 * (g.maxrin + g.maxrin / 16) + 2;
     const int lring_pad = (g.lring + 31) / 32 * 32 + 16;

@@ -25,25 +25,12 @@
 #include "ralign_exact.h"
 #include "ralign_refine.h"
 #include "ralign_host.h"
+#include "ralign_plan.h"
 
 using namespace ralign;
 
 static thread_local std::string g_last_error;
 void set_error(const std::string &msg) { g_last_error = msg; }
-
-// The size-generic kernels for a geometry the LDS-resident ones cover: RALIGN_GENERIC=1 (A/B runs, tests), or an engine whose
-// options only they implement (ra_create_ex: RA_INTERP_QUADRI).  The option is engine state; the flag below carries it into the
-// planning helpers that see a geometry but no engine (fits_specialised_kernels, resident_expected) while that engine is planned.
-static thread_local bool g_force_generic = false;
-// ... and: plan this engine in the size-generic CLASS (crop / pair / solo kernels allowed) although the LDS-resident kernels would hold its
-// image -- the second attempt of ra_create_ex for more than 16 references in boxes whose tiled plan does not fit next to the whole image
-static thread_local bool g_generic_class = false;
-static bool generic_forced() { return g_force_generic || (getenv("RALIGN_GENERIC") && atoi(getenv("RALIGN_GENERIC")) != 0); }
-struct ForceGenericScope {
-    bool prev;
-    explicit ForceGenericScope(bool on) : prev(g_force_generic) { g_force_generic = g_force_generic || on; }
-    ~ForceGenericScope() { g_force_generic = prev; }
-};
 
 // device workspace of one engine, shared by ra_create and the size checks of the reference surface
 // (pre_align_size_check / ref_free_alignment_2D_size_check), so that the estimate cannot drift from what is allocated
@@ -101,8 +88,10 @@ struct ra_engine {
     float *d_wr = nullptr;
     size_t lds_polar = 0, lds_ref = 0, lds_ccf = 0, lds_xf = 0;
     bool force_generic = false;         // options that only the size-generic kernels implement (ra_create_ex)
+    // the class of this engine's plan (ralign_plan.h), decided once per plan: create_engine, ra_reset_shifts.  What the class
+    // wants; fused / tiled / solo / duo / pair below say what the LDS plans then gave.
+    struct { bool fused, tiled, solo, duo, pair; } want{};
     bool generic = false;               // size-generic kernels (ralign_generic.h): large boxes, maxrin > 256, > 48 rings
-    bool no_tcrop = false;              // the crop plan did not fit the real tables once: planned without it (create_engine)
     bool tcrop = false;                 // generic class, but the search runs search_tiled_kernel over a CROP of the image (tcrop_wanted)
     int crop_S = 0;                     // ... whose side was planned for search shifts of up to this many pixels
     int crop_pst = 0;                   // ... and its row stride in LDS (tcrop_wanted)
@@ -222,42 +211,6 @@ static gpolar_fn gpolar_kernel(const ra_engine *e, bool refs)
                 : (q ? (gpolar_fn)polar_generic_kernel<false, true> : (gpolar_fn)polar_generic_kernel<false, false>);
 }
 
-// the particle-resident kernel is planned for this engine (decided before the LDS layout, which differs slightly)
-static bool tiled_wanted(const ra_engine *e)
-{
-    // search_tiled_kernel: more references than one pass of search_fused_kernel accumulates (RALIGN_TILED=1 forces it for fewer)
-    const bool force = getenv("RALIGN_TILED") && atoi(getenv("RALIGN_TILED")) != 0;
-    if (getenv("RALIGN_TILED") && !force) return false;
-    // (from 15 references on: search_fused_kernel needs two spectra rounds per pass from 12 on and is 4 % slower at 15 and 16)
-    return (e->cfg.nref >= RT_MINREF || force) && e->geo.maxrin == 256 && e->geo.nring <= 4 * RT_NQ && e->cfg.nref <= 127;
-}
-
-// search_solo_kernel is planned for this engine: a geometry of the size-generic class whose rings end at 512 samples
-// (RALIGN_SOLO=0: the generic kernels)
-static bool solo_wanted(const ra_engine *e)
-{
-    if (!e->generic || e->geo.maxrin != 512 || e->geo.nring > 4 * RS_NQ || e->geo.numr[2] < 8 || e->cfg.nref > 127) return false;
-    if (g_force_generic) return false;      // engine options that only the size-generic kernels implement (RALIGN_GENERIC=1 leaves this class alone, as before)
-    return !(getenv("RALIGN_SOLO") && atoi(getenv("RALIGN_SOLO")) == 0);
-}
-
-// search_pair_kernel is planned for this engine: a geometry of the size-generic class whose rings end at 256 samples -- a box
-// too large for the four ring buffers of the LDS-resident kernels (RALIGN_PAIR=0: the generic kernels)
-static bool pair_wanted(const ra_engine *e)
-{
-    if (!e->generic || e->geo.maxrin != 256 || e->geo.nring > 4 * RP_NQ || e->geo.numr[2] < 8 || e->cfg.nref > 127) return false;
-    if (generic_forced()) return false;      // the switch that forces the generic kernels
-    return !(getenv("RALIGN_PAIR") && atoi(getenv("RALIGN_PAIR")) == 0);
-}
-
-// two offsets per pass (search_duo_kernel, ralign_duo.h) for the solo class: the default (measured against search_solo_kernel:
-// +4.5 % at 128 / 60 / nref 10, +24 % at 130 / 52 / nref 50); RALIGN_DUO=0: one offset per pass
-static bool duo_wanted(const ra_engine *e)
-{
-    if (!solo_wanted(e)) return false;
-    return !(getenv("RALIGN_DUO") && atoi(getenv("RALIGN_DUO")) == 0);
-}
-
 typedef void (*fused_fn)(DevGeom, FusedGeom, const float *, const float *, int, const float *, int, CandT *, const int *);
 static fused_fn select_tiled(int nh, int sbuf);
 static fused_fn select_fused(int maxrin, int nref, int nzr, int sbuf, bool pack = false, bool crop = false);
@@ -265,16 +218,12 @@ static fused_fn select_fused(int maxrin, int nref, int nzr, int sbuf, bool pack 
 // that the whole image does not fit next to four ring buffers, but a crop around the particle's sampling centre does (crop_plan,
 // ralign_solo.h).  Four offsets per pass with every wave in a ring job instead of the pair kernel's two: 1.6 x its rate.
 // RALIGN_TCROP=0: the pair kernel
-static bool tcrop_wanted(ra_engine *e)
+static bool tcrop_wanted(ra_engine *e, const PlanRequest &rq)
 {
     const Geometry &g = e->geo;
-    // (search_tiled_kernel holds slices of at most 36 rings, search_fused_kernel reads its operand from the ring buffers: up to 64)
-    if (!e->generic || g.maxrin != 256 || g.nring > 64 || g.numr[2] < 8 || e->cfg.nref > 127) return false;
-    if (generic_forced()) return false;
-    if (e->no_tcrop || (getenv("RALIGN_TCROP") && atoi(getenv("RALIGN_TCROP")) == 0)) return false;
-    if (getenv("RALIGN_FUSED") && atoi(getenv("RALIGN_FUSED")) == 0) return false;
+    if (!tcrop_class(g, e->cfg, rq, e->generic)) return false;
     FusedGeom t{};
-    crop_plan(g, t);
+    crop_plan(g, t, rq.sw.crop);
     if (!t.s_crop) return false;
     // the job tables and the image stride are laid out for this kernel before its plan is made (build_device_geometry), so the
     // answer has to be the plan's: the same plan on an upper estimate of the polar part's LDS (tables of 4 offset slots)
@@ -290,9 +239,9 @@ static bool tcrop_wanted(ra_engine *e)
     const size_t polar = (size_t)pst * pst + 4 * (size_t)std::max(sbuf, sbuf <= RF_SBUF_FIXED ? RF_SBUF_FIXED : sbuf) + 2 * g.maxrin + 3000;
     // the kernels' division of the reference counts is that of the 90 x 90 engines: search_fused_kernel up to RT_MINREF - 1
     // references, search_tiled_kernel from there on (RALIGN_TILED=1: from 7 on, the fewest its tile sizes are instantiated for)
-    const bool force = getenv("RALIGN_TILED") && atoi(getenv("RALIGN_TILED")) != 0, no_tiled = getenv("RALIGN_TILED") && !force;
+    const bool no_tiled = rq.sw.tiled == 0;
     for (int sb : {sbuf <= RF_SBUF_FIXED ? RF_SBUF_FIXED : sbuf, sbuf}) {
-        if (!no_tiled && (e->cfg.nref >= RT_MINREF || force) && build_tiled_plan(g, e->cfg.nref, sb, polar, tmp) && select_tiled(tmp.f.nh, sb)) return true;
+        if (tiled_by_count(e->cfg, rq) && build_tiled_plan(g, e->cfg.nref, sb, polar, tmp) && select_tiled(tmp.f.nh, sb)) return true;
         if (e->cfg.nref <= RF_MAXREF && build_fused_plan(g, e->cfg.nref, sb, polar, tmp) && select_fused(g.maxrin, e->cfg.nref, tmp.f.nzr, sb, false, true)) return true;
         if (!no_tiled && build_tiled_plan(g, e->cfg.nref, sb, polar, tmp) && select_tiled(tmp.f.nh, sb)) return true;
     }
@@ -300,17 +249,20 @@ static bool tcrop_wanted(ra_engine *e)
     return false;
 }
 
-static bool fused_wanted(const ra_engine *e)
+// the class of the engine's plan, once e->generic and e->tcrop stand
+static void decide_class(ra_engine *e, const PlanRequest &rq)
 {
-    if (e->generic) return false;
-    if (getenv("RALIGN_FUSED") && atoi(getenv("RALIGN_FUSED")) == 0) return false;
-    if (tiled_wanted(e)) return true;
-    if (e->cfg.nref > RF_MAXREF) return false;
-    return e->geo.maxrin == 256 || e->geo.maxrin == 128;
+    const Geometry &g = e->geo;
+    e->want.fused = fused_class(g, e->cfg, rq, e->generic);
+    e->want.tiled = e->tcrop ? tiled_by_count(e->cfg, rq) : tiled_class(g, e->cfg, rq);
+    e->want.solo = solo_class(g, e->cfg, rq, e->generic);
+    e->want.duo = duo_class(g, e->cfg, rq, e->generic);
+    e->want.pair = pair_class(g, e->cfg, rq, e->generic);
 }
 
-static int build_device_geometry(ra_engine *e)
+static int build_device_geometry(ra_engine *e, const PlanRequest &rq)
 {
+    const bool resident4 = e->want.fused || e->tcrop;      // four offset slots per pass in the LDS: search_fused_kernel / search_tiled_kernel
     Geometry &g = e->geo;
     DevGeom &d = e->dg;
     d.nx = g.nx; d.cnx = g.nx / 2 + 1;
@@ -335,10 +287,10 @@ static int build_device_geometry(ra_engine *e)
     // ring-buffer stride.  Kernel pair: == 8 (mod 32), the 4 offsets of an entry hit disjoint banks in the write-out gather.
     // Fused kernel: == 16 (mod 32), the two offsets a 4x4x1 MFMA A operand reads (16 bins x Re/Im each) sit in disjoint
     // halves of the 32 banks (RALIGN_SBUF_PAD overrides: experiments)
-    int sbuf = (g.lring + 31) / 32 * 32 + (RA_EXP_ENV("RALIGN_SBUF_PAD") ? ra_atoi(RA_EXP_ENV("RALIGN_SBUF_PAD")) : ((fused_wanted(e) || e->tcrop) ? 16 : 8));
+    int sbuf = (g.lring + 31) / 32 * 32 + (RA_EXP_ENV("RALIGN_SBUF_PAD") ? ra_atoi(RA_EXP_ENV("RALIGN_SBUF_PAD")) : (resident4 ? 16 : 8));
     // fused kernel at maxrin 256: pad the stride to the compile-time value of its fixed-stride instantiations when the image
     // and four such buffers (+ 16 KB of tables and records) still fit the LDS (RALIGN_SBUF_FIXED=0: keep the run-time stride)
-    if ((fused_wanted(e) || e->tcrop) && g.maxrin == 256 && sbuf <= RF_SBUF_FIXED && !RA_EXP_ENV("RALIGN_SBUF_PAD") &&
+    if (resident4 && g.maxrin == 256 && sbuf <= RF_SBUF_FIXED && !RA_EXP_ENV("RALIGN_SBUF_PAD") &&
         !(RA_EXP_ENV("RALIGN_SBUF_FIXED") && ra_atoi(RA_EXP_ENV("RALIGN_SBUF_FIXED")) == 0)) {
         const int bd0 = (int)std::ceil(std::max(e->cfg.xrng, e->cfg.yrng)) + 2, pst0 = e->tcrop ? e->crop_pst : g.nx + 2 * bd0 + 3;
         if ((size_t)(pst0 * pst0 + 4 * RF_SBUF_FIXED + 3400) * sizeof(float) <= 160 * 1024) sbuf = RF_SBUF_FIXED;
@@ -445,7 +397,7 @@ static int build_device_geometry(ra_engine *e)
             // rings of 8 .. 32 samples share jobs of code 9 (ring_job_mix: n / 8 lanes per ring, one table entry per lane)
             // (RALIGN_MIX_JOBS=0, one job per ring length, is an experiment switch of the kernel pair: the fused kernel carries
             // the job variants of codes 1, 6, 7 and 9 only)
-            const bool mixed = solo || pairj || (nslot == 4 && (fused_wanted(e) || e->tcrop || !(RA_EXP_ENV("RALIGN_MIX_JOBS") && ra_atoi(RA_EXP_ENV("RALIGN_MIX_JOBS")) == 0)));
+            const bool mixed = solo || pairj || (nslot == 4 && (resident4 || !(RA_EXP_ENV("RALIGN_MIX_JOBS") && ra_atoi(RA_EXP_ENV("RALIGN_MIX_JOBS")) == 0)));
             for (int lg = solo ? 9 : 8; lg >= (mixed ? 6 : 3); lg--) {
                 const int n = 1 << lg;
                 const int code = lightjobs && n == 512 ? 11 : lightjobs && n == 256 ? 0 :
@@ -489,16 +441,16 @@ static int build_device_geometry(ra_engine *e)
                 flush();
             }
         };
-        const bool light_only = getenv("RALIGN_SOLO_JOBS") && atoi(getenv("RALIGN_SOLO_JOBS")) == 1;
+        const bool light_only = rq.sw.solo_jobs == 1;
         if (!e->generic) make_jobs(4, jobs, inst, instw, false);
-        else if (solo_wanted(e)) {
+        else if (e->want.solo) {
             // table A (every kernel of the class; the first offset of a duo pass), then -- duo -- table B: the light jobs of the second offset
             make_jobs(1, jobs, inst, instw, light_only);
             d.n_job_b = 0;
             const int na = (int)jobs.size();
-            if (duo_wanted(e) && !light_only) { make_jobs(1, jobs, inst, instw, true); d.n_job_b = (int)jobs.size() - na; }
+            if (e->want.duo && !light_only) { make_jobs(1, jobs, inst, instw, true); d.n_job_b = (int)jobs.size() - na; }
         } else if (e->tcrop) make_jobs(4, jobs, inst, instw, false);
-        else if (pair_wanted(e)) make_jobs(2, jobs, inst, instw, false);
+        else if (e->want.pair) make_jobs(2, jobs, inst, instw, false);
         if (const char *po = RA_EXP_ENV("RALIGN_JOB_ORDER")) {       // experiments: wave w of a pass runs job order[w] ("3,2,1,0,...")
             std::vector<int4> perm;
             for (const char *c = po; *c;) {
@@ -510,7 +462,7 @@ static int build_device_geometry(ra_engine *e)
             if (perm.size() == jobs.size()) jobs = perm;
         }
     }
-    if (!(e->generic && solo_wanted(e))) d.n_job_b = 0;
+    if (!e->want.solo) d.n_job_b = 0;
     d.n_job = (int)jobs.size() - d.n_job_b; d.n_qtab = (int)qtab.size(); d.n_inst = (int)inst.size();
     e->ringw_h = ringw;
     d.bd = (int)std::ceil(std::max(e->cfg.xrng, e->cfg.yrng)) + 2;
@@ -606,60 +558,38 @@ template <typename T> static int dev_grow(ra_engine *e, T **p, size_t count, boo
     return dev_alloc(e, p, count, zero);
 }
 
-// Will ra_create select a particle-resident kernel (search_fused_kernel / search_tiled_kernel) for this geometry?  The same
-// conditions as fused_wanted / tiled_wanted and the LDS estimate of build_device_geometry, evaluated without an engine, so
+// Will ra_create select a particle-resident kernel (search_fused_kernel / search_tiled_kernel) for this geometry?  The class
+// conditions of the engine's plan (ralign_plan.h) and the LDS estimate of build_device_geometry, evaluated without an engine, so
 // that the size checks charge what that path allocates (candidate records, the B stream) instead of the spectra panels of
-// the two-kernel path, which are then never allocated (ensure_unfused_ws is lazy).
-static bool resident_expected(const Geometry &g, const ra_config &cfg, bool generic, size_t *b_floats)
+// the two-kernel path, which are then never allocated (ensure_unfused_ws is lazy).  The LDS figures are estimates of its own, made
+// before any table exists; it knows nothing of the crop plan over four ring buffers (tcrop) or the tight-ring geometry.
+static bool resident_expected(const Geometry &g, const ra_config &cfg, const PlanRequest &rq, bool generic, size_t *b_floats)
 {
     if (generic) {
         // search_solo_kernel / search_duo_kernel (setup_solo): rings of 512 samples, image and one ring buffer in the LDS;
         // search_pair_kernel: rings of 256 samples, image and two ring buffers
-        const bool c512 = g.maxrin == 512 && g.nring <= 4 * RS_NQ && !g_force_generic && !(getenv("RALIGN_SOLO") && atoi(getenv("RALIGN_SOLO")) == 0);
-        const bool c256 = g.maxrin == 256 && g.nring <= 4 * RP_NQ && !(getenv("RALIGN_PAIR") && atoi(getenv("RALIGN_PAIR")) == 0) &&
-                          !generic_forced();
-        if (!(c512 || c256) || g.numr[2] < 8 || cfg.nref > 127) return false;
+        const bool c512 = solo_class(g, cfg, rq, generic), c256 = pair_class(g, cfg, rq, generic);
+        if (!(c512 || c256)) return false;
         // the LDS image is a crop around the particle's centre when the box is larger than the rings need (crop_plan)
-        const int S = (int)std::ceil(std::max(g.nkx, g.nky) * g.step - 1e-6), side = 2 * (S + g.last_ring) + 5;
-        const int cols = (side < g.nx && !(getenv("RALIGN_CROP") && atoi(getenv("RALIGN_CROP")) == 0)) ? side : g.nx;
-        int pst = cols + 1;
-        while (!((pst & 1) && ((pst - 1) & 7) && ((pst + 1) & 7))) pst++;
+        FusedGeom t{};
+        const int cols = crop_plan(g, t, rq.sw.crop), pst = t.s_pst;
         const int nrp = (cfg.nref + 1) / 2, ntile = (nrp + RS_MAXNH - 1) / RS_MAXNH, nh = (nrp + ntile - 1) / ntile;
         const int sbuf = c256 ? 2 * ((g.lring + 31) / 32 * 32 + 16)
                               : std::max((g.lring + 31) / 32 * 32 + 16, 2 * nh * (2 * (g.maxrin + g.maxrin / 16) + 2));
         if ((size_t)((cols + 1) * pst + sbuf + 4600 + 2 * g.nring + 10 * (g.nring + 16)) * sizeof(float) > 160 * 1024) return false;
-        size_t quads = 0;
-        for (int m = 0; m < g.maxrin / 32; m++) {
-            int r0 = 0;
-            while (r0 < g.nring) {
-                const int n = g.numr[3 * r0 + 2], nbin = (n == g.maxrin) ? n / 2 : n / 2 + 1;
-                if (16 * m < nbin) break;
-                r0++;
-            }
-            quads += (g.nring - r0 + 3) / 4;
-        }
-        if (b_floats) *b_floats = (size_t)nrp * quads * 256 + 256;
+        if (b_floats) *b_floats = (size_t)nrp * b_stream_quads(g) * 256 + 256;
         return true;
     }
-    if (getenv("RALIGN_FUSED") && atoi(getenv("RALIGN_FUSED")) == 0) return false;
-    const bool tiled = cfg.nref >= RT_MINREF && g.maxrin == 256 && g.nring <= 4 * RT_NQ && cfg.nref <= 127 &&
-                       !(getenv("RALIGN_TILED") && atoi(getenv("RALIGN_TILED")) == 0);
-    if (!tiled && (cfg.nref > RF_MAXREF || !(g.maxrin == 256 || g.maxrin == 128))) return false;
+    if (!fused_class(g, cfg, rq, generic)) return false;
+    // the estimate charges the tiled plan's tables from RT_MINREF references on and does not know RALIGN_TILED=1 below that count
+    // (the engine's tiled_class does): a forced tiled plan is estimated as the fused one, as it always was.  (fused_class holds for
+    // such a request either way: RT_MINREF - 1 <= RF_MAXREF.)
+    const bool tiled = tiled_class(g, cfg, rq) && cfg.nref >= RT_MINREF;
     if (g.numr[2] < 8 || g.nring > 64) return false;
     const int bd0 = (int)std::ceil(std::max(cfg.xrng, cfg.yrng)) + 2, pst0 = g.nx + 2 * bd0 + 3;
     const int sbuf0 = (g.lring + 31) / 32 * 32 + 16;
     if ((size_t)(pst0 * pst0 + 4 * sbuf0 + 3400 + (tiled ? 1200 : 0)) * sizeof(float) > 160 * 1024) return false;
-    size_t quads = 0;
-    for (int m = 0; m < g.maxrin / 32; m++) {
-        int r0 = 0;
-        while (r0 < g.nring) {
-            const int n = g.numr[3 * r0 + 2], nbin = (n == g.maxrin) ? n / 2 : n / 2 + 1;
-            if (16 * m < nbin) break;
-            r0++;
-        }
-        quads += (g.nring - r0 + 3) / 4;
-    }
-    if (b_floats) *b_floats = (size_t)((cfg.nref + 1) / 2) * quads * 256 + 256;
+    if (b_floats) *b_floats = (size_t)((cfg.nref + 1) / 2) * b_stream_quads(g) * 256 + 256;
     return true;
 }
 
@@ -673,15 +603,15 @@ static size_t refine_resident_lds(const Geometry &g)
 // (RA_EXACT_STATIC_LDS) exceed the 160 KB of a workgroup, or when RALIGN_REFINE_GM=1 asks for that route (tests).  The one rule of
 // plan_workspace (no device: ra_legacy_bytes) and setup_refine.
 #define RA_LDS_PER_WORKGROUP ((size_t)160 * 1024)
-static bool refine_rings_global(const Geometry &g)
+static bool refine_rings_global(const Geometry &g, const PlanRequest &rq)
 {
     // (a candidate's spectrum, maxrin doubles, lies in the second half of a block of global scratch: ring sets shorter than that
     // keep the resident layout, which has room for it)
-    if (getenv("RALIGN_REFINE_GM") && atoi(getenv("RALIGN_REFINE_GM")) != 0 && g.lcirc >= 2 * g.maxrin) return true;
+    if (rq.sw.refine_gm && g.lcirc >= 2 * g.maxrin) return true;
     return refine_resident_lds(g) + RA_EXACT_STATIC_LDS > RA_LDS_PER_WORKGROUP;
 }
 
-static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, bool generic)
+static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, const PlanRequest &rq, bool generic)
 {
     WorkspacePlan w{};
     const int a_blk = g.LBP * 8 + 64, nrtile = (cfg.nref + 7) / 8;
@@ -693,12 +623,12 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, boo
         const size_t cap = std::max<size_t>(2, ((size_t)12 << 30) / per_particle);
         if ((size_t)chunk > cap) chunk = (int)(cap & ~(size_t)1);
     }
-    if (generic && g.maxrin == 1024 && !(getenv("RALIGN_GCCF_SPLIT") && atoi(getenv("RALIGN_GCCF_SPLIT")) == 0) && cfg.chunk <= 0) {
+    if (generic && g.maxrin == 1024 && rq.sw.gccf_split && cfg.chunk <= 0) {
         // split contraction: a chunk is walked in slices of nblk blocks, one block per workgroup, and a slice takes its time
         // whether it is full or not (341 particles = 2580 blocks of 4 x 7 tiles = 10 slices of 256 + one of 20): take the chunk
         // size, up to 64 particles below the cap, with the most particles per slice
         const bool wide = gccf_wide_blocks(nrtile);
-        const int tm = wide ? gccf_tm(nrtile, g.maxrin) : 2, tr = wide ? 7 : 2, nblk = (tm >= 4 ? 256 : 512) * gccf_blocks_per_wg();
+        const int tm = wide ? gccf_tm(nrtile, g.maxrin, rq.sw.gccf_tm) : 2, tr = wide ? 7 : 2, nblk = (tm >= 4 ? 256 : 512) * gccf_blocks_per_wg();
         int best = chunk;
         double best_pps = 0.0;
         for (int cn = chunk; cn >= std::max(2, chunk - 64); cn -= 2) {
@@ -716,7 +646,7 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, boo
     w.b_floats = (size_t)nrtile * g.LBP * 16;
     w.alscratch_floats = (size_t)chunk * g.nx * g.nx;
     // CCF-spectra scratch of ccf_generic_kernel: 64 pairs x 7 tiles per workgroup, x 14 for the 2 x 7 blocks (gccf_tm; 4 x 7: half the workgroups)
-    const bool wide2 = generic && gccf_tm(nrtile, g.maxrin) >= 2;
+    const bool wide2 = generic && gccf_tm(nrtile, g.maxrin, rq.sw.gccf_tm) >= 2;
     w.zscr_recs = generic ? (size_t)512 * (wide2 ? RA_GCCF_ZPAIRS_MAX : RA_GCCF_ZPAIRS_MAX / 2) * (g.maxrin + 2) : 0;      // + 2: N/2 + 1 bins of two values (split kernels); allocated on first use of the generic search
     if (generic && g.maxrin == 1024) w.zscr_recs *= gccf_blocks_per_wg();
     const size_t nxh = g.nx / 2 + 1, rf_cap = 2 * (size_t)cfg.nref;
@@ -725,7 +655,7 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, boo
     // the particle-resident kernels need one candidate record per particle-offset and their B stream; the spectra panels and
     // per-tile candidates of the two-kernel path are allocated on first use only (never, when the resident kernel runs)
     size_t bf = 0;
-    const bool resident = resident_expected(g, cfg, generic, &bf);
+    const bool resident = resident_expected(g, cfg, rq, generic, &bf);
     const size_t fcand = (size_t)chunk * g.nshift_pad + 8;
     const size_t search_ws = resident ? bf * (sizeof(float) + sizeof(int)) + fcand * sizeof(CandT)      // B stream + its gather table
                                       : w.a_floats * sizeof(float) + (w.cand_recs + fcand) * sizeof(CandT);
@@ -737,7 +667,7 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, boo
                               : w.alscratch_floats * sizeof(float) + nseg * chunk * sizeof(int) + 16 * nseg * npix * sizeof(float);
     // sub-bin refinement (ralign_exact.h): exact reference spectra, the list of flagged particles, global ring buffers of large boxes
     const size_t exact_ws = (size_t)cfg.nref * g.lcirc * sizeof(float) + (size_t)chunk * sizeof(RefineRec) +
-                            (refine_rings_global(g) ? (size_t)std::max(256, cfg.nref) * 2 * g.lcirc * sizeof(float) : 0);
+                            (refine_rings_global(g, rq) ? (size_t)std::max(256, cfg.nref) * 2 * g.lcirc * sizeof(float) : 0);
     w.bytes = (w.refspec_floats + w.b_floats + 2) * sizeof(float) + search_ws + sums_ws + exact_ws +
               (resident ? 0 : w.zscr_recs * sizeof(float2)) + refine + tables;
     // every hipMalloc is rounded up to the allocator's granule; ~40 small tables and buffers
@@ -841,29 +771,42 @@ template <typename T> static int grow_upload(ra_engine *e, T **dptr, size_t *cap
 }
 
 // dense offset stream (search_fused_kernel's PACK): pays when the last pass of a particle would carry padding offsets
-// (RALIGN_PACK=0: off)
+// (RALIGN_PACK=0: off -- a switch of the LAUNCH, read at every search, not of the plan: both kernels are prepared by setup_fused)
+static bool pack_allowed() { return env_int("RALIGN_PACK", 1) != 0; }
 static bool pack_ok(const ra_engine *e)
 {
-    if (!e->fused || e->tiled || (getenv("RALIGN_PACK") && atoi(getenv("RALIGN_PACK")) == 0)) return false;
+    if (!e->fused || e->tiled || !pack_allowed()) return false;
     if (e->geo.nshift % 4 == 0 || e->geo.nshift < 4) return false;      // (a pass holds the offsets of at most two particles)
     return select_fused(e->geo.maxrin, e->cfg.nref, e->fplan.f.nzr, e->dg.sbuf, true, e->tcrop) != nullptr;
 }
 
+// the resident tables of the plan in e->fplan (fused, tiled, solo, duo, pair): the gather table of the B stream, the stream itself and
+// the DC weights of the references
+static int upload_resident_tables(ra_engine *e)
+{
+    FusedPlanHost &fp = e->fplan;
+    int rc;
+    if ((rc = grow_upload(e, &e->d_fbsrc, &e->f_cap_b, fp.bsrc))) return rc;
+    if (!e->d_Bf && (rc = dev_alloc(e, &e->d_Bf, (size_t)fp.f.b_floats + 256, true))) return rc;
+    if (!e->d_gcdc && (rc = dev_alloc(e, &e->d_gcdc, (size_t)e->cfg.nref, true))) return rc;
+    fp.f.bsrc = e->d_fbsrc; fp.f.cdc_w = e->d_gcdc;
+    return RA_OK;
+}
+
 // plan of the particle-resident search kernel (ralign_fused.h) and its tables.  It covers every search window of a
 // geometry the LDS-resident kernels cover, up to RF_MAXREF references; everything else keeps the two-kernel path.
-static int setup_fused(ra_engine *e)
+static int setup_fused(ra_engine *e, const PlanRequest &rq)
 {
     e->fused = false; e->tiled = false;
     e->fplan.f.on = 0;
     if (e->generic && !e->tcrop) return RA_OK;
-    if (getenv("RALIGN_FUSED") && atoi(getenv("RALIGN_FUSED")) == 0) return RA_OK;
+    if (!rq.sw.fused) return RA_OK;
     const Geometry &g = e->geo;
     FusedPlanHost &fp = e->fplan;
-    const bool force_tiled = getenv("RALIGN_TILED") && atoi(getenv("RALIGN_TILED")) != 0, no_tiled = getenv("RALIGN_TILED") && !force_tiled;
-    const bool want_tiled = e->tcrop ? (!no_tiled && (e->cfg.nref >= RT_MINREF || force_tiled)) : tiled_wanted(e);
+    const bool no_tiled = rq.sw.tiled == 0;
     auto plan_tiled = [&]() { return build_tiled_plan(g, e->cfg.nref, e->dg.sbuf, e->lds_polar / sizeof(float), fp) && select_tiled(fp.f.nh, e->dg.sbuf); };
     auto plan_fused = [&]() { return select_fused(g.maxrin, e->cfg.nref, 1, 0, false, e->tcrop) && build_fused_plan(g, e->cfg.nref, e->dg.sbuf, e->lds_polar / sizeof(float), fp); };
-    if (want_tiled && plan_tiled()) e->tiled = true;
+    if (e->want.tiled && plan_tiled()) e->tiled = true;
     else if (plan_fused()) e->tiled = false;
     else if (e->tcrop && !no_tiled && plan_tiled()) e->tiled = true;
     else if (e->tcrop) {
@@ -872,21 +815,18 @@ static int setup_fused(ra_engine *e)
     } else return RA_OK;
     if (e->tcrop) {
         FusedGeom tcr{};
-        crop_plan(g, tcr);
+        crop_plan(g, tcr, rq.sw.crop);
         fp.f.s_crop = tcr.s_crop; fp.f.s_cropm = tcr.s_cropm;
     }
     int rc;
-    if ((rc = grow_upload(e, &e->d_fbsrc, &e->f_cap_b, fp.bsrc))) return rc;
-    if (!e->d_Bf && (rc = dev_alloc(e, &e->d_Bf, (size_t)fp.f.b_floats + 256, true))) return rc;
-    if (!e->d_gcdc && (rc = dev_alloc(e, &e->d_gcdc, (size_t)e->cfg.nref, true))) return rc;
-    fp.f.bsrc = e->d_fbsrc; fp.f.cdc_w = e->d_gcdc;
+    if ((rc = upload_resident_tables(e))) return rc;
     for (int pk = 0; pk < (e->tiled ? 1 : 2); pk++) {
         const fused_fn fk = e->tiled ? select_tiled(fp.f.nh, e->dg.sbuf) : select_fused(g.maxrin, e->cfg.nref, fp.f.nzr, e->dg.sbuf, pk != 0, e->tcrop);
         if (!fk) continue;
         const std::string kn = std::string(e->tiled ? "search_tiled_kernel" : pk ? "search_fused_kernel<pack>" : "search_fused_kernel") + (e->tcrop ? " (crop)" : "");
         if ((rc = raise_dynamic_lds(e, (const void *)fk, kn.c_str(), fp.lds_bytes))) return rc;
     }
-    if (getenv("RALIGN_INFO")) fprintf(stderr, "libralign_hip: %s plan: %zu bytes of LDS (polar part %zu), sbuf %d, pst %d, nzr %d, rz %d\n", e->tiled ? "tiled" : "fused", fp.lds_bytes, e->lds_polar, e->dg.sbuf, e->dg.pst, fp.f.nzr, fp.f.rz);
+    if (rq.sw.info) fprintf(stderr, "libralign_hip: %s plan: %zu bytes of LDS (polar part %zu), sbuf %d, pst %d, nzr %d, rz %d\n", e->tiled ? "tiled" : "fused", fp.lds_bytes, e->lds_polar, e->dg.sbuf, e->dg.pst, fp.f.nzr, fp.f.rz);
     e->fused = true;
     return RA_OK;
 }
@@ -949,42 +889,36 @@ static solo_fn select_pair(int maxrin, int nhw)
 // plan of search_solo_kernel (ralign_solo.h) for an engine of the size-generic class whose rings end at 512 samples; the generic
 // kernels stay available underneath (reference preparation, RALIGN_SOLO=0, geometries whose image and one ring buffer exceed
 // the LDS)
-static int setup_solo(ra_engine *e)
+static int setup_solo(ra_engine *e, const PlanRequest &rq)
 {
     e->solo = false; e->duo = false; e->pair = false;
     const Geometry &g = e->geo;
     FusedPlanHost &fp = e->fplan;
     if (e->fused) return RA_OK;          // tcrop: search_tiled_kernel over a crop of the image took this engine of the generic class
-    if (pair_wanted(e)) {
+    if (e->want.pair) {
         // maxrin 256 in a box too large for four ring buffers: two offsets per pass in two (ralign_pair.h)
-        if (!build_pair_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job, fp)) { fp.f.on = 0; return RA_OK; }
+        if (!build_pair_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job, rq.sw.crop, fp)) { fp.f.on = 0; return RA_OK; }
         const solo_fn fk = select_pair(g.maxrin, fp.f.nrpw);
         if (!fk) { fp.f.on = 0; return RA_OK; }
         int rc;
-        if ((rc = grow_upload(e, &e->d_fbsrc, &e->f_cap_b, fp.bsrc))) return rc;
-        if (!e->d_Bf && (rc = dev_alloc(e, &e->d_Bf, (size_t)fp.f.b_floats + 256, true))) return rc;
-        if (!e->d_gcdc && (rc = dev_alloc(e, &e->d_gcdc, (size_t)e->cfg.nref, true))) return rc;
-        fp.f.bsrc = e->d_fbsrc; fp.f.cdc_w = e->d_gcdc;
+        if ((rc = upload_resident_tables(e))) return rc;
         if ((rc = raise_dynamic_lds(e, (const void *)fk, "search_pair_kernel", fp.lds_bytes)) || (rc = raise_dynamic_lds(e, (const void *)search_pair_kernel<256, 1>, "search_pair_kernel<256, 1>", fp.lds_bytes))) return rc;
-        if (getenv("RALIGN_INFO")) fprintf(stderr, "libralign_hip: pair plan: %zu bytes of LDS, image %d x %d, 2 ring buffers of %d floats, %d jobs, %d tiles of 2 x %d reference pairs\n",
+        if (rq.sw.info) fprintf(stderr, "libralign_hip: pair plan: %zu bytes of LDS, image %d x %d, 2 ring buffers of %d floats, %d jobs, %d tiles of 2 x %d reference pairs\n",
                                            fp.lds_bytes, fp.f.s_rows, fp.f.s_pst, fp.f.s_sbuf, e->dg.n_job, fp.f.ntile, fp.f.nrpw);
         e->solo = true; e->pair = true;
         return RA_OK;
     }
-    if (!solo_wanted(e)) return RA_OK;
-    e->duo = duo_wanted(e) && build_duo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, fp) && select_duo(g.maxrin, fp.f.nh, plan_nqmax(fp.f));
-    if (!e->duo && !build_solo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, fp)) { fp.f.on = 0; return RA_OK; }
+    if (!e->want.solo) return RA_OK;
+    e->duo = e->want.duo && build_duo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, rq.sw.crop, fp) && select_duo(g.maxrin, fp.f.nh, plan_nqmax(fp.f));
+    if (!e->duo && !build_solo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, rq.sw.crop, fp)) { fp.f.on = 0; return RA_OK; }
     const solo_fn fk = e->duo ? select_duo(g.maxrin, fp.f.nh, plan_nqmax(fp.f)) : select_solo(g.maxrin, fp.f.nh, fp.f.ntile);
     if (!fk) { fp.f.on = 0; return RA_OK; }
     int rc;
-    if ((rc = grow_upload(e, &e->d_fbsrc, &e->f_cap_b, fp.bsrc))) return rc;
-    if (!e->d_Bf && (rc = dev_alloc(e, &e->d_Bf, (size_t)fp.f.b_floats + 256, true))) return rc;
-    if (!e->d_gcdc && (rc = dev_alloc(e, &e->d_gcdc, (size_t)e->cfg.nref, true))) return rc;
-    fp.f.bsrc = e->d_fbsrc; fp.f.cdc_w = e->d_gcdc;
+    if ((rc = upload_resident_tables(e))) return rc;
     if ((rc = raise_dynamic_lds(e, (const void *)fk, e->duo ? "search_duo_kernel" : "search_solo_kernel", fp.lds_bytes)) ||
         (rc = raise_dynamic_lds(e, (const void *)search_solo_kernel<512, 1, true>, "search_solo_kernel<512, 1, true>", fp.lds_bytes))) return rc;          // ra_debug_spectra: the polar stage through the solo kernel's debug path
-    if (getenv("RALIGN_INFO")) fprintf(stderr, "libralign_hip: %s plan:", e->duo ? "duo" : "solo");
-    if (getenv("RALIGN_INFO")) fprintf(stderr, " %zu bytes of LDS, image %d x %d, ring buffer %d floats, %d jobs, %d tiles of %d reference pairs\n",
+    if (rq.sw.info) fprintf(stderr, "libralign_hip: %s plan:", e->duo ? "duo" : "solo");
+    if (rq.sw.info) fprintf(stderr, " %zu bytes of LDS, image %d x %d, ring buffer %d floats, %d jobs, %d tiles of %d reference pairs\n",
                                        fp.lds_bytes, fp.f.s_rows, fp.f.s_pst, fp.f.s_sbuf, e->dg.n_job, fp.f.ntile, fp.f.nh);
     e->solo = true;
     return RA_OK;
@@ -993,11 +927,11 @@ static int setup_solo(ra_engine *e)
 // plan and tables of polar_zone_kernel (ralign_zone.h) for an engine that runs the size-generic polar stage: ring zones whose
 // annulus (for every search offset of the window) fits the LDS.  RALIGN_ZONES=0: the global-tap kernel.  Quadri sampling (six
 // taps, periodic) stays with the global-tap kernel.
-static int setup_zones(ra_engine *e)
+static int setup_zones(ra_engine *e, const PlanRequest &rq)
 {
     e->zones = false;
     if (!e->generic || e->fused || e->solo || e->dg.interp != RA_INTERP_BILINEAR) return RA_OK;
-    if (getenv("RALIGN_ZONES") && atoi(getenv("RALIGN_ZONES")) == 0) return RA_OK;
+    if (!rq.sw.zones) return RA_OK;
     const Geometry &g = e->geo;
     const int S = (int)std::ceil(std::max(g.nkx, g.nky) * g.step - 1e-6);
     if (!build_zone_plan(g, S, RA_ZONE_NW, e->dg.n_qtab, e->zplan)) return RA_OK;
@@ -1015,7 +949,7 @@ static int setup_zones(ra_engine *e)
     if ((rc = RA_LDS(e, polar_zone_kernel<RA_ZONE_NW>, zp.lds_bytes))) return rc;
     e->zdev.zones = e->d_zone_desc; e->zdev.rowtab = e->d_zone_rows; e->zdev.pixtab = e->d_zone_pix;
     e->zdev.nzone = (int)zp.zones.size(); e->zdev.nchunk = zp.nchunk; e->zdev.nquad_total = zp.nquad_total; e->zdev.max_rows = zp.max_rows;
-    if (getenv("RALIGN_INFO")) {
+    if (rq.sw.info) {
         fprintf(stderr, "libralign_hip: zone plan: %d zones, %zu bytes of LDS, %d offset chunks, S = %d:", e->zdev.nzone, zp.lds_bytes, zp.nchunk, S);
         for (const ZoneDesc &z : zp.zones) fprintf(stderr, " [rings %d..%d: %d px, %d rows]", z.ring0, std::min(z.ring0 + 4 * z.nquad, g.nring) - 1, z.npix, z.nrow);
         fprintf(stderr, "\n");
@@ -1030,11 +964,11 @@ static int setup_zones(ra_engine *e)
 // in all three stages once the states have moved.  The entries of a chunk then depend on its states: live_scan_kernel lays the ranges
 // out on the device, the kernels read the total there, the host launches for the full lists (empty slices return at once).
 // RALIGN_LIVE_OFFSETS=0: every offset of the list, masked later (as the particle-resident 90 x 90 kernels do).
-static int update_live_mode(ra_engine *e)
+static int update_live_mode(ra_engine *e, const PlanRequest &rq)
 {
     e->dg.ent_base = nullptr; e->dg.ent_total = nullptr;
     if (!e->generic || e->fused || e->solo) return RA_OK;
-    if (getenv("RALIGN_LIVE_OFFSETS") && atoi(getenv("RALIGN_LIVE_OFFSETS")) == 0) return RA_OK;
+    if (!rq.sw.live_offsets) return RA_OK;
     int rc;
     if (!e->d_ent_base && ((rc = dev_alloc(e, &e->d_ent_base, (size_t)e->chunk + 8, true)) || (rc = dev_alloc(e, &e->d_ent_total, 4, true)))) return rc;
     e->dg.ent_base = e->d_ent_base; e->dg.ent_total = e->d_ent_total;
@@ -1065,11 +999,11 @@ static int launch_generic_polar(ra_engine *e, const float *part, const float *st
 
 // tables and buffers of the sub-bin angle refinement (ralign_exact.h): twiddles (float) of the double-precision cos / sin for
 // every power-of-two length, as fftr_q's tables; exact reference spectra; the list of flagged particles of a chunk
-static int setup_refine(ra_engine *e)
+static int setup_refine(ra_engine *e, const PlanRequest &rq)
 {
     const Geometry &g = e->geo;
     e->refine_ok = false;
-    if (getenv("RALIGN_REFINE")) e->refine_thr = (float)atof(getenv("RALIGN_REFINE"));
+    if (rq.sw.refine) e->refine_thr = (float)atof(rq.sw.refine);
     e->lds_refine = refine_resident_lds(g);
     if (g.lcirc & 1) return RA_OK;
     // large boxes: one offset's rings exceed the LDS (271 KB at 256 x 256 / ou = 120) -- the same kernels with the ring buffers
@@ -1087,7 +1021,7 @@ static int setup_refine(ra_engine *e)
             return RA_ERR_HIP;
         }
     }
-    e->refine_gm = refine_rings_global(g);
+    e->refine_gm = refine_rings_global(g, rq);
     e->refine_grid = e->refine_gm ? 256 : 2048;
     if (e->refine_gm) e->lds_refine = RA_EXACT_TABLE_BYTES(g.maxrin);
     std::vector<float> tw;
@@ -1190,7 +1124,7 @@ static int ensure_unfused_ws(ra_engine *e)
 // the LDS-resident kernels cover <= 48 rings of 8..256 samples and images whose padded copy plus four ring buffers
 // fit one CU's LDS; everything else runs the size-generic kernels
 static ccf_fn select_ccf(int maxrin);
-static bool fits_specialised_kernels(const Geometry &g0, const ra_config &cfg)
+static bool fits_specialised_kernels(const Geometry &g0, const ra_config &cfg, const PlanRequest &rq)
 {
     bool fast = g0.nring <= 4 * RA_CCF_MAXNS && select_ccf(g0.maxrin) != nullptr && g0.numr[2] >= 8;
     const int bd0 = (int)std::ceil(std::max(cfg.xrng, cfg.yrng)) + 2, pst0 = g0.nx + 2 * bd0;
@@ -1202,36 +1136,40 @@ static bool fits_specialised_kernels(const Geometry &g0, const ra_config &cfg)
         if (ns != prev) { ncls++; prev = ns; }
     }
     if (ncls > 8) fast = false;
-    if (generic_forced()) fast = false;
+    if (rq.generic_forced()) fast = false;
     return fast;
 }
 
-static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options *opt, bool allow_tcrop);
+static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options *opt, const PlanRequest &rq);
 extern "C" int ra_create(ra_engine **out, const ra_config *cfg) { return ra_create_ex(out, cfg, nullptr); }
 extern "C" int ra_create_ex(ra_engine **out, const ra_config *cfg, const ra_options *opt)
 {
     if (opt && (opt->interp != RA_INTERP_BILINEAR && opt->interp != RA_INTERP_QUADRI)) { g_last_error = "bad interpolation"; return RA_ERR_ARG; }
     if (opt && (opt->normalize_ring < -1 || opt->normalize_ring > 1)) { g_last_error = "normalize_ring is -1 (by mode), 0 or 1"; return RA_ERR_ARG; }
-    ForceGenericScope scope(opt && opt->interp == RA_INTERP_QUADRI);
-    int rc = create_engine(out, cfg, opt, true);
+    const PlanRequest rq{read_switches(), opt && opt->interp == RA_INTERP_QUADRI, false, true};
+    int rc = create_engine(out, cfg, opt, rq);
     // the plan of the four-offset kernels over a crop of the image is promised by tcrop_wanted on an estimate of the tables; should
     // the real tables miss it, the engine is planned again without that path (pair or generic kernels) instead of failing
-    if (rc == RA_ERR_STATE) rc = create_engine(out, cfg, opt, false);
+    if (rc == RA_ERR_STATE) {
+        PlanRequest no_crop = rq;
+        no_crop.allow_tcrop = false;
+        rc = create_engine(out, cfg, opt, no_crop);
+    }
     // More than 16 references in a box whose image fits the LDS but leaves no room for the tiled kernel's plan beside it (100 - 128
     // pixels at ou = 21 .. 32) used to fall to the round-1 kernel pair (3.7 MB of HBM per particle): planned in the size-generic
     // class instead, the search runs search_tiled_kernel over a crop of the image.  Kept only when that plan exists.
-    if (rc == RA_OK && *out && !(*out)->generic && !(*out)->fused && cfg->nref > RF_MAXREF && (*out)->geo.maxrin == 256 && !generic_forced() &&
-        !(getenv("RALIGN_FUSED") && atoi(getenv("RALIGN_FUSED")) == 0)) {          // (RALIGN_FUSED=0 asks for the kernel pair)
+    if (rc == RA_OK && *out && !(*out)->generic && !(*out)->fused && cfg->nref > RF_MAXREF && (*out)->geo.maxrin == 256 && !rq.generic_forced() &&
+        rq.sw.fused) {          // (RALIGN_FUSED=0 asks for the kernel pair)
         ra_engine *alt = nullptr;
-        g_generic_class = true;
-        const int rc2 = create_engine(&alt, cfg, opt, true);
-        g_generic_class = false;
+        PlanRequest in_class = rq;
+        in_class.generic_class = true;
+        const int rc2 = create_engine(&alt, cfg, opt, in_class);
         if (rc2 == RA_OK && alt && (alt->fused || alt->solo)) { ra_destroy(*out); *out = alt; }
         else if (alt) ra_destroy(alt);
     }
     return rc;
 }
-static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options *opt, bool allow_tcrop)
+static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options *opt, const PlanRequest &rq)
 {
     if (!out || !cfg) { g_last_error = "null argument"; return RA_ERR_ARG; }
     *out = nullptr;
@@ -1252,7 +1190,7 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
     {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, cfg->device) == hipSuccess && prop.multiProcessorCount > 0) e->n_cu = prop.multiProcessorCount;
-        if (getenv("RALIGN_GRID") && atoi(getenv("RALIGN_GRID")) > 0) e->n_cu = atoi(getenv("RALIGN_GRID"));      // experiments: fewer persistent workgroups
+        if (rq.sw.grid > 0) e->n_cu = rq.sw.grid;      // experiments: fewer persistent workgroups
     }
     if (!build_rings(e->geo, cfg->nx, cfg->first_ring, cfg->last_ring, cfg->ring_skip > 0 ? cfg->ring_skip : 1) ||
         !build_shifts(e->geo, cfg->xrng, cfg->yrng, cfg->step)) {
@@ -1260,11 +1198,10 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
         delete e;
         return RA_ERR_ARG;
     }
-    e->force_generic = g_force_generic;
-    e->no_tcrop = !allow_tcrop;
-    e->generic = !fits_specialised_kernels(e->geo, *cfg) || g_generic_class;
-    e->tcrop = tcrop_wanted(e);
-    if (!e->tcrop && allow_tcrop && e->generic && e->geo.maxrin == 256 && !(getenv("RALIGN_TIGHT_RINGS") && atoi(getenv("RALIGN_TIGHT_RINGS")) == 0)) {
+    e->force_generic = rq.option_generic;
+    e->generic = !fits_specialised_kernels(e->geo, *cfg, rq) || rq.generic_class;
+    e->tcrop = tcrop_wanted(e, rq);
+    if (!e->tcrop && rq.allow_tcrop && e->generic && e->geo.maxrin == 256 && rq.sw.tight_rings) {
         // ou = 37 ... 40: crop + four ring buffers miss the LDS by 4 - 8 KB, of which the 16 padding floats per ring are 10 KB.  With
         // rings 4 floats apart (the in-place real transform needs 2; 4 keeps every ring 16-byte aligned) the four-offset kernels take
         // the class from the pair kernel (RALIGN_TIGHT_RINGS=0: the pair kernel)
@@ -1276,7 +1213,7 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
         if (build_rings(g4, cfg->nx, cfg->first_ring, cfg->last_ring, cfg->ring_skip > 0 ? cfg->ring_skip : 1, pad) &&
             build_shifts(g4, cfg->xrng, cfg->yrng, cfg->step)) {
             e->geo = g4;
-            e->tcrop = tcrop_wanted(e);
+            e->tcrop = tcrop_wanted(e, rq);
             if (!e->tcrop) e->geo = g16;
         }
     }
@@ -1289,7 +1226,8 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
     }
     e->nrtile = (cfg->nref + 7) / 8;
     e->dg.rpt = (cfg->nref + e->nrtile - 1) / e->nrtile;      // balanced reference tiles (10 -> 5 + 5)
-    int rc = build_device_geometry(e);
+    decide_class(e, rq);
+    int rc = build_device_geometry(e, rq);
     if (rc) { ra_destroy(e); return rc; }
     if (opt) {
         e->dg.interp = opt->interp;
@@ -1340,7 +1278,7 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
 
     // workspace.  The spectra panels and candidate records of the two-kernel path are allocated on first use only
     // (ensure_unfused_ws); the fused kernel needs candidate records alone.
-    const WorkspacePlan wp = plan_workspace(g, *cfg, e->generic);
+    const WorkspacePlan wp = plan_workspace(g, *cfg, rq, e->generic);
     e->wp = wp;
     e->chunk = wp.chunk;
     if ((rc = dev_alloc(e, &e->d_refspec, wp.refspec_floats, true)) ||
@@ -1356,12 +1294,12 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
         if ((rc = dev_alloc(e, &e->d_gstats, (size_t)wp.chunk * g.nshift_pad + 8, true)) ||
             (rc = dev_alloc(e, &e->d_gcdc, (size_t)cfg->nref, true))) { ra_destroy(e); return rc; }
     }
-    if ((rc = setup_fused(e))) { ra_destroy(e); return rc; }
-    if ((rc = setup_solo(e))) { ra_destroy(e); return rc; }
-    if ((rc = setup_zones(e))) { ra_destroy(e); return rc; }
-    if ((rc = update_live_mode(e))) { ra_destroy(e); return rc; }
-    if ((rc = setup_refine(e))) { ra_destroy(e); return rc; }
-    e->atomic_sums = getenv("RALIGN_ATOMIC_SUMS") && atoi(getenv("RALIGN_ATOMIC_SUMS")) != 0;
+    if ((rc = setup_fused(e, rq))) { ra_destroy(e); return rc; }
+    if ((rc = setup_solo(e, rq))) { ra_destroy(e); return rc; }
+    if ((rc = setup_zones(e, rq))) { ra_destroy(e); return rc; }
+    if ((rc = update_live_mode(e, rq))) { ra_destroy(e); return rc; }
+    if ((rc = setup_refine(e, rq))) { ra_destroy(e); return rc; }
+    e->atomic_sums = rq.sw.atomic_sums;
     *out = e;
     return RA_OK;
 }
@@ -1463,7 +1401,7 @@ extern "C" int ra_lcirc(const ra_engine *e) { return e ? e->geo.lcirc : RA_ERR_A
 extern "C" int ra_reset_shifts(ra_engine *e, float xrng, float yrng, float step)
 {
     if (!e) return RA_ERR_ARG;
-    ForceGenericScope scope(e->force_generic);
+    const PlanRequest rq{read_switches(), e->force_generic, false, false};      // (generic class and crop were decided at create: e->generic, e->tcrop)
     Geometry g2 = e->geo;
     if (!build_shifts(g2, xrng, yrng, step)) { g_last_error = "bad shift window"; return RA_ERR_ARG; }
     // the reference asserts the offset count does not change (gpu_aln_noref.cu:135); we only
@@ -1495,13 +1433,14 @@ extern "C" int ra_reset_shifts(ra_engine *e, float xrng, float yrng, float step)
     e->cfg.xrng = xrng; e->cfg.yrng = yrng; e->cfg.step = step;
     e->dg.nkx = g2.nkx; e->dg.nky = g2.nky; e->dg.nshift = g2.nshift; e->dg.nshift_pad = g2.nshift_pad; e->dg.ent_stride = e->generic ? g2.nshift : g2.nshift_pad;
     e->dg.step = step; e->dg.xrng = xrng; e->dg.yrng = yrng;
-    int rc = setup_fused(e);
+    decide_class(e, rq);
+    int rc = setup_fused(e, rq);
     // the solo / duo / pair kernels keep a crop of the image whose side follows the search range: plan again (a wider range at a
     // constant offset count, e.g. xr = 1, ts = 0.5 -> xr = 4, ts = 2, would otherwise let taps leave the crop)
     // (also when the previous window made the plan fall back to the generic kernels: the new one may fit again)
-    if (!rc && e->generic && !e->fused && (e->solo || solo_wanted(e) || pair_wanted(e))) rc = setup_solo(e);
-    if (!rc) rc = setup_zones(e);          // the zones' annuli follow the search range
-    if (!rc) rc = update_live_mode(e);     // (the plan may have moved between the particle-resident and the size-generic kernels)
+    if (!rc && e->generic && !e->fused && (e->solo || e->want.solo || e->want.pair)) rc = setup_solo(e, rq);
+    if (!rc) rc = setup_zones(e, rq);        // the zones' annuli follow the search range
+    if (!rc) rc = update_live_mode(e, rq);   // (the plan may have moved between the particle-resident and the size-generic kernels)
     return rc;
 }
 
@@ -1791,7 +1730,7 @@ extern "C" int ra_align(ra_engine *e, const float *d_particles, int n, float *d_
         // launch stays a bounded unit of work (timing, candidate workspace)
         FusedGeom f = e->fplan.f;
         // dense offset stream: a template parameter of search_fused_kernel, a run-time flag of search_tiled_kernel (RALIGN_PACK=0: off)
-        f.pack = e->tiled && g.nshift % 4 != 0 && g.nshift >= 4 && !(getenv("RALIGN_PACK") && atoi(getenv("RALIGN_PACK")) == 0);
+        f.pack = e->tiled && g.nshift % 4 != 0 && g.nshift >= 4 && pack_allowed();
         fused_fn fk = e->tiled ? select_tiled(f.nh, e->dg.sbuf) : select_fused(g.maxrin, e->cfg.nref, e->fplan.f.nzr, e->dg.sbuf, pack_ok(e), e->tcrop);
         const int rch = resident_batch(e, n);
         {
@@ -1849,8 +1788,8 @@ extern "C" int ra_align(ra_engine *e, const float *d_particles, int n, float *d_
         const int n_mtile = (cn * e->dg.ent_stride + 7) / 8;
         if (evc) RA_HIP(hipEventRecord(evc->first, sp));
         // blocks of TM x 7 tiles when the reference tiles come in sevens (gccf_tm): the B stream is read once per 8 TM particle-offsets
-        const bool split = e->generic && g.maxrin == 1024 && !(getenv("RALIGN_GCCF_SPLIT") && atoi(getenv("RALIGN_GCCF_SPLIT")) == 0);
-        const int tmv = e->generic ? gccf_tm(e->nrtile, g.maxrin) : 1;
+        const bool split = e->generic && g.maxrin == 1024 && env_int("RALIGN_GCCF_SPLIT", 1) != 0;
+        const int tmv = e->generic ? gccf_tm(e->nrtile, g.maxrin, env_int("RALIGN_GCCF_TM", 0)) : 1;
         const bool tm2 = tmv >= 2 && gccf_wide_blocks(e->nrtile);
         if (tm2 && !split)
             hipLaunchKernelGGL((ccf_generic_kernel<2, 7>), dim3(std::min((n_mtile + 1) / 2, e->g_nblk)), dim3(RA_GCCF_THREADS), e->lds_gccf, sp, e->dg,
@@ -1985,9 +1924,9 @@ static bool xs_whole_image(const ra_engine *e)
 static bool xs_usable(const ra_engine *e)
 {
     if (e->atomic_sums) return false;
-    if (getenv("RALIGN_XSUM") && atoi(getenv("RALIGN_XSUM")) == 0) return false;
+    if (env_int("RALIGN_XSUM", 1) == 0) return false;
     if (xs_whole_image(e)) return true;
-    return e->geo.nx >= RA_XT_BB && !(getenv("RALIGN_XTILE") && atoi(getenv("RALIGN_XTILE")) == 0);
+    return e->geo.nx >= RA_XT_BB && env_int("RALIGN_XTILE", 1) != 0;
 }
 static int transform_sum(ra_engine *e, const float *d_particles, int n, int index0, const ra_result *d_result, float *d_sums, int *d_counts)
 {
@@ -2429,9 +2368,12 @@ size_t ra_planned_workspace_bytes(const ra_config *rc)
     Geometry g;
     if (!build_rings(g, rc->nx, rc->first_ring, rc->last_ring, rc->ring_skip) || !build_shifts(g, rc->xrng, rc->yrng, rc->step))
         return (size_t)-1;
-    const bool generic = !fits_specialised_kernels(g, *rc);
+    // the FIRST plan of ra_create with default options: the estimate knows nothing of ra_options, the tight-ring geometry or the
+    // generic-class second attempt of ra_create_ex
+    const PlanRequest rq{read_switches(), false, false, true};
+    const bool generic = !fits_specialised_kernels(g, *rc, rq);
     if (generic && g.maxrin <= 1024) align_ring_quads(g);      // as ra_create: the panel size follows the layout
-    return plan_workspace(g, *rc, generic).bytes;
+    return plan_workspace(g, *rc, rq, generic).bytes;
 }
 
 // ---- rot_shift2D without an engine (it launches the engine's transform kernels)

@@ -476,11 +476,10 @@ inline int gccf_blocks_per_wg()
     const int v = ev ? atoi(ev) : 0;
     return v >= 1 && v <= 8 ? v : 2;
 }
-inline int gccf_tm(int nrtile, int maxrin)
+// (v: the value of RALIGN_GCCF_TM, 0 when it is not set)
+inline int gccf_tm(int nrtile, int maxrin, int v)
 {
     if (!gccf_wide_blocks(nrtile)) return 1;
-    const char *ev = getenv("RALIGN_GCCF_TM");
-    const int v = ev ? atoi(ev) : 0;
     if (v == 1 || v == 2 || (v == 4 && maxrin == 1024)) return v;
     return maxrin == 1024 ? 4 : 1;
 }

@@ -48,7 +48,7 @@ inline SoloLds pair_lds_plan(int N, int rows, int pst, int sbuf, int n_qtab, int
 }
 
 // n_qtab, n_inst, n_job: sizes of the job tables build_device_geometry made for TWO offset slots
-inline bool build_pair_plan(const Geometry &g, int nref, int n_qtab, int n_inst, int n_job, FusedPlanHost &out)
+inline bool build_pair_plan(const Geometry &g, int nref, int n_qtab, int n_inst, int n_job, bool crop_allowed, FusedPlanHost &out)
 {
     FusedGeom &f = out.f;
     f = FusedGeom{};
@@ -57,7 +57,7 @@ inline bool build_pair_plan(const Geometry &g, int nref, int n_qtab, int n_inst,
     f.ng = g.maxrin / 32; f.wpg = 2;
     f.nrp = (nref + 1) / 2;
     const int zstride = 2 * (g.maxrin + g.maxrin / 16) + 2;
-    crop_plan(g, f);
+    crop_plan(g, f, crop_allowed);
     // references per tile: 2 offsets x RZ spectra in the two ring buffers, which grow past the rings' own length when the LDS has the
     // room (ou 36: 12 spectra need 6552 floats, the rings 5.7 k -- without the slack 96 x 96 / ou 36 fell back to the generic kernels)
     // row stride of a crop: 101 words (the 90 x 90 headline geometry's, as for the engines that run its kernels over a crop: 35.9 ->

@@ -66,11 +66,12 @@ inline SoloLds solo_lds_plan(int N, int rows, int pst, int sbuf, int n_qtab, int
 // ou + (largest search shift) + 1 of its sampling centre only, so a box much larger than the rings (256 x 256 around ou = 40) need
 // not be resident: the image is a CROP of 2 (ou + S) + 5 columns and rows whose origin follows the particle's centre (clamped to
 // the box), plus the never-written zero row / column the tap of weight 0 at the box's edge may read.  Returns the resident columns.
-inline int crop_plan(const Geometry &g, FusedGeom &f)
+// crop_allowed: the RALIGN_CROP switch of the plan request (false: the whole image)
+inline int crop_plan(const Geometry &g, FusedGeom &f, bool crop_allowed)
 {
     const int S = (int)std::ceil(std::max(g.nkx, g.nky) * g.step - 1e-6);
     const int side = 2 * (S + g.last_ring) + 5;
-    const bool crop = side < g.nx && !(getenv("RALIGN_CROP") && atoi(getenv("RALIGN_CROP")) == 0);
+    const bool crop = side < g.nx && crop_allowed;
     f.s_crop = crop ? side : 0;
     f.s_cropm = S + g.last_ring + 1;
     const int cols = crop ? side : g.nx;
@@ -87,7 +88,7 @@ __device__ __forceinline__ int crop_origin(const FusedGeom &f, int nx, float cen
 }
 
 // n_qtab, n_inst, n_job: sizes of the job tables build_device_geometry made for ONE offset slot
-inline bool build_solo_plan(const Geometry &g, int nref, int n_qtab, int n_inst, int n_job, FusedPlanHost &out)
+inline bool build_solo_plan(const Geometry &g, int nref, int n_qtab, int n_inst, int n_job, bool crop_allowed, FusedPlanHost &out)
 {
     FusedGeom &f = out.f;
     f = FusedGeom{};
@@ -103,7 +104,7 @@ inline bool build_solo_plan(const Geometry &g, int nref, int n_qtab, int n_inst,
     rf_layout_b(g, nref, f, out.bsrc);
     // image without a search-range border; the row stride keeps vertical and diagonal neighbours out of one LDS bank
     // (as build_device_geometry does for the bordered image)
-    crop_plan(g, f);
+    crop_plan(g, f, crop_allowed);
     const int zstride = 2 * (g.maxrin + g.maxrin / 16) + 2;
     f.s_sbuf = std::max((g.lring + 31) / 32 * 32 + 16, f.rz * zstride);
     // ring jobs: longest first, wave w runs jobs rank[w], rank[w] + 16, ..; the waves with the highest ranks have no job in a
