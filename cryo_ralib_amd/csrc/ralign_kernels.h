@@ -429,6 +429,13 @@ __device__ __forceinline__ void ring_fft_all(const DevGeom &g, float *bufs, int 
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");       \
     } while (0)
 
+// counting builds (-DRALIGN_MARK_PHASES) leave a comment line in the assembly at the edges of a phase; nothing otherwise
+#ifdef RALIGN_MARK_PHASES
+#define RA_PHASE_MARK(name) asm volatile("; RA_PHASE " name)
+#else
+#define RA_PHASE_MARK(name) do {} while (0)
+#endif
+
 // `nlive`: offset slots >= nlive are padding and skipped.
 // `part` receives the Normalize_ring partial sums {sum w x, sum w x^2} of every (offset slot, ring).  NYQ1 (fused
 // search kernel): the Nyquist coefficient of a full-length ring (n == maxrin) is stored in the imaginary slot of
@@ -438,7 +445,11 @@ __device__ __forceinline__ void ring_fft_all(const DevGeom &g, float *bufs, int 
 // (their spectra occupy the ring buffers), so a wave samples while the others still transform.
 struct NoSync { __device__ __forceinline__ void operator()() const {} };
 
-template <int R1, int LR, bool NYQ1 = false, class Sync = NoSync>
+// EARLY: the split step's reads (the twiddles; in the generic schedule Z_k and Z_{H-k} too) are all requested before the first pair
+// is combined, so the job waits for them once.  That holds up to 3 LR / 2 more values in registers at that point: a gain in the
+// kernels that have the registers (fused, tiled), a loss in one that sits at the 128-register limit (pair), see
+// profiles/ring_fft_diet_ab.txt.
+template <int R1, int LR, bool NYQ1 = false, bool EARLY = false, class Sync = NoSync>
 __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, float *bufs, const float2 *tw_s,
                                          const float2 *qt_s, const float *ctr, float *part, const int4 *inst_s,
                                          const float *instw_s, int inst0, int count, int zero, int sbuf, int nlive = 4,
@@ -530,63 +541,85 @@ __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, fl
         for (int a = 0; a < R1; a++) *reinterpret_cast<float2 *>(buf + 2 * (LR * a + t)) = v[a];
         return;
     }
+    RA_PHASE_MARK("ring_fft_begin");
     Dft<-1, R1>::run(v);
     constexpr int LGH = __builtin_ctz(H), LGNR = LGH + 1;
     const int tstep = t << (g.lg_maxrin - LGH);      // t * maxrin / H
-    // element (row c, column t) is parked at LR*c + ((t + c) mod LR): conflict-free both ways
+    const int lsh = g.lg_maxrin - LGNR;              // the split step's twiddle of bin k is tw_s[k << lsh]
+    // Element (row c, column t) is parked at LR*c + (t ^ (c mod LR)): conflict-free both ways (the columns of a row and the
+    // rows of a column are permuted inside aligned groups of LR complex values).  A lane meets at most LR - 1 swizzled
+    // columns, on the way in and on the way out: each is one xor-add on the ring's base, formed once and shared by all the
+    // rows that use it; the row itself is an immediate offset of the write or the read.
+    char *const bufb = reinterpret_cast<char *>(buf);
 #pragma unroll
     for (int c = 0; c < R1; c++) {
         float2 o = v[c];
         if (c > 0) o = cmul(o, tw_s[__mul24(tstep, c)]);      // t c < H: no wrap; 24-bit multiplies are full rate, v_mul_lo_u32 is not
-        *reinterpret_cast<float2 *>(buf + 2 * (LR * c + ((t + c) & (LR - 1)))) = o;
+        *reinterpret_cast<float2 *>(bufb + ((8 * t) ^ (8 * (c & (LR - 1)))) + 8 * LR * c) = o;
     }
     RA_WAVE_SYNC();
-    // real-FFT split step of one pair: X_k and X_{H-k} from Z_k, Z_{H-k} (k = 0 gives X_0 and the Nyquist term X_H)
-    auto split_pair = [&](float2 zk, float2 zm, int k, float2 &xk, float2 &xm) {
-        v2f a, b;
-        vsplit_pair(to_v(zk), to_v(zm), to_v(tw_s[k << (g.lg_maxrin - LGNR)]), a, b);
-        xk = to_f2(a); xm = to_f2(b);
+    // The reads' own copy of 8 t.  As one value with the writes' the compiler shares the xor and spends a second add on every
+    // address; apart, each swizzled column is one v_xad_u32: 7 instructions less per 256-sample job (hipcc of ROCm 7.2; a
+    // compiler that does not share them loses nothing by the empty asm).
+    int t8r = 8 * t;
+    asm("" : "+v"(t8r));
+    // row `row` (any of the ring) into z[0 .. LR-1], column order; rowb: the row's byte address, swz: 8 * (row mod LR)
+    // X_0 and X_H, both real, from Z_0 (lane 0 of the ring)
+    auto store_dc = [&](float2 z0) {
+        if (NYQ1 && NR == g.maxrin) {
+            *reinterpret_cast<float2 *>(buf) = make_float2(z0.x + z0.y, z0.x - z0.y);
+        } else {
+            *reinterpret_cast<float2 *>(buf) = make_float2(z0.x + z0.y, 0.f);
+            *reinterpret_cast<float2 *>(buf + 2 * H) = make_float2(z0.x - z0.y, 0.f);
+        }
+    };
+    auto load_row = [&](const char *rowb, int swz, float2 *z) {
+#pragma unroll
+        for (int b = 0; b < LR; b++) z[b] = *reinterpret_cast<const float2 *>(rowb + (swz ^ (8 * b)));
     };
     if constexpr (R1 == 2 * LR) {
         // Two rows per lane, chosen so that the split step stays inside the lane: lane t transforms rows t and R1 - t
         // (lane 0: rows 0 and R1/2), and Z_{H-k} of every k = row + R1 e of one row is element LR-1-e of the other
         // (rows 0 and R1/2 pair with themselves).  The second-pass output never goes back to LDS: one write and one
         // read of every element and one wave hand-off less than the generic schedule below.
-        const int rowA = t, rowB = t ? R1 - t : R1 / 2;
+        const bool l0 = t == 0;
+        const int rowB = l0 ? R1 / 2 : R1 - t;
         float2 z[2][LR];
+        load_row(bufb + 8 * LR * t, t8r, z[0]);
+        load_row(bufb + 8 * LR * rowB, 8 * (rowB & (LR - 1)), z[1]);
+        // Pair i of lane t > 0 is (Z[k], Z[H - k]) with k = t + R1 i.  Lane 0 takes row R1/2 for i < LR/2 (k = R1/2 + R1 i), then
+        // row 0 (k = R1 (i - LR/2 + 1)): per half of the loop k is a lane base plus a multiple of R1, and so are the addresses of
+        // the pair's twiddle and of its two outputs -- immediate offsets of four lane bases.  EARLY: the twiddles are requested
+        // here, ahead of the transforms: they arrive with the rows, and the split step below waits for nothing.
+        const int kb0 = l0 ? R1 / 2 : t, kb1 = l0 ? R1 : t + H / 2;
+        const float2 *twp[2] = {tw_s + (kb0 << lsh), tw_s + (kb1 << lsh)};
+        float2 w[LR];
+        if constexpr (EARLY) {
 #pragma unroll
-        for (int b = 0; b < LR; b++) z[0][b] = *reinterpret_cast<const float2 *>(buf + 2 * (LR * rowA + ((b + rowA) & (LR - 1))));
-#pragma unroll
-        for (int b = 0; b < LR; b++) z[1][b] = *reinterpret_cast<const float2 *>(buf + 2 * (LR * rowB + ((b + rowB) & (LR - 1))));
+            for (int i = 0; i < LR; i++) w[i] = twp[i >= LR / 2][(R1 * (i % (LR / 2))) << lsh];
+        }
         Dft<-1, LR>::run(z[0]);
         Dft<-1, LR>::run(z[1]);
         RA_WAVE_SYNC();                  // every lane of the ring has its rows: the buffer may be overwritten
-        const bool l0 = t == 0;
+        float *const xkp[2] = {buf + 2 * kb0, buf + 2 * kb1};
+        float *const xmp[2] = {buf + 2 * (H / 2 + R1 - kb0), buf + 2 * (H / 2 + R1 - kb1)};       // H - k of the LAST pair of the half
 #pragma unroll
         for (int i = 0; i < LR; i++) {
             // lane t > 0: (Z[t + R1 i], Z[R1 - t + R1 (LR-1-i)]); lane 0: row R1/2 for i < LR/2, then row 0 (e = 1 .. LR/2)
-            const int e0 = i < LR / 2 ? i : i - LR / 2 + 1;
-            const float2 zk0 = i < LR / 2 ? z[1][e0] : z[0][e0];
-            const float2 zm0 = i < LR / 2 ? z[1][LR - 1 - e0] : z[0][(LR - e0) & (LR - 1)];
-            const int k0 = i < LR / 2 ? LR + R1 * e0 : R1 * e0;
+            constexpr int HL = LR / 2;
+            const int e0 = i < HL ? i : i - HL + 1, hf = i >= HL, j = i % HL;
+            const float2 zk0 = i < HL ? z[1][e0] : z[0][e0];
+            const float2 zm0 = i < HL ? z[1][LR - 1 - e0] : z[0][(LR - e0) & (LR - 1)];
             float2 zk, zm;
             zk.x = l0 ? zk0.x : z[0][i].x; zk.y = l0 ? zk0.y : z[0][i].y;
             zm.x = l0 ? zm0.x : z[1][LR - 1 - i].x; zm.y = l0 ? zm0.y : z[1][LR - 1 - i].y;
-            const int k = l0 ? k0 : t + R1 * i;
-            float2 xk, xm;
-            split_pair(zk, zm, k, xk, xm);
-            *reinterpret_cast<float2 *>(buf + 2 * (H - k)) = xm;      // lane 0, last step: k = H/2 = H - k, X_k lands last
-            *reinterpret_cast<float2 *>(buf + 2 * k) = xk;
+            v2f xk, xm;
+            if constexpr (!EARLY) w[i] = twp[hf][(R1 * j) << lsh];
+            vsplit_pair(to_v(zk), to_v(zm), to_v(w[i]), xk, xm);
+            *reinterpret_cast<float2 *>(xmp[hf] + 2 * R1 * (HL - 1 - j)) = to_f2(xm);      // lane 0, last step: k = H/2 = H - k, X_k lands last
+            *reinterpret_cast<float2 *>(xkp[hf] + 2 * R1 * j) = to_f2(xk);
         }
-        if (l0) {
-            const float2 zk = z[0][0];
-            if (NYQ1 && NR == g.maxrin) {
-                *reinterpret_cast<float2 *>(buf) = make_float2(zk.x + zk.y, zk.x - zk.y);
-            } else {
-                *reinterpret_cast<float2 *>(buf) = make_float2(zk.x + zk.y, 0.f);
-                *reinterpret_cast<float2 *>(buf + 2 * H) = make_float2(zk.x - zk.y, 0.f);
-            }
-        }
+        if (l0) store_dc(z[0][0]);
     } else {
         // second pass: the R1 rows of the LR-point transforms are dealt to the LR lanes of the ring
         // (one row per lane when R1 <= LR, R1/LR rows per lane otherwise: no idle half-groups)
@@ -594,10 +627,9 @@ __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, fl
         float2 z[NROW][LR];
 #pragma unroll
         for (int m = 0; m < NROW; m++) {
-            const int row = t + LR * m;
+            const int row = t + LR * m;       // row mod LR = t: the rows of a lane share their swizzled columns
             if (row < R1) {
-#pragma unroll
-                for (int b = 0; b < LR; b++) z[m][b] = *reinterpret_cast<const float2 *>(buf + 2 * (LR * row + ((b + row) & (LR - 1))));
+                load_row(bufb + 8 * LR * row, t8r, z[m]);
                 Dft<-1, LR>::run(z[m]);
             }
         }
@@ -612,24 +644,49 @@ __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, fl
         }
         RA_WAVE_SYNC();
         // split step X_k <- (Z_k, Z_{H-k}), k = 0..H/2, in place; X_0 and X_H are real
-        for (int k = t; k <= H / 2; k += LR) {
-            float2 zk = *reinterpret_cast<const float2 *>(buf + 2 * k);
-            if (k == 0) {
-                if (NYQ1 && NR == g.maxrin) {
-                    *reinterpret_cast<float2 *>(buf) = make_float2(zk.x + zk.y, zk.x - zk.y);
+        constexpr int NI = H / 2 / LR;
+        if constexpr (EARLY && NI >= 1) {
+            // Pair i of a lane is k = t + LR i, except that lane 0 takes k = H/2 (which pairs with itself) in place of k = 0,
+            // whose two real terms follow the loop.  Every pair is read and written by one lane only, so all the reads of a
+            // lane -- Z_k, Z_{H-k} and the twiddle, at immediate offsets of the lane's bases -- go out before the first pair is
+            // combined: one wait per job.
+            const bool l0 = t == 0;
+            const int k0 = l0 ? H / 2 : t;
+            float *const pk0 = buf + 2 * k0, *const pm0 = buf + 2 * (H - k0);
+            float *const pk = buf + 2 * t, *const pm = buf + 2 * (H - LR * (NI - 1) - t);
+            const float2 *const tw0 = tw_s + (k0 << lsh), *const twt = tw_s + (t << lsh);
+            float2 zk[NI], zm[NI], w[NI];
+#pragma unroll
+            for (int i = 0; i < NI; i++) {
+                zk[i] = *reinterpret_cast<const float2 *>(i ? pk + 2 * LR * i : pk0);
+                zm[i] = *reinterpret_cast<const float2 *>(i ? pm + 2 * LR * (NI - 1 - i) : pm0);
+                w[i] = i ? twt[(LR * i) << lsh] : *tw0;
+            }
+            const float2 zdc = *reinterpret_cast<const float2 *>(buf);
+#pragma unroll
+            for (int i = 0; i < NI; i++) {
+                v2f xk, xm;
+                vsplit_pair(to_v(zk[i]), to_v(zm[i]), to_v(w[i]), xk, xm);
+                *reinterpret_cast<float2 *>(i ? pm + 2 * LR * (NI - 1 - i) : pm0) = to_f2(xm);     // lane 0, i = 0: k = H/2 = H - k, X_k lands last
+                *reinterpret_cast<float2 *>(i ? pk + 2 * LR * i : pk0) = to_f2(xk);
+            }
+            if (l0) store_dc(zdc);
+        } else {
+            for (int k = t; k <= H / 2; k += LR) {
+                float2 zk = *reinterpret_cast<const float2 *>(buf + 2 * k);
+                if (k == 0) {
+                    store_dc(zk);
                 } else {
-                    *reinterpret_cast<float2 *>(buf) = make_float2(zk.x + zk.y, 0.f);
-                    *reinterpret_cast<float2 *>(buf + 2 * H) = make_float2(zk.x - zk.y, 0.f);
+                    float2 zm = *reinterpret_cast<const float2 *>(buf + 2 * (H - k));
+                    v2f xk, xm;
+                    vsplit_pair(to_v(zk), to_v(zm), to_v(tw_s[k << lsh]), xk, xm);
+                    *reinterpret_cast<float2 *>(buf + 2 * k) = to_f2(xk);
+                    if (2 * k != H) *reinterpret_cast<float2 *>(buf + 2 * (H - k)) = to_f2(xm);
                 }
-            } else {
-                float2 zm = *reinterpret_cast<const float2 *>(buf + 2 * (H - k));
-                float2 xk, xm;
-                split_pair(zk, zm, k, xk, xm);
-                *reinterpret_cast<float2 *>(buf + 2 * k) = xk;
-                if (2 * k != H) *reinterpret_cast<float2 *>(buf + 2 * (H - k)) = xm;
             }
         }
     }
+    RA_PHASE_MARK("ring_fft_end");
     // Normalize_ring partial sums of this ring -> its own slot (summed in ring order later)
     av = group_sum_dpp<LR>(av); sq = group_sum_dpp<LR>(sq);
     if (t == 0) { part[2 * (slot * g.nring + ring)] = av; part[2 * (slot * g.nring + ring) + 1] = sq; }
