@@ -81,6 +81,7 @@ EXPORTED_SYMBOLS = [
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
+    "ra_hdbscan_core", "ra_hdbscan_round",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
 ]
 
@@ -209,6 +210,8 @@ def load_library(path=None):
     L.ra_gmm_mstep.argtypes = [vp, ci, ci, ci, ci, vp, ci, ctypes.c_double, vp, vp, vp, vp]
     L.ra_dbscan_count.argtypes = [vp, ci, ci, ctypes.c_double, ci, vp, vp, vp]
     L.ra_dbscan_step.argtypes = [vp, ci, ci, ctypes.c_double, vp, ci, vp, vp, vp, vp]
+    L.ra_hdbscan_core.argtypes = [vp, ci, ci, ci, vp, vp]
+    L.ra_hdbscan_round.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -407,6 +410,12 @@ def dbscan(X, eps, **kw):
     """DBSCAN of X [n][d] (dbscan.dbscan): DbscanResult with labels (-1 for noise), core_mask, core_sample_indices, n_clusters, ..."""
     from . import dbscan as _dbscan
     return _dbscan.dbscan(X, eps, **kw)
+
+
+def hdbscan(X, **kw):
+    """HDBSCAN of X [n][d] (hdbscan.hdbscan): HdbscanResult with labels (-1 for noise), probabilities, tie_mask, n_clusters, ..."""
+    from . import hdbscan as _hdbscan
+    return _hdbscan.hdbscan(X, **kw)
 
 
 def dbscan_kdistances(X, min_samples, **kw):

@@ -1,9 +1,11 @@
-// t-SNE, k-means, cluster validity and DBSCAN of 2SDR factors (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h, ralign_dbscan.h):
-// the engine-less ra_tsne_*, ra_kmeans_* and ra_dbscan_* entry points of libralign_hip.so, each on the caller's stream.
+// t-SNE, k-means, cluster validity, DBSCAN and HDBSCAN of 2SDR factors (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h,
+// ralign_dbscan.h, ralign_hdbscan.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_* and ra_hdbscan_* entry points of
+// libralign_hip.so, each on the caller's stream.
 #include "ralign_host.h"
 #include "ralign_kmeans.h"
 #include "ralign_validity.h"
 #include "ralign_dbscan.h"
+#include "ralign_hdbscan.h"
 
 using namespace ralign;
 
@@ -397,4 +399,59 @@ extern "C" int ra_dbscan_step(const float *d_x, int n, int d, double eps, const 
     RA_LAUNCH(he, dbs_compress_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, d_label, (const int *)m, (const int *)P,
               d_label_out, d_changed);
     return he == hipSuccess ? RA_OK : hip_error("ra_dbscan_step", he);
+}
+
+// ---- HDBSCAN (ralign_hdbscan.h)
+
+static bool hdb_shape_ok(const char *what, int n, int d)
+{
+    if (n < 2 || n > HDB_MAX_N || d < 1 || d > HDB_MAX_D) {
+        set_error(std::string(what) + ": need 2 <= n <= 262144 and 1 <= d <= 2048");
+        return false;
+    }
+    return true;
+}
+
+extern "C" int ra_hdbscan_core(const float *d_x, int n, int d, int min_samples, double *d_core2, void *hip_stream)
+{
+    if (!hdb_shape_ok("ra_hdbscan_core", n, d)) return RA_ERR_ARG;
+    if (min_samples < 1 || min_samples > std::min(n, HDB_MAX_MIN_SAMPLES))
+        return arg_error("ra_hdbscan_core: need 1 <= min_samples <= min(n, 302)");
+    if (!d_x || !d_core2) return arg_error("ra_hdbscan_core: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int k = min_samples - 1;
+    if (k == 0) {
+        const hipError_t he = hipMemsetAsync(d_core2, 0, (size_t)n * sizeof(double), stream);
+        return he == hipSuccess ? RA_OK : hip_error("ra_hdbscan_core", he);
+    }
+    StreamScratch scratch(stream);
+    int *idx = scratch.get<int>((size_t)n * k);
+    double *dist2 = scratch.get<double>((size_t)n * k);
+    if (!idx || !dist2) return hip_error("ra_hdbscan_core", scratch.status());
+    if (const int rc = ra_tsne_knn(d_x, n, d, k, idx, dist2, hip_stream)) return rc;
+    // the neighbour comes from the list; the stored value is rule 2's chain to it, not the list's distance
+    hipLaunchKernelGGL(hdb_core_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, (const int *)idx, k, d_core2);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_hdbscan_core", he);
+}
+
+extern "C" int ra_hdbscan_round(const float *d_x, int n, int d, const double *d_core2, const int *d_comp, double *d_w2, int *d_lo, int *d_hi,
+                                void *hip_stream)
+{
+    if (!hdb_shape_ok("ra_hdbscan_round", n, d)) return RA_ERR_ARG;
+    if (!d_x || !d_core2 || !d_comp || !d_w2 || !d_lo || !d_hi) return arg_error("ra_hdbscan_round: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nt = (n + 255) / 256;
+    StreamScratch scratch(stream);
+    unsigned long long *buf = scratch.get<unsigned long long>((size_t)4 * n);
+    if (!buf) return hip_error("ra_hdbscan_round", scratch.status());
+    unsigned long long *roww = buf, *rowe = buf + n, *cw = buf + 2 * (size_t)n, *ce = buf + 3 * (size_t)n;
+    hipError_t he = hipMemsetAsync(cw, 0xff, (size_t)2 * n * sizeof(unsigned long long), stream);       // HDB_NONE
+    RA_LAUNCH(he, hdb_row_kernel, dim3((n + DBS_TR - 1) / DBS_TR), dim3(256), 0, stream, d_x, n, d, d_core2, d_comp, roww, rowe);
+    RA_LAUNCH(he, hdb_minw_kernel, dim3(nt), dim3(256), 0, stream, d_comp, n, (const unsigned long long *)roww, cw);
+    RA_LAUNCH(he, hdb_mine_kernel, dim3(nt), dim3(256), 0, stream, d_comp, n, (const unsigned long long *)roww,
+              (const unsigned long long *)rowe, (const unsigned long long *)cw, ce);
+    RA_LAUNCH(he, hdb_out_kernel, dim3(nt), dim3(256), 0, stream, d_comp, n, (const unsigned long long *)cw, (const unsigned long long *)ce,
+              d_w2, d_lo, d_hi);
+    return he == hipSuccess ? RA_OK : hip_error("ra_hdbscan_round", he);
 }

@@ -27,7 +27,8 @@ The contract, rule by rule:
   8. The result is a pure function of (X, eps, min_samples), bitwise reproducible call to call and stream to stream.
 Domain: 1 <= n <= 262144, 1 <= d <= 2048, finite eps > 0, integer min_samples >= 1, finite X.  Anything else raises DbscanError
 (a ValueError) before anything is launched.
-Not built: other metrics, sample_weight, precomputed or sparse input, HDBSCAN / OPTICS, multi-GPU, more than 262144 points.
+Not built: other metrics, sample_weight, precomputed or sparse input, OPTICS, multi-GPU, more than 262144 points (HDBSCAN is
+hdbscan.py).
 
 On the device every pass recomputes its n^2 distances in the HIP kernels behind ra_dbscan_count / ra_dbscan_step
 (csrc/ralign_dbscan.h); nothing of size n^2 is stored.  The host reads one int per round (the number of core points whose label

@@ -522,6 +522,26 @@ int  ra_dbscan_count(const float *d_x, int n, int d, double eps, int min_samples
 int  ra_dbscan_step(const float *d_x, int n, int d, double eps, const int *d_count, int min_samples, const int *d_label,
                     int *d_label_out, int *d_changed, void *hip_stream);
 
+/* HDBSCAN of X [n][d] (float32, device memory): the two device parts of cryo_ralib_amd/hdbscan.py, whose docstring holds the
+ * contract rule by rule.  D2 is ra_dbscan_count's: double, from differences, the features in order,
+ * exactly symmetric.  w2(i, j) = max(core2_i, core2_j, D2(i, j)); edges are totally ordered by (w2, min(i, j), max(i, j)), so the
+ * minimum spanning tree is unique.  Every pass recomputes its distances: nothing of size n^2 is stored.  Same conventions as the
+ * DBSCAN entries: asynchronous on hip_stream, scratch allocated and freed on that stream, integer atomics only (bitwise
+ * reproducible call to call and across streams), no workgroup waits for another, RA_ERR_ARG with nothing launched outside the
+ * domain: 2 <= n <= 262144, 1 <= d <= 2048, 1 <= min_samples <= min(n, 302).
+ *   ra_hdbscan_core   d_core2 [n] (double) = D2 from i to its (min_samples - 1)-th nearest other point, 0 for min_samples = 1.
+ *                     The neighbour is the last column of ra_tsne_knn's index list; the value is recomputed by D2's own chain.
+ *   ra_hdbscan_round  one Boruvka round.  d_comp [n]: the lowest index of i's component (values are compared, and range-checked
+ *                     before they address anything).  A row pass (one workgroup per 64 rows over all n columns, 4 x 4 double
+ *                     accumulators per thread) keeps for every row the least (w2, lo, hi) over the columns of other components;
+ *                     the minimum per component then comes from integer atomicMin in two launches: the bit pattern of w2, then
+ *                     lo << 32 | hi among the rows that hold that w2.  At a root i = d_comp[i]: d_w2 [i], d_lo [i] < d_hi [i] =
+ *                     the component's least outgoing edge.  At every other index, and at the root of a component that holds
+ *                     every point: +inf, -1, -1.  The loop, the union-find and the tree of clusters are cryo_ralib_amd/hdbscan.py. */
+int  ra_hdbscan_core(const float *d_x, int n, int d, int min_samples, double *d_core2, void *hip_stream);
+int  ra_hdbscan_round(const float *d_x, int n, int d, const double *d_core2, const int *d_comp, double *d_w2, int *d_lo, int *d_hi,
+                      void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
