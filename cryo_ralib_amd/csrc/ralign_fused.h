@@ -691,41 +691,55 @@ __global__ __launch_bounds__(RF_THREADS) void search_fused_kernel(DevGeom g_in, 
             const int ref_b = 2 * rp0 + (xj >> 1);
             float *zk = bufs + (odd * f.rz + ref_b - ref_lo) * ZL::kPairStride + 2 * (k + (k >> 4));
             const int dkm = 2 * (km + (km >> 4)) - 2 * (k + (k >> 4));
-            // Normalize_ring mean x DC weight of every unit (bin group 0 only), read up front: under the unit's own condition
-            // each of the reads is a dependent LDS round trip of its own
-            float dcv[NU];
-            if (xm == 0) {
-                const float av0 = red[8 + odd], av1 = red[10 + odd];
+            // live units: the reference pair of a unit exists and belongs to this round (h), its offset is live (op) -- formed
+            // once per round, a unit combines two of them
+            bool lr[NRPW], lo[2];
 #pragma unroll
-                for (int h = 0; h < NRPW; h++) {
-                    const float w = cdc_s[min(ref_b + 2 * h, nref - 1)];
-                    dcv[2 * h] = av0 * w; dcv[2 * h + 1] = av1 * w;
-                }
+            for (int h = 0; h < NRPW; h++) {
+                const int ref = ref_b + 2 * h, rr = ref - ref_lo;
+                lr[h] = ref < nref && rr >= 0 && rr < nrz;                // ref < nref implies a real reference pair
             }
+            lo[0] = odd < nlive; lo[1] = 2 + odd < nlive;
+            // 2x2 block exchange between the Re/Im column lanes of one reference: the four values of the neighbouring lane by DPP
+            // moves, then one select per value through ONE lane-parity mask (opaque: the compiler would form it again per unit)
+            unsigned long long oddm = __builtin_amdgcn_ballot_w64(odd != 0);
+            asm volatile("" : "+s"(oddm));
+            const bool isodd = __builtin_amdgcn_inverse_ballot_w64(oddm);       // one mask register for all the selects below
+            auto exchange = [&](const f32x4 c4, float &ca, float &cb, float &cc, float &cd) {
+                const float x0 = swap_lane_pair(c4[0]), x1 = swap_lane_pair(c4[1]), x2 = swap_lane_pair(c4[2]), x3 = swap_lane_pair(c4[3]);
+                ca = isodd ? x2 : c4[0]; cb = isodd ? x3 : c4[1]; cc = isodd ? c4[2] : x0; cd = isodd ? c4[3] : x1;
+            };
 #pragma unroll
             for (int i = 0; i < NU; i++) {
-                const int h = i >> 1, op = i & 1, ref = ref_b + 2 * h, o = 2 * op + odd, rr = ref - ref_lo;
-                const f32x4 c4 = acc[i];
-                const float s0 = odd ? c4[0] : c4[2], s1 = odd ? c4[1] : c4[3];
-                const float r0x = swap_lane_pair(s0), r1x = swap_lane_pair(s1);
-                float ca = odd ? r0x : c4[0];
-                const float cb = odd ? r1x : c4[1], cc = odd ? c4[2] : r0x, cd = odd ? c4[3] : r1x;
-                const bool live = ref < nref && rr >= 0 && rr < nrz && o < nlive;      // ref < nref implies a real reference pair
-                float2 vk, vm;
-                if (xm == 0) {                                            // wave-uniform: the group that holds bin 0
-                    if (xb == 0 && live) ca -= dcv[i];                    // Normalize_ring mean: the DC term only
-                    const float apd = ca + cd, amd = ca - cd, bpc = cb + cc, cmb = cc - cb;
-                    vk = xb == 0 ? make_float2(ca, ca) : make_float2(apd + bpc, cmb + amd);
-                    vm = xb == 0 ? make_float2(cd, cd) : make_float2(apd - bpc, amd - cmb);
-                } else {
-                    const float apd = ca + cd, amd = ca - cd, bpc = cb + cc, cmb = cc - cb;
-                    vk = make_float2(apd + bpc, cmb + amd);
-                    vm = make_float2(apd - bpc, amd - cmb);
-                }
-                if (live) {
+                const int h = i >> 1, op = i & 1;
+                float ca, cb, cc, cd;
+                exchange(acc[i], ca, cb, cc, cd);
+                const float apd = ca + cd, amd = ca - cd, bpc = cb + cc, cmb = cc - cb;
+                if (lr[h] && lo[op]) {
                     float *z = zk + (2 * op * f.rz + 2 * h) * ZL::kPairStride;
-                    *reinterpret_cast<float2 *>(z) = vk;
-                    *reinterpret_cast<float2 *>(z + dkm) = vm;
+                    *reinterpret_cast<float2 *>(z) = make_float2(apd + bpc, cmb + amd);
+                    *reinterpret_cast<float2 *>(z + dkm) = make_float2(apd - bpc, amd - cmb);
+                }
+            }
+            // bin 0 (one lane quad of the waves of bin group 0; tested once per round): the DC term, less the Normalize_ring
+            // mean x the DC weight of the unit, goes to slot 0 and the Nyquist term to slot N/2, over what the loop above put there
+            if (xm == 0) {
+#pragma clang fp contract(off)                                            // the product is rounded before it is subtracted
+                const float av0 = red[8 + odd], av1 = red[10 + odd];
+                float w[NRPW];
+#pragma unroll
+                for (int h = 0; h < NRPW; h++) w[h] = cdc_s[min(ref_b + 2 * h, nref - 1)];
+#pragma unroll
+                for (int i = 0; i < NU; i++) {
+                    const int h = i >> 1, op = i & 1;
+                    float ca, cb, cc, cd;
+                    exchange(acc[i], ca, cb, cc, cd);
+                    if (xb == 0 && lr[h] && lo[op]) {
+                        float *z = zk + (2 * op * f.rz + 2 * h) * ZL::kPairStride;
+                        ca -= (op ? av1 : av0) * w[h];
+                        *reinterpret_cast<float2 *>(z) = make_float2(ca, ca);
+                        *reinterpret_cast<float2 *>(z + dkm) = make_float2(cd, cd);
+                    }
                 }
             }
         };
@@ -742,11 +756,15 @@ __global__ __launch_bounds__(RF_THREADS) void search_fused_kernel(DevGeom g_in, 
         };
         if (!RA_DBG(g, 4)) {
             if constexpr (ONE) {               // the accumulators die before the inverse FFT: no register pressure from them
+                RA_PHASE_MARK("store_begin");
                 store_round(0, nref);
+                RA_PHASE_MARK("store_end");
                 RA_STAMP(g, tl, grp, wave, 5);
                 RF_LDS_BARRIER();
                 RA_STAMP(g, tl, grp, wave, 6);
+                RA_PHASE_MARK("ifft_begin");
                 ifft_round(0, nref);
+                RA_PHASE_MARK("ifft_end");
                 RA_STAMP(g, tl, grp, wave, 7);
             } else {
                 for (int zr = 0; zr < f.nzr; zr++) {

@@ -1252,9 +1252,21 @@ __device__ __forceinline__ void contract_class(const float *__restrict__ Ablk, c
     }
 }
 
+// c[LO + i], i < LEN, by the bits of i: hi[b] = bit b of i.  LEN - 1 selects and no compare; the indices are constants
+// where the compiler first sees them (written as a loop over an array, the tree comes back as LEN compares)
+template <int LO, int LEN, int R>
+__device__ __forceinline__ float select_tree(const float (&c)[R], const bool (&hi)[4])
+{
+    if constexpr (LEN == 1) return c[LO];
+    else {
+        const float a = select_tree<LO, LEN / 2>(c, hi), b = select_tree<LO + LEN / 2, LEN / 2>(c, hi);
+        return hi[LEN == 16 ? 3 : LEN == 8 ? 2 : LEN == 4 ? 1 : 0] ? b : a;
+    }
+}
+
 // two-kernel path: the same transform, but the 7-point neighbourhood of the maximum is picked out of the REGISTERS
 // (lane j holds the outputs with index = j mod R1; every one of the 7 neighbours sits in a different lane, which
-// selects it with a compare chain and stores it straight into the candidate record) -- the transformed sequence is
+// selects it with a tree of selects and stores it straight into the candidate record) -- the transformed sequence is
 // never written back to LDS.  Records: pc[pair] = {val, jtot, refmir = mirror << 16 | ref0 + (pair & 7), t7[7]}.
 template <int N, int NP, int REFMASK = 7>
 __device__ __forceinline__ void ifft_argmax(float *Z, CandT *pc, const float2 *twl, int pairA, int pairB, int j, int ref0,
@@ -1294,6 +1306,7 @@ __device__ __forceinline__ void ifft_argmax(float *Z, CandT *pc, const float2 *t
 #pragma unroll
         for (int q = 0; q < NP; q++) Dft<1, R2>::run(v[q]);
     }
+    RA_PHASE_MARK("argmax_begin");
 #pragma unroll
     for (int q = 0; q < NP; q++) {
         // Maximum first, index second: the running maximum of both sequences is one v_max per value, the 16-lane maximum
@@ -1315,13 +1328,24 @@ __device__ __forceinline__ void ifft_argmax(float *Z, CandT *pc, const float2 *t
         float c[R2];
         int jt = -1;
         if (j < R1) {
+            // the last n1 whose element equals the maximum.  The compares are independent: four at a time go into mask
+            // registers of their own ahead of their selects (through the compiler as opaque lane masks, or it folds them back
+            // into one compare -> wait states -> select chain through a single mask register)
             int nb = -1;
 #pragma unroll
-            for (int n1 = 0; n1 < R2; n1++) {
-                c[n1] = mir ? v[q][n1].y : v[q][n1].x;
-                nb = c[n1] == best ? n1 : nb;
+            for (int n1 = 0; n1 < R2; n1++) c[n1] = mir ? v[q][n1].y : v[q][n1].x;
+#pragma unroll
+            for (int n0 = 0; n0 < R2; n0 += 4) {
+                unsigned long long m0 = __builtin_amdgcn_ballot_w64(c[n0] == best), m1 = __builtin_amdgcn_ballot_w64(c[n0 + 1] == best);
+                unsigned long long m2 = __builtin_amdgcn_ballot_w64(c[n0 + 2] == best), m3 = __builtin_amdgcn_ballot_w64(c[n0 + 3] == best);
+                asm volatile("" : "+s"(m0), "+s"(m1), "+s"(m2), "+s"(m3));
+                nb = __builtin_amdgcn_inverse_ballot_w64(m0) ? n0 : nb;
+                nb = __builtin_amdgcn_inverse_ballot_w64(m1) ? n0 + 1 : nb;
+                nb = __builtin_amdgcn_inverse_ballot_w64(m2) ? n0 + 2 : nb;
+                nb = __builtin_amdgcn_inverse_ballot_w64(m3) ? n0 + 3 : nb;
             }
-            jt = nb >= 0 ? R1 * nb + j : -1;
+            asm volatile("" : "+v"(nb));        // the selects take n1 as an inline constant: scaled by R1 ahead of them, every n1 is a register
+            jt = max(R1 * nb + j, -1);          // no element equal to it (a NaN in the sequence): -1
         }
 #define RA_DPP_IMAX(CTRL) jt = max(jt, __builtin_amdgcn_update_dpp(0, jt, CTRL, 0xF, 0xF, true))
         RA_DPP_IMAX(0x140); RA_DPP_IMAX(0x141); RA_DPP_IMAX(0x4E); RA_DPP_IMAX(0xB1);
@@ -1331,11 +1355,19 @@ __device__ __forceinline__ void ifft_argmax(float *Z, CandT *pc, const float2 *t
         const int d = (j - jt) & (R1 - 1);
         const int k = d <= 3 ? d : d - R1;
         if (j < R1 && k >= -3) {
+            // 1 of R2 by a binary tree over the bits of the register index: log2 R2 lane masks formed ahead of the tree (opaque,
+            // or the compiler turns the tree back into R2 compares with one select each), R2 - 1 selects
             const int n1 = ((jt + k + N) & (N - 1)) / R1;
-            float val = 0.f;
+            unsigned long long mb[4];
 #pragma unroll
-            for (int r = 0; r < R2; r++) val = (r == n1) ? c[r] : val;
-            dst->t7[k + 3] = val;
+            for (int b = 0; (1 << b) < R2; b++) mb[b] = __builtin_amdgcn_ballot_w64((n1 & (1 << b)) != 0);
+            if constexpr (R2 == 16) asm volatile("" : "+s"(mb[0]), "+s"(mb[1]), "+s"(mb[2]), "+s"(mb[3]));
+            else if constexpr (R2 == 8) asm volatile("" : "+s"(mb[0]), "+s"(mb[1]), "+s"(mb[2]));
+            else asm volatile("" : "+s"(mb[0]), "+s"(mb[1]));
+            bool hi[4] = {false, false, false, false};
+#pragma unroll
+            for (int b = 0; (1 << b) < R2; b++) hi[b] = __builtin_amdgcn_inverse_ballot_w64(mb[b]);
+            dst->t7[k + 3] = select_tree<0, R2>(c, hi);
         }
         if (j == 0) {
             dst->val = best;

@@ -359,6 +359,7 @@ __global__ __launch_bounds__(RF_THREADS) void search_pair_kernel(DevGeom g_in, F
                 RF_LDS_BARRIER();         // t = 0: every slice is in registers; t > 0: the inverse FFTs of tile t - 1 are over
                 RA_STAMP(g, tl && t == 0, ipass, wave, 5);
                 if (t > 0) { merge_records(t - 1, false, p, s0, 0); if (two) merge_records(t - 1, false, p, s1, 1); }
+                RA_PHASE_MARK("store_begin");
                 {
                     // Z_k = Q_k + i T_k and Z_{N-k} = conj Q_k + i conj T_k for this lane's bin of the wave's reference pairs: the even
                     // lane of a pair keeps offset A (rows 0, 1), the odd lane offset B (rows 2, 3), after the 2 x 2 exchange of
@@ -401,15 +402,18 @@ __global__ __launch_bounds__(RF_THREADS) void search_pair_kernel(DevGeom g_in, F
                         }
                     }
                 }
+                RA_PHASE_MARK("store_end");
                 RA_STAMP(g, tl && t == 0, ipass, wave, 6);
                 RF_LDS_BARRIER();         // the spectra of the tile are complete
                 RA_STAMP(g, tl && t == 0, ipass, wave, 7);
+                RA_PHASE_MARK("ifft_begin");
                 if (call >= 0) {          // four transforms per call, 16 lanes each: slot zs = offset * RZ + reference
                     const int j = ln & 15, zs = 4 * call + (ln >> 4);
                     const int o = zs >= RZ ? 1 : 0, rr = zs - o * RZ;
                     if (zs < 2 * RZ && rr < nrz && (two || !o))
                         ifft_argmax<N, 1, 0>(bufs, pc, tws + j, zs, zs, j, ref_lo + rr, g.nomirror != 0);
                 }
+                RA_PHASE_MARK("ifft_end");
                 RA_STAMP(g, tl && t == 0, ipass, wave, 8);
             }
             RA_STAMP(g, tl, ipass, wave, 9);

@@ -411,6 +411,7 @@ __global__ __launch_bounds__(RF_THREADS) void search_tiled_kernel(DevGeom g_in, 
             RF_LDS_BARRIER();         // t = 0: every slice is in registers; t > 0: the inverse FFTs of tile t - 1 are over
             RA_STAMP(g, tl && t < 2, grp, wave, 5 + 5 * t);
             if (t > 0) merge_records(t - 1, false, i0, s0, nlive);
+            RA_PHASE_MARK("store_begin");
             {
                 // Z_k = Q_k + i T_k and Z_{N-k} (rf_store_z) for this lane's bin of every reference pair of the tile
                 typedef ZLayout<N> ZL;
@@ -418,39 +419,49 @@ __global__ __launch_bounds__(RF_THREADS) void search_tiled_kernel(DevGeom g_in, 
                 const int ref_b = ref_lo + (xj >> 1), o = 2 * op + odd;
                 float *zk = bufs + (o * RZ + (xj >> 1)) * ZL::kPairStride + 2 * (k + (k >> 4));
                 const int dkm = 2 * (km + (km >> 4)) - 2 * (k + (k >> 4));
-                float dcv[NH];
-                if (xm == 0) {
-                    const float av = red[8 + o];
-#pragma unroll
-                    for (int h = 0; h < NH; h++) dcv[h] = av * cdc_s[min(ref_b + 2 * h, nref - 1)];
-                }
+                // live units: the lane's offset is live and the reference pair of the unit exists; one lane mask for the
+                // selects of the 2x2 exchange (as store_round of search_fused_kernel)
+                const bool lo = o < nlive;
+                unsigned long long oddm = __builtin_amdgcn_ballot_w64(odd != 0);
+                asm volatile("" : "+s"(oddm));
+                const bool isodd = __builtin_amdgcn_inverse_ballot_w64(oddm);
+                auto exchange = [&](const f32x4 c4, float &ca, float &cb, float &cc, float &cd) {
+                    const float x0 = swap_lane_pair(c4[0]), x1 = swap_lane_pair(c4[1]), x2 = swap_lane_pair(c4[2]), x3 = swap_lane_pair(c4[3]);
+                    ca = isodd ? x2 : c4[0]; cb = isodd ? x3 : c4[1]; cc = isodd ? c4[2] : x0; cd = isodd ? c4[3] : x1;
+                };
 #pragma unroll
                 for (int h = 0; h < NH; h++) {
-                    const int ref = ref_b + 2 * h;
-                    const f32x4 c4 = acc[h];
-                    const float s0 = odd ? c4[0] : c4[2], s1 = odd ? c4[1] : c4[3];
-                    const float r0x = swap_lane_pair(s0), r1x = swap_lane_pair(s1);
-                    float ca = odd ? r0x : c4[0];
-                    const float cb = odd ? r1x : c4[1], cc = odd ? c4[2] : r0x, cd = odd ? c4[3] : r1x;
-                    const bool live = ref < nref && o < nlive;
-                    float2 vk, vm;
-                    if (xm == 0) {
-                        if (xb == 0 && live) ca -= dcv[h];
-                        const float apd = ca + cd, amd = ca - cd, bpc = cb + cc, cmb = cc - cb;
-                        vk = xb == 0 ? make_float2(ca, ca) : make_float2(apd + bpc, cmb + amd);
-                        vm = xb == 0 ? make_float2(cd, cd) : make_float2(apd - bpc, amd - cmb);
-                    } else {
-                        const float apd = ca + cd, amd = ca - cd, bpc = cb + cc, cmb = cc - cb;
-                        vk = make_float2(apd + bpc, cmb + amd);
-                        vm = make_float2(apd - bpc, amd - cmb);
-                    }
-                    if (live) {
+                    float ca, cb, cc, cd;
+                    exchange(acc[h], ca, cb, cc, cd);
+                    const float apd = ca + cd, amd = ca - cd, bpc = cb + cc, cmb = cc - cb;
+                    if (lo && ref_b + 2 * h < nref) {
                         float *z = zk + 2 * h * ZL::kPairStride;
-                        *reinterpret_cast<float2 *>(z) = vk;
-                        *reinterpret_cast<float2 *>(z + dkm) = vm;
+                        *reinterpret_cast<float2 *>(z) = make_float2(apd + bpc, cmb + amd);
+                        *reinterpret_cast<float2 *>(z + dkm) = make_float2(apd - bpc, amd - cmb);
+                    }
+                }
+                // bin 0 (bin group 0 only, tested once): DC term less the Normalize_ring mean x DC weight -> slot 0, Nyquist
+                // term -> slot N/2, over what the loop above put there
+                if (xm == 0) {
+#pragma clang fp contract(off)                                            // the product is rounded before it is subtracted
+                    const float av = red[8 + o];
+                    float w[NH];
+#pragma unroll
+                    for (int h = 0; h < NH; h++) w[h] = cdc_s[min(ref_b + 2 * h, nref - 1)];
+#pragma unroll
+                    for (int h = 0; h < NH; h++) {
+                        float ca, cb, cc, cd;
+                        exchange(acc[h], ca, cb, cc, cd);
+                        if (xb == 0 && lo && ref_b + 2 * h < nref) {
+                            float *z = zk + 2 * h * ZL::kPairStride;
+                            ca -= av * w[h];
+                            *reinterpret_cast<float2 *>(z) = make_float2(ca, ca);
+                            *reinterpret_cast<float2 *>(z + dkm) = make_float2(cd, cd);
+                        }
                     }
                 }
             }
+            RA_PHASE_MARK("store_end");
             RA_STAMP(g, tl && t < 2, grp, wave, 6 + 5 * t);
             RF_LDS_BARRIER();         // the spectra of the tile are complete
             RA_STAMP(g, tl && t < 2, grp, wave, 7 + 5 * t);
@@ -459,6 +470,7 @@ __global__ __launch_bounds__(RF_THREADS) void search_tiled_kernel(DevGeom g_in, 
             // of the OLDEST waves 0 and 1, whose first call is over first (the SIMDs issue oldest-first; full calls with 2-way
             // bank conflicts on their 35 LDS instructions rather than four half-filled calls of 390 vector instructions each:
             // the phase is bound by vector issue, not by the LDS)
+            RA_PHASE_MARK("ifft_begin");
 #pragma unroll 1
             for (int call = 0; call < 2; call++) {
                 if (wave >= (call ? 2 : 8) || (call == 1 && 4 * RZ <= 32)) break;
@@ -468,6 +480,7 @@ __global__ __launch_bounds__(RF_THREADS) void search_tiled_kernel(DevGeom g_in, 
                 if (zs < 4 * RZ && rr < nrz && o < nlive)
                     ifft_argmax<N, 1, 0>(bufs, pc + (o * RZ + rr) - zs, tws + j, zs, zs, j, ref_lo + rr, g.nomirror != 0);
             }
+            RA_PHASE_MARK("ifft_end");
             RA_STAMP(g, tl && t < 2, grp, wave, 8 + 5 * t);
         }
         RA_STAMP(g, tl, grp, wave, 15);
