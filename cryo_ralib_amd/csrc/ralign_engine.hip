@@ -2107,10 +2107,13 @@ static int ensure_refine_ws(ra_engine *e, int nimg)
     const int nx = e->geo.nx, nxh = nx / 2 + 1;
     const int cap = std::max(nimg, 2 * e->cfg.nref);
     int rc;
-    if ((rc = dev_alloc(e, &e->d_rfT, (size_t)cap * nx * nxh, false)) || (rc = dev_alloc(e, &e->d_rfF, (size_t)cap * nx * nxh, false)) ||
-        (rc = dev_alloc(e, &e->d_rfmean, (size_t)cap, true)) || (rc = dev_alloc(e, &e->d_rffsc, (size_t)cap * (nx / 2 + 1), true)) ||
-        (rc = dev_alloc(e, &e->d_rfcs, (size_t)cap * 2, true)))
+    // growing replaces the buffers that hold one call's images (the old ones are released now); the per-class curves are
+    // 2 nref rows whatever nimg is and outlive the call (ra_last_class_fsc), so they are allocated once and kept
+    e->rf_cap = 0;          // until every buffer is in place again
+    if ((rc = dev_grow(e, &e->d_rfT, (size_t)cap * nx * nxh, false)) || (rc = dev_grow(e, &e->d_rfF, (size_t)cap * nx * nxh, false)) ||
+        (rc = dev_grow(e, &e->d_rfmean, (size_t)cap, true)) || (rc = dev_grow(e, &e->d_rfcs, (size_t)cap * 2, true)))
         return rc;
+    if (!e->d_rffsc && (rc = dev_alloc(e, &e->d_rffsc, (size_t)2 * e->cfg.nref * (nx / 2 + 1), true))) return rc;
     if (!e->d_rftw) {
         std::vector<double2> tw(nx);
         for (int t = 0; t < nx; t++) { const double a = 2.0 * M_PI * t / nx; tw[t] = make_double2(cos(a), sin(a)); }
