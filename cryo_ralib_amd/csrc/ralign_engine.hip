@@ -83,6 +83,7 @@ struct ra_engine {
     float *d_xs_partial = nullptr;
     float2 *d_xs_trig = nullptr;
     size_t xs_cap_members = 0, xs_cap_partial = 0, xs_cap_trig = 0;
+    int xs_slots = 0;          // workgroups of transform_sum_db_kernel resident on the device at once (occupancy query at first use)
     bool atomic_sums = false;           // RALIGN_ATOMIC_SUMS=1: fp32 atomics instead of particle-order sums
     int *d_ring_off = nullptr, *d_numr = nullptr;
     float *d_wr = nullptr;
@@ -1897,28 +1898,45 @@ extern "C" int ra_debug_spectra(ra_engine *e, const float *d_particles, int n, c
 // once, every (class, parity) list cut into runs so that ~1000 workgroups share the work
 #define RA_XS_BATCH 65536
 typedef void (*xs_fn)(int, const float *, int, int, const ra_result *, const float2 *, const int *, const int *, int, float *);
-static xs_fn select_xs(int nx, int *nband = nullptr)
+// sweeps of the 1024-thread workgroup over the image: up to 24 (three row bands of 8) are instantiated
+static bool xs_sweeps_fit(int nx)
 {
-    if (nband) *nband = 1;
-    if (nx < 8 || nx > RA_XS_THREADS) return nullptr;
+    if (nx < 8 || nx > RA_XS_THREADS) return false;
+    const int ry = RA_XS_THREADS / nx;
+    return (nx + ry - 1) / ry <= 24;
+}
+// one copy of the padded image (transform_sum_kernel): the boxes from 100 pixels on, whose two copies would not leave room for a
+// second workgroup (select_xs_db takes everything below): row bands of at most 8 sweeps per workgroup (9 accumulators and their
+// prefetch registers are what 128 registers hold)
+static xs_fn select_xs(int nx, int *nband)
+{
     const int ry = RA_XS_THREADS / nx, npt = (nx + ry - 1) / ry;      // sweeps of the workgroup over the image
-    if (npt <= 1) return transform_sum_kernel<1>;
-    if (npt <= 2) return transform_sum_kernel<2>;
-    if (npt <= 4) return transform_sum_kernel<4>;
-    if (npt <= 6) return transform_sum_kernel<6>;
-    if (npt <= 9) return transform_sum_kernel<9>;
-    // larger boxes: row bands of at most 8 sweeps per workgroup (9 accumulators and their prefetch registers are what 128 hold)
-    if (npt <= 12) { if (nband) *nband = 2; return transform_sum_kernel<6, 12>; }
-    if (npt <= 16) { if (nband) *nband = 2; return transform_sum_kernel<8, 16>; }
-    if (npt <= 20) { if (nband) *nband = 3; return transform_sum_kernel<7, 20>; }
-    if (npt <= 24) { if (nband) *nband = 3; return transform_sum_kernel<8, 24>; }
+    if (npt <= 12) { *nband = 2; return transform_sum_kernel<6, 12>; }
+    if (npt <= 16) { *nband = 2; return transform_sum_kernel<8, 16>; }
+    if (npt <= 20) { *nband = 3; return transform_sum_kernel<7, 20>; }
+    if (npt <= 24) { *nband = 3; return transform_sum_kernel<8, 24>; }
     return nullptr;
+}
+// two copies of the padded image per workgroup where that still leaves room for two workgroups on a CU (transform_sum_db_kernel):
+// sweeps per row band (at most 9 accumulators per thread, as above) and the instantiation that holds them
+typedef void (*xs_db_fn)(int, const float *, const ra_result *, const float2 *, const int *, const int *, int, float *, XsGrid);
+static xs_db_fn select_xs_db(int nx, int *npf_out, int *sb0_out, int *nb0_out)
+{
+    if (nx < 8 || 2 * (size_t)(nx + 2) * ((nx + 2) | 1) * sizeof(float) > RA_XS_LDS_MAX) return nullptr;
+    const int ry = RA_XS_THREADS / nx, npf = (nx + ry - 1) / ry;      // sweeps of the workgroup over the image
+    const int nb0 = (npf + 8) / 9, sb0 = (npf + nb0 - 1) / nb0;
+    *npf_out = npf; *sb0_out = sb0; *nb0_out = nb0;
+    if (sb0 <= 1) return transform_sum_db_kernel<1>;
+    if (sb0 <= 2) return transform_sum_db_kernel<2>;
+    if (sb0 <= 4) return transform_sum_db_kernel<4>;
+    if (sb0 <= 6) return transform_sum_db_kernel<6>;
+    return transform_sum_db_kernel<9>;
 }
 // the whole image in LDS (transform_sum_kernel), or -- larger boxes -- output tiles with the source box of each in LDS
 // (transform_sum_tile_kernel; RALIGN_XTILE=0: the aligned stack + class_sum_kernel as before)
 static bool xs_whole_image(const ra_engine *e)
 {
-    if (e->xf_generic || !select_xs(e->geo.nx)) return false;
+    if (e->xf_generic || !xs_sweeps_fit(e->geo.nx)) return false;
     return (size_t)(e->geo.nx + 2) * ((e->geo.nx + 2) | 1) * sizeof(float) <= RA_XS_LDS_MAX;
 }
 static bool xs_usable(const ra_engine *e)
@@ -1933,10 +1951,23 @@ static int transform_sum(ra_engine *e, const float *d_particles, int n, int inde
     const int nx = e->geo.nx, npix = nx * nx, nseg = 2 * e->cfg.nref;
     int nband = 1;
     const bool tiles = !xs_whole_image(e);
-    const xs_fn fn = tiles ? transform_sum_tile_kernel : select_xs(nx, &nband);
+    int npf = 0, sb0 = 0, nb0 = 0;
+    const xs_db_fn dbfn = tiles ? nullptr : select_xs_db(nx, &npf, &sb0, &nb0);
+    const xs_fn fn = tiles ? transform_sum_tile_kernel : dbfn ? nullptr : select_xs(nx, &nband);
+    if (!dbfn && !fn) { g_last_error = "transform_sum: no kernel for this box"; return RA_ERR_ARG; }
     const int ntile = ((nx + RA_XT_TS - 1) / RA_XT_TS) * ((nx + RA_XT_TS - 1) / RA_XT_TS);
     const size_t xs_lds = tiles ? (size_t)2 * RA_XT_BB * RA_XT_BB * sizeof(float) : (size_t)(nx + 2) * ((nx + 2) | 1) * sizeof(float);
-    if (xs_lds > 64 * 1024) {
+    if (dbfn) {
+        if (2 * xs_lds > 64 * 1024) {
+            const int rc = raise_dynamic_lds(e, (const void *)dbfn, "transform_sum_db_kernel", 2 * xs_lds);
+            if (rc) return rc;
+        }
+        if (!e->xs_slots) {
+            int per_cu = 0;
+            RA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)dbfn, RA_XS_THREADS, 2 * xs_lds));
+            e->xs_slots = std::max(1, per_cu) * std::max(1, e->n_cu);
+        }
+    } else if (xs_lds > 64 * 1024) {
         const int rc = raise_dynamic_lds(e, (const void *)fn, tiles ? "transform_sum_tile_kernel" : "transform_sum_kernel", xs_lds);
         if (rc) return rc;
     }
@@ -1968,9 +1999,21 @@ static int transform_sum(ra_engine *e, const float *d_particles, int n, int inde
         hipLaunchKernelGGL(class_members_wide_kernel, dim3(nseg), dim3(1024), 0, e->stream, d_result + start, cn, index0 + start,
                            e->d_xs_members, e->d_xs_mcount, cn, d_counts);
         RA_HIP(hipGetLastError());
-        hipLaunchKernelGGL(fn, dim3(nseg, nrun, tiles ? ntile : nband), dim3(tiles ? RA_XT_THREADS : RA_XS_THREADS), xs_lds, e->stream, nx,
-                           d_particles + (size_t)start * npix, cn, index0 + start, d_result + start, (const float2 *)e->d_xs_trig, (const int *)e->d_xs_members,
-                           (const int *)e->d_xs_mcount, cn, e->d_xs_partial);
+        if (dbfn) {
+            // a small surplus of work items over whole rounds of resident workgroups would hold a round of its own: those
+            // items run as row bands, a third of the sweeps each, behind the full ones
+            const int items = nseg * nrun, over = items % e->xs_slots;
+            XsGrid gr{nseg, nrun, items, sb0, nb0, sb0, 1};
+            if (nb0 == 1 && npf >= 2 && items > e->xs_slots && over > 0 && over * 8 <= e->xs_slots) {
+                gr.sb1 = (npf + 2) / 3; gr.nb1 = (npf + gr.sb1 - 1) / gr.sb1; gr.nfull = items - over;
+            }
+            hipLaunchKernelGGL(dbfn, dim3(gr.nfull * gr.nb0 + (items - gr.nfull) * gr.nb1), dim3(RA_XS_THREADS), 2 * xs_lds, e->stream, nx,
+                               d_particles + (size_t)start * npix, d_result + start, (const float2 *)e->d_xs_trig, (const int *)e->d_xs_members,
+                               (const int *)e->d_xs_mcount, cn, e->d_xs_partial, gr);
+        } else
+            hipLaunchKernelGGL(fn, dim3(nseg, nrun, tiles ? ntile : nband), dim3(tiles ? RA_XT_THREADS : RA_XS_THREADS), xs_lds, e->stream, nx,
+                               d_particles + (size_t)start * npix, cn, index0 + start, d_result + start, (const float2 *)e->d_xs_trig, (const int *)e->d_xs_members,
+                               (const int *)e->d_xs_mcount, cn, e->d_xs_partial);
         RA_HIP(hipGetLastError());
         hipLaunchKernelGGL(class_sum_combine_kernel, dim3((unsigned)(((size_t)nseg * npix + 255) / 256)), dim3(256), 0, e->stream, npix, nseg, nrun,
                            (const float *)e->d_xs_partial, d_sums);

@@ -1951,8 +1951,17 @@ __global__ __launch_bounds__(256) void class_sum_combine_kernel(int npix, int ns
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= (size_t)nseg * npix) return;
+    const size_t rst = (size_t)nseg * npix;
     float acc = sums[i];
-    for (int r = 0; r < nrun; r++) acc += partial[(size_t)r * nseg * npix + i];
+    int r = 0;
+    for (; r + 8 <= nrun; r += 8) {          // eight loads in flight, added in run order
+        float v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = partial[(size_t)(r + u) * rst + i];
+#pragma unroll
+        for (int u = 0; u < 8; u++) acc += v[u];
+    }
+    for (; r < nrun; r++) acc += partial[r * rst + i];
     sums[i] = acc;
 }
 
@@ -1994,6 +2003,7 @@ __device__ __forceinline__ float quadri_background_wrap(const float *P, int pst,
 // NPF sweeps fill the LDS image (NPF * (1024 / nx) >= nx), NPT sweeps of output rows per workgroup: larger boxes are cut into
 // gridDim.z row bands (NPT * gridDim.z >= NPF) so that a thread keeps at most 9 accumulators -- every band loads the whole image
 // (any pixel may be a tap), but 16 - 20 accumulators per thread next to their prefetch registers spilled 75 - 126 registers.
+// (Launched for boxes of 100 pixels and more, always in row bands; smaller boxes go to transform_sum_db_kernel below.)
 template <int NPT, int NPF = NPT>
 __global__ __launch_bounds__(RA_XS_THREADS) void transform_sum_kernel(int nx, const float *__restrict__ particles, int n, int index0,
                                                                       const ra_result *__restrict__ res, const float2 *__restrict__ trig,
@@ -2080,6 +2090,159 @@ __global__ __launch_bounds__(RA_XS_THREADS) void transform_sum_kernel(int nx, co
     float *dst = partial + ((size_t)run * gridDim.x + seg) * npix;
 #pragma unroll
     for (int k = 0; k < NPT; k++) { const int o = tid + (band + k) * S; if (live && o < npix) dst[o] = acc[k]; }
+}
+
+// K4c': the same pass with TWO copies of the padded image in LDS, for boxes whose two copies still leave room for a second
+// workgroup on the CU (nx <= 99).  The next member's image travels global -> LDS without a stop in registers while this one is
+// interpolated -- one wave per padded row, the two wrap-around border rows included (they are whole image rows); only the two
+// border columns, 2 nx + 4 elements, go through a register of the first threads -- so one barrier per member is left, no
+// prefetch registers are held, and the next member's pose (res, trig) is asked for a member ahead.  A wave whose rows of a
+// sweep all lie past the image (13 of 16 waves in the ninth sweep of a 90 x 90 box) skips that sweep.  Arithmetic, member
+// order and the association of the runs are transform_sum_kernel's to the bit.  (Pairs of sweeps on packed floats were tried:
+// 80 vector instructions per pair against 2 x 35 -- the compiler packs seven operations inside one pixel already, and pairs
+// across sweeps pay register moves behind ds_read2 --; profiles/step_tail_ab.txt.)
+// The grid is one-dimensional: the first nfull work items (segment, run) -- item = run * nseg + seg, the order the 3-D grid
+// was dealt in -- come as nb0 row bands of sb0 sweeps each (band-major, nb0 = 1 up to 9 sweeps), the remaining ones, which
+// would start another round of resident workgroups for a few items, as nb1 bands of sb1 sweeps behind them.  A band adds the
+// same members in the same order to its own rows.
+struct XsGrid { int nseg, nrun, nfull, sb0, nb0, sb1, nb1; };
+// quadri_background_wrap with the fractions from v_fract: x >= 1 after the background rule, so x - (float)(int)x is
+// x - floor(x), which v_fract returns exactly (bilinear_pad has the argument)
+__device__ __forceinline__ float quadri_background_wrap1(const float *P, int pst, int nx, float xx, float yy, float xnew, float ynew)
+{
+#pragma clang fp contract(off)
+    // (the four tests joined without short-circuit: selects, not branches; NaN: background)
+    const float hi = (float)(nx + 1);
+    const bool in = (xx >= 1.0f) & (xx < hi) & (yy >= 1.0f) & (yy < hi);
+    const float x = in ? xx : xnew, y = in ? yy : ynew;
+    const float dx0 = __builtin_amdgcn_fractf(x), dy0 = __builtin_amdgcn_fractf(y);
+    const float *q = (const float *)((const char *)P + (__mul24((int)y, pst * 4) + ((int)x << 2)));          // (24-bit multiply: full rate, exact for these sizes)
+    const float f0 = q[0];
+    const float c1 = q[1] - f0;
+    const float c2 = (c1 - f0 + q[-1]) * 0.5f;
+    const float c3 = q[pst] - f0;
+    const float c4 = (c3 - f0 + q[-pst]) * 0.5f;
+    const float dxb = dx0 - 1, dyb = dy0 - 1;
+    const float c5 = q[pst + 1] - f0 - c1 - c3;
+    return f0 + dx0 * (c1 + dxb * c2 + dy0 * c5) + dy0 * (c3 + dyb * c4);
+}
+
+// (amdgpu_waves_per_eu(8, 8): two workgroups of 16 waves per CU need 8 waves per SIMD.  Left to itself the compiler gives <9> 96
+// scalar registers, which it counts as 7 waves -- one workgroup per CU, half the residency --; held to 8 waves it keeps up to 26
+// scalar values in lanes of a VGPR instead, at most one of them read per sweep, and stays at 44 VGPRs without scratch.)
+template <int NPT>
+__global__ __launch_bounds__(RA_XS_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) void transform_sum_db_kernel(int nx, const float *__restrict__ particles,
+                                                                         const ra_result *__restrict__ res, const float2 *__restrict__ trig,
+                                                                         const int *__restrict__ members,
+                                                                         const int *__restrict__ mcount, int mstride,
+                                                                         float *__restrict__ partial, XsGrid gr)
+{
+#pragma clang fp contract(off)
+    extern __shared__ __align__(16) float img[];          // [2][(nx + 2)][pst]: rows / columns 0 and nx + 1 repeat nx and 1
+    const int tid = threadIdx.x, npix = nx * nx;
+    const int pst = (nx + 2) | 1, nimg = (nx + 2) * pst;
+    const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const unsigned nx_rcp = 0xFFFFFFFFu / (unsigned)nx + 1u;      // i / nx = (i * nx_rcp) >> 32, exact for i * nx < 2^32
+    const int RY = RA_XS_THREADS / nx, S = RY * nx;               // rows, pixels per sweep
+    const int npf = (nx + RY - 1) / RY;                           // sweeps over the whole image
+    // work item and row band [k0, k0 + kn) of this workgroup
+    int item, k0, kn;
+    {
+        const int b = blockIdx.x, nhead = gr.nfull * gr.nb0;
+        if (b < nhead) { const int bd = b / gr.nfull; item = b - bd * gr.nfull; k0 = bd * gr.sb0; kn = gr.sb0; }
+        else { const int s = b - nhead, nsur = gr.nseg * gr.nrun - gr.nfull, bd = s / nsur; item = gr.nfull + (s - bd * nsur); k0 = bd * gr.sb1; kn = gr.sb1; }
+        kn = min(min(kn, NPT), npf - k0);
+    }
+    const int run = item / gr.nseg, seg = item - run * gr.nseg, nrun = gr.nrun;
+    const int cnt = mcount[seg];
+    const int j0 = (int)((long long)cnt * run / nrun), j1 = (int)((long long)cnt * (run + 1) / nrun);
+    const int *mem = members + (size_t)seg * mstride;
+    const int ty = (int)__umulhi((unsigned)tid, nx_rcp), tx = tid - ty * nx;
+    const int tyw = __builtin_amdgcn_readfirstlane(ty);          // the wave's first row (its lanes' rows ascend)
+    const bool live = tid < S;
+    float acc[NPT];
+#pragma unroll
+    for (int k = 0; k < NPT; k++) acc[k] = 0.f;
+    // the two border columns of the padded copy: 2 nx + 4 elements, one per thread tid < 2 nx + 4 (padded (row, col) <- pixel)
+    int bdst = -1, bsrc = 0;
+    if (tid < 2 * nx + 4) {
+        const int right = tid >= nx + 2, pr = right ? tid - (nx + 2) : tid;
+        const int sr = pr == 0 ? nx - 1 : pr == nx + 1 ? 0 : pr - 1;
+        bdst = pr * pst + (right ? nx + 1 : 0); bsrc = sr * nx + (right ? 0 : nx - 1);
+    }
+    float preb = 0.f;
+    const int xc = nx / 2, yc = nx / 2, mstart = 1 - nx % 2;
+    struct Pose { float sx, sy, cang, sang; int mirror; };
+    auto pose_of = [&](int m) { const ra_result r = res[m]; const float2 cs = trig[m]; return Pose{r.sx, r.sy, cs.x, cs.y, r.mirror}; };
+    // particle m -> copy `dst`: padded row pr is image row pr - 1 (mod nx) at columns 1 .. nx, pieces of 64 pixels per request
+    auto fill = [&](int m, float *dst) {
+        const float *src = particles + (size_t)m * npix;
+        if (bdst >= 0) preb = src[bsrc];
+#pragma unroll 1
+        for (int pr = wave; pr < nx + 2; pr += RA_XS_THREADS / 64) {
+            const int sr = pr == 0 ? nx - 1 : pr == nx + 1 ? 0 : pr - 1;
+            const float *row = src + sr * nx + lane;
+            float *drow = dst + pr * pst + 1;
+            // (nx <= 99 here: two pieces; the second one through the instruction's offset, which moves source and destination alike)
+            if (lane < nx) __builtin_amdgcn_global_load_lds(row, (__attribute__((address_space(3))) void *)drow, 4, 0, 0);
+            if (lane + 64 < nx) __builtin_amdgcn_global_load_lds(row, (__attribute__((address_space(3))) void *)drow, 4, 256, 0);
+        }
+    };
+    Pose cur{}, nxt{};
+    int mcur = 0, mnxt = 0;
+    if (j0 < j1) {
+        mcur = mem[j0]; mnxt = mem[min(j0 + 1, j1 - 1)];
+        fill(mcur, img);
+        cur = pose_of(mcur);
+    }
+#pragma unroll 1
+    for (int j = j0; j < j1; j++) {
+        float *buf = img + ((j - j0) & 1) * nimg;
+        if (bdst >= 0) buf[bdst] = preb;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();                                  // this member's copy is complete; the other copy's taps are read
+        if (j + 1 < j1) {
+            fill(mnxt, img + ((j + 1 - j0) & 1) * nimg);
+            nxt = pose_of(mnxt);
+            mnxt = mem[min(j + 2, j1 - 1)];
+        }
+        // (ty passes through an empty asm in every trip: the row coordinates of the sweeps are rebuilt from it with a few
+        // instructions instead of being hoisted out of the loop into registers, as in transform_sum_kernel)
+        int tyv = ty;
+        asm volatile("" : "+v"(tyv));
+        float delx = cur.sx, dely = cur.sy;
+        while (delx >= (float)nx) delx -= nx;
+        while (delx <= -(float)nx) delx += nx;
+        while (dely >= (float)nx) dely -= nx;
+        while (dely <= -(float)nx) dely += nx;
+        const float shiftxc = xc + delx, shiftyc = yc + dely;
+        const float cang = cur.cang, sang = cur.sang;
+        // destination column tx; xform.mirror(x) reverses columns [1 - nx%2, nx): its source column is ix
+        const int ix = (cur.mirror && tx >= mstart) ? mstart + (nx - 1) - tx : tx;
+        const float x = (float)ix - shiftxc;
+        const float xcang = x * cang, xsang = x * sang;
+        const float xnew = (float)ix + 1.0f;              // the pixel's own 1-based position (small integers: exact)
+#pragma unroll
+        for (int k = 0; k < NPT; k++) {
+            // rows past the image (last sweep, idle threads) shadow the last row; a wave whose first row is past it skips the sweep
+            if (k < kn && tyw + (k0 + k) * RY < nx) {
+                const float yi = (float)min(tyv + (k0 + k) * RY, nx - 1);
+                const float y = yi - shiftyc;
+                const float ycang = y * cang + yc;
+                const float ysang = -y * sang + xc;
+                const float xold = xcang + ysang;
+                const float yold = xsang + ycang;
+                acc[k] += quadri_background_wrap1(buf, pst, nx, xold + 1.0f, yold + 1.0f, xnew, yi + 1.0f);
+            }
+        }
+        cur = nxt;
+    }
+    float *dst = partial + ((size_t)run * gr.nseg + seg) * npix;
+#pragma unroll
+    for (int k = 0; k < NPT; k++) {
+        const int o = tid + (k0 + k) * S;
+        if (k < kn && live && o < npix) dst[o] = acc[k];
+    }
 }
 
 // K4d: the same for boxes whose image does not fit the LDS (transform_sum_kernel stops at ~140 pixels): workgroup = (segment, run,
