@@ -16,6 +16,7 @@
 #include "ralign_geom.h"
 #include "ralign_kernels.h"
 #include "ralign_generic.h"
+#include "ralign_xform.h"
 #include "ralign_zone.h"
 #include "ralign_fused.h"
 #include "ralign_tiled.h"
@@ -35,6 +36,66 @@ void set_error(const std::string &msg) { g_last_error = msg; }
 // device workspace of one engine, shared by ra_create and the size checks of the reference surface
 // (pre_align_size_check / ref_free_alignment_2D_size_check), so that the estimate cannot drift from what is allocated
 #define RA_XS_LDS_MAX ((size_t)80 * 1024)      // padded image copy of transform_sum_kernel: two workgroups of 1024 threads share a CU
+
+// ---- which kernel of ralign_xform.h a box goes to, decided here and nowhere else (no device is asked)
+
+// transform_kernel keeps the image in this much LDS; transform_generic_kernel takes the boxes beyond a workgroup's 160 KB (203 pixels on)
+static size_t xf_lds_bytes(int nx) { return (size_t)((nx * nx + 3) & ~3) * sizeof(float); }
+static bool xf_in_lds(int nx) { return xf_lds_bytes(nx) <= (size_t)160 * 1024; }
+
+// rot_shift2D + class sums without the aligned stack
+typedef void (*xs_fn)(int, const float *, const ra_result *, const float2 *, const int *, const int *, int, float *);
+typedef void (*xs_db_fn)(int, const float *, const ra_result *, const float2 *, const int *, const int *, int, float *, XsGrid);
+struct XsPlan {
+    enum Kind { NONE, TWO_COPY, ONE_COPY, TILE } kind = NONE;
+    xs_db_fn dbfn = nullptr;      // TWO_COPY: transform_sum_db_kernel<sweeps per row band>
+    xs_fn fn = nullptr;           // ONE_COPY: transform_sum_kernel<sweeps per band, sweeps>; TILE: transform_sum_tile_kernel
+    const char *name = "";        // the kernel's row in the LDS ledger
+    int threads = 0;
+    size_t lds = 0;               // dynamic LDS of a workgroup
+    int npf = 0;                  // sweeps of the 1024-thread workgroup over the image (the whole-image kinds)
+    int sb0 = 0, nb0 = 0;         // TWO_COPY: sweeps per row band (at most 9 accumulators per thread), row bands
+    int nband = 1;                // ONE_COPY: row bands of at most 8 sweeps (9 accumulators and their prefetch registers are what 128 registers hold)
+    int ntile = 0;                // TILE: output tiles of 64 x 64 pixels
+    bool whole_image() const { return kind == TWO_COPY || kind == ONE_COPY; }
+    const void *kernel() const { return kind == TWO_COPY ? (const void *)dbfn : (const void *)fn; }
+};
+// Two copies of the padded image per workgroup where that still leaves room for two workgroups on a CU (up to 99 pixels); one
+// copy while it fits RA_XS_LDS_MAX (up to 141; up to 24 sweeps are instantiated); beyond, output tiles with the source box of
+// each in LDS.  NONE (boxes under 8 pixels): the aligned stack + class_sum_kernel.
+static XsPlan xs_plan(int nx)
+{
+    XsPlan p;
+    if (nx < 8) return p;
+    const size_t copy = (size_t)(nx + 2) * ((nx + 2) | 1) * sizeof(float);
+    const int ry = RA_XS_THREADS / std::min(nx, RA_XS_THREADS), npf = (nx + ry - 1) / ry;
+    if (nx <= RA_XS_THREADS && npf <= 24 && copy <= RA_XS_LDS_MAX) {
+        p.threads = RA_XS_THREADS; p.npf = npf;
+        if (2 * copy <= RA_XS_LDS_MAX) {
+            p.kind = XsPlan::TWO_COPY; p.name = "transform_sum_db_kernel"; p.lds = 2 * copy;
+            p.nb0 = (npf + 8) / 9; p.sb0 = (npf + p.nb0 - 1) / p.nb0;
+            p.dbfn = p.sb0 <= 1 ? transform_sum_db_kernel<1> : p.sb0 <= 2 ? transform_sum_db_kernel<2> : p.sb0 <= 4 ? transform_sum_db_kernel<4>
+                   : p.sb0 <= 6 ? transform_sum_db_kernel<6> : transform_sum_db_kernel<9>;
+        } else {
+            p.kind = XsPlan::ONE_COPY; p.name = "transform_sum_kernel"; p.lds = copy;
+            p.nband = npf <= 16 ? 2 : 3;
+            p.fn = npf <= 12 ? transform_sum_kernel<6, 12> : npf <= 16 ? transform_sum_kernel<8, 16> : npf <= 20 ? transform_sum_kernel<7, 20>
+                 : transform_sum_kernel<8, 24>;
+        }
+    } else if (nx >= RA_XT_BB) {
+        p.kind = XsPlan::TILE; p.name = "transform_sum_tile_kernel"; p.fn = transform_sum_tile_kernel; p.threads = RA_XT_THREADS;
+        p.lds = (size_t)2 * RA_XT_BB * RA_XT_BB * sizeof(float);
+        p.ntile = ((nx + RA_XT_TS - 1) / RA_XT_TS) * ((nx + RA_XT_TS - 1) / RA_XT_TS);
+    }
+    return p;
+}
+// runs every (class, parity) list of cn particles is cut into: ~1024 workgroups (TILE: ~2048, ntile of them per run already), at
+// least ~8 members per run on average
+static int xs_runs(const XsPlan &p, int nseg, int cn)
+{
+    const int nrun = p.kind == XsPlan::TILE ? std::min(64, 2048 / (nseg * p.ntile)) : std::min(512, (1024 + nseg - 1) / nseg);
+    return std::max(1, std::min(nrun, cn / (8 * nseg)));
+}
 
 struct WorkspacePlan {
     int chunk;
@@ -76,18 +137,26 @@ struct ra_engine {
     int *d_refdup = nullptr;                        // [2 nref] copies of a reference inside the stack (DevGeom::ref_dup)
     int *d_twxoff = nullptr, *d_rcount = nullptr;
     RefineRec *d_rlist = nullptr;
-    int *d_members = nullptr, *d_mcount = nullptr;      // [2 nref][chunk] member lists of a chunk, [2 nref] their lengths (class_members_kernel)
-    float *d_sumpart = nullptr;         // [16][2 nref][nx*nx] per-run partial class sums (few classes: class_sum_kernel with runs)
-    // transform_sum_kernel (rot_shift2D + class sums in one pass): member lists of a whole batch and per-run partial sums
-    int *d_xs_members = nullptr, *d_xs_mcount = nullptr;
-    float *d_xs_partial = nullptr;
-    float2 *d_xs_trig = nullptr;
-    size_t xs_cap_members = 0, xs_cap_partial = 0, xs_cap_trig = 0;
-    int xs_slots = 0;          // workgroups of transform_sum_db_kernel resident on the device at once (occupancy query at first use)
+    // buffers of the class sums (ralign_xform.h), allocated on first use
+    struct {
+        // through the aligned stack (class_sum_kernel), sized for a chunk at first use
+        int *members = nullptr;         // [2 nref][chunk] member lists of a chunk (class_members_wide_kernel)
+        int *mcount = nullptr;          // [2 nref] their lengths
+        float *sumpart = nullptr;       // [16][2 nref][nx*nx] per-run partial sums (few classes: class_sum_kernel with runs)
+        // in one pass with rot_shift2D (transform_sum), grown to the largest batch seen
+        int *xs_members = nullptr;      // [2 nref][batch] member lists of a batch
+        size_t cap_members = 0;
+        int *xs_mcount = nullptr;       // [2 nref] their lengths
+        float *xs_partial = nullptr;    // [runs][2 nref][nx*nx] per-run partial sums
+        size_t cap_partial = 0;
+        float2 *xs_trig = nullptr;      // [batch] (cos, sin) of every particle's angle (transform_trig_kernel)
+        size_t cap_trig = 0;
+        int xs_slots = 0;               // workgroups of transform_sum_db_kernel resident on the device at once (occupancy query at first use)
+    } cs;
     bool atomic_sums = false;           // RALIGN_ATOMIC_SUMS=1: fp32 atomics instead of particle-order sums
     int *d_ring_off = nullptr, *d_numr = nullptr;
     float *d_wr = nullptr;
-    size_t lds_polar = 0, lds_ref = 0, lds_ccf = 0, lds_xf = 0;
+    size_t lds_polar = 0, lds_ref = 0, lds_ccf = 0;
     bool force_generic = false;         // options that only the size-generic kernels implement (ra_create_ex)
     // the class of this engine's plan (ralign_plan.h), decided once per plan: create_engine, ra_reset_shifts.  What the class
     // wants; fused / tiled / solo / duo / pair below say what the LDS plans then gave.
@@ -96,7 +165,6 @@ struct ra_engine {
     bool tcrop = false;                 // generic class, but the search runs search_tiled_kernel over a CROP of the image (tcrop_wanted)
     int crop_S = 0;                     // ... whose side was planned for search shifts of up to this many pixels
     int crop_pst = 0;                   // ... and its row stride in LDS (tcrop_wanted)
-    bool xf_generic = false;            // image does not fit LDS in transform_kernel
     float2 *d_zscr = nullptr;           // [g_nblk][maxrin][64 TM TR] CCF spectra scratch of ccf_generic_kernel
     // polar stage with the image in LDS, ring zone by ring zone (ralign_zone.h); the global-tap kernel stays underneath
     ZonePlanHost zplan;
@@ -661,9 +729,10 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, con
     const size_t search_ws = resident ? bf * (sizeof(float) + sizeof(int)) + fcand * sizeof(CandT)      // B stream + its gather table
                                       : w.a_floats * sizeof(float) + (w.cand_recs + fcand) * sizeof(CandT);
     // rot_shift2D + class sums: member lists, per-run partial sums and cos / sin of a batch (transform_sum_kernel), or -- images
-    // that do not fit the LDS -- the aligned images of a chunk, their member lists and 16 runs of partial sums
+    // that do not fit the LDS -- the aligned images of a chunk, their member lists and 16 runs of partial sums.  (The boxes of
+    // transform_sum_tile_kernel are counted with the latter, which overestimates them: they write no aligned stack either.)
     const size_t npix = (size_t)g.nx * g.nx, nseg = 2 * (size_t)cfg.nref;
-    const bool xs = (size_t)(g.nx + 2) * ((g.nx + 2) | 1) * sizeof(float) <= RA_XS_LDS_MAX && g.nx <= 1024;
+    const bool xs = xs_plan(g.nx).whole_image();
     const size_t sums_ws = xs ? nseg * chunk * sizeof(int) + std::min<size_t>(512, (1024 + nseg - 1) / nseg) * nseg * npix * sizeof(float) + (size_t)chunk * sizeof(float2)
                               : w.alscratch_floats * sizeof(float) + nseg * chunk * sizeof(int) + 16 * nseg * npix * sizeof(float);
     // sub-bin refinement (ralign_exact.h): exact reference spectra, the list of flagged particles, global ring buffers of large boxes
@@ -1242,14 +1311,12 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
                             4 * e->dg.n_job + 32 + 8 * g.nring) * sizeof(float);
     e->lds_ref = (size_t)(npix_pad + e->dg.sbuf + 8) * sizeof(float);
     e->lds_ccf = (size_t)64 * (2 * (g.maxrin + g.maxrin / 16) + 2) * sizeof(float);
-    e->lds_xf = (size_t)npix_pad * sizeof(float);
     const size_t lds_max = 160 * 1024;
     if (!e->generic && (e->lds_polar > lds_max || e->lds_ccf > lds_max)) {
         g_last_error = "image / ring geometry does not fit the 160 KB LDS of one CU";
         ra_destroy(e);
         return RA_ERR_ARG;
     }
-    e->xf_generic = e->lds_xf > lds_max;
     // generic contraction: P pairs per inverse-FFT batch, two N-point buffers per pair
     e->g_P = 64;
     while (e->g_P > 1 && (size_t)e->g_P * (g.maxrin + 1) * sizeof(float2) > 66 * 1024) e->g_P >>= 1;      // two workgroups per CU
@@ -1273,7 +1340,7 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
             if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<4, 7>, "gccf_ifft_kernel<4, 7>", lds2);
         }
     }
-    if (!rc && !e->xf_generic) rc = RA_LDS(e, transform_kernel, e->lds_xf);
+    if (!rc && xf_in_lds(g.nx)) rc = RA_LDS(e, transform_kernel, xf_lds_bytes(g.nx));
     if (!rc) rc = RA_LDS(e, class_sum_kernel, (size_t)160 * 1024 - 64);
     if (rc) { ra_destroy(e); return rc; }
 
@@ -1894,129 +1961,86 @@ extern "C" int ra_debug_spectra(ra_engine *e, const float *d_particles, int n, c
     return RA_OK;
 }
 
-// rot_shift2D + class sums without the aligned stack (transform_sum_kernel): member lists of up to RA_XS_BATCH particles at
-// once, every (class, parity) list cut into runs so that ~1000 workgroups share the work
-#define RA_XS_BATCH 65536
-typedef void (*xs_fn)(int, const float *, int, int, const ra_result *, const float2 *, const int *, const int *, int, float *);
-// sweeps of the 1024-thread workgroup over the image: up to 24 (three row bands of 8) are instantiated
-static bool xs_sweeps_fit(int nx)
+// ---- rot_shift2D and the class sums (ralign_xform.h; xs_plan at the top of this file)
+
+// rot_shift2D of n images, with fp32-atomic sums and counts where they are not null: the image in LDS while it fits, read from
+// global memory beyond.  e == null: no engine, whose create raised transform_kernel's LDS.
+static int launch_transform(hipStream_t stream, ra_engine *e, int nx, const float *d_in, int n, int index0, const ra_result *d_res,
+                            float *d_aligned, float *d_sums, int *d_counts)
 {
-    if (nx < 8 || nx > RA_XS_THREADS) return false;
-    const int ry = RA_XS_THREADS / nx;
-    return (nx + ry - 1) / ry <= 24;
+    const int npix = nx * nx;
+    if (xf_in_lds(nx)) {
+        if (!e) { if (const int rc = RA_LDS(nullptr, transform_kernel, xf_lds_bytes(nx))) return rc; }
+        hipLaunchKernelGGL(transform_kernel, dim3(n), dim3(RA_XF_THREADS), xf_lds_bytes(nx), stream, nx, d_in, n, index0, d_res, d_aligned,
+                           d_sums, d_counts);
+    } else
+        // (at least 8 row blocks per image; a handful of images -- the references of an update step -- are cut into more: 10 images x 8 blocks left the GPU idle)
+        hipLaunchKernelGGL(transform_generic_kernel, dim3(n, std::max(8, std::min((npix + 255) / 256, (2048 + n - 1) / n))), dim3(256), 0, stream,
+                           nx, d_in, n, index0, d_res, d_aligned, d_sums, d_counts);
+    RA_HIP(hipGetLastError());
+    return RA_OK;
 }
-// one copy of the padded image (transform_sum_kernel): the boxes from 100 pixels on, whose two copies would not leave room for a
-// second workgroup (select_xs_db takes everything below): row bands of at most 8 sweeps per workgroup (9 accumulators and their
-// prefetch registers are what 128 registers hold)
-static xs_fn select_xs(int nx, int *nband)
-{
-    const int ry = RA_XS_THREADS / nx, npt = (nx + ry - 1) / ry;      // sweeps of the workgroup over the image
-    if (npt <= 12) { *nband = 2; return transform_sum_kernel<6, 12>; }
-    if (npt <= 16) { *nband = 2; return transform_sum_kernel<8, 16>; }
-    if (npt <= 20) { *nband = 3; return transform_sum_kernel<7, 20>; }
-    if (npt <= 24) { *nband = 3; return transform_sum_kernel<8, 24>; }
-    return nullptr;
-}
-// two copies of the padded image per workgroup where that still leaves room for two workgroups on a CU (transform_sum_db_kernel):
-// sweeps per row band (at most 9 accumulators per thread, as above) and the instantiation that holds them
-typedef void (*xs_db_fn)(int, const float *, const ra_result *, const float2 *, const int *, const int *, int, float *, XsGrid);
-static xs_db_fn select_xs_db(int nx, int *npf_out, int *sb0_out, int *nb0_out)
-{
-    if (nx < 8 || 2 * (size_t)(nx + 2) * ((nx + 2) | 1) * sizeof(float) > RA_XS_LDS_MAX) return nullptr;
-    const int ry = RA_XS_THREADS / nx, npf = (nx + ry - 1) / ry;      // sweeps of the workgroup over the image
-    const int nb0 = (npf + 8) / 9, sb0 = (npf + nb0 - 1) / nb0;
-    *npf_out = npf; *sb0_out = sb0; *nb0_out = nb0;
-    if (sb0 <= 1) return transform_sum_db_kernel<1>;
-    if (sb0 <= 2) return transform_sum_db_kernel<2>;
-    if (sb0 <= 4) return transform_sum_db_kernel<4>;
-    if (sb0 <= 6) return transform_sum_db_kernel<6>;
-    return transform_sum_db_kernel<9>;
-}
-// the whole image in LDS (transform_sum_kernel), or -- larger boxes -- output tiles with the source box of each in LDS
-// (transform_sum_tile_kernel; RALIGN_XTILE=0: the aligned stack + class_sum_kernel as before)
-static bool xs_whole_image(const ra_engine *e)
-{
-    if (e->xf_generic || !xs_sweeps_fit(e->geo.nx)) return false;
-    return (size_t)(e->geo.nx + 2) * ((e->geo.nx + 2) | 1) * sizeof(float) <= RA_XS_LDS_MAX;
-}
+
+// (RALIGN_XSUM=0 / RALIGN_XTILE=0, read at the launch: the aligned stack + class_sum_kernel instead, for every box / for the tile boxes)
 static bool xs_usable(const ra_engine *e)
 {
-    if (e->atomic_sums) return false;
-    if (env_int("RALIGN_XSUM", 1) == 0) return false;
-    if (xs_whole_image(e)) return true;
-    return e->geo.nx >= RA_XT_BB && env_int("RALIGN_XTILE", 1) != 0;
+    if (e->atomic_sums || env_int("RALIGN_XSUM", 1) == 0) return false;
+    const XsPlan p = xs_plan(e->geo.nx);
+    return p.whole_image() || (p.kind == XsPlan::TILE && env_int("RALIGN_XTILE", 1) != 0);
 }
+
+// rot_shift2D + class sums without the aligned stack: member lists of up to RA_XS_BATCH particles at once, every
+// (class, parity) list cut into runs (xs_runs)
+#define RA_XS_BATCH 65536
 static int transform_sum(ra_engine *e, const float *d_particles, int n, int index0, const ra_result *d_result, float *d_sums, int *d_counts)
 {
     const int nx = e->geo.nx, npix = nx * nx, nseg = 2 * e->cfg.nref;
-    int nband = 1;
-    const bool tiles = !xs_whole_image(e);
-    int npf = 0, sb0 = 0, nb0 = 0;
-    const xs_db_fn dbfn = tiles ? nullptr : select_xs_db(nx, &npf, &sb0, &nb0);
-    const xs_fn fn = tiles ? transform_sum_tile_kernel : dbfn ? nullptr : select_xs(nx, &nband);
-    if (!dbfn && !fn) { g_last_error = "transform_sum: no kernel for this box"; return RA_ERR_ARG; }
-    const int ntile = ((nx + RA_XT_TS - 1) / RA_XT_TS) * ((nx + RA_XT_TS - 1) / RA_XT_TS);
-    const size_t xs_lds = tiles ? (size_t)2 * RA_XT_BB * RA_XT_BB * sizeof(float) : (size_t)(nx + 2) * ((nx + 2) | 1) * sizeof(float);
-    if (dbfn) {
-        if (2 * xs_lds > 64 * 1024) {
-            const int rc = raise_dynamic_lds(e, (const void *)dbfn, "transform_sum_db_kernel", 2 * xs_lds);
-            if (rc) return rc;
-        }
-        if (!e->xs_slots) {
-            int per_cu = 0;
-            RA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)dbfn, RA_XS_THREADS, 2 * xs_lds));
-            e->xs_slots = std::max(1, per_cu) * std::max(1, e->n_cu);
-        }
-    } else if (xs_lds > 64 * 1024) {
-        const int rc = raise_dynamic_lds(e, (const void *)fn, tiles ? "transform_sum_tile_kernel" : "transform_sum_kernel", xs_lds);
-        if (rc) return rc;
+    const XsPlan p = xs_plan(nx);
+    if (p.kind == XsPlan::NONE) { g_last_error = "transform_sum: no kernel for this box"; return RA_ERR_ARG; }
+    auto &cs = e->cs;
+    int rc;
+    if (p.lds > 64 * 1024 && (rc = raise_dynamic_lds(e, p.kernel(), p.name, p.lds))) return rc;
+    if (p.kind == XsPlan::TWO_COPY && !cs.xs_slots) {
+        int per_cu = 0;
+        RA_HIP(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, p.kernel(), p.threads, p.lds));
+        cs.xs_slots = std::max(1, per_cu) * std::max(1, e->n_cu);
     }
+    auto reserve = [e](auto **buf, size_t *cap, size_t need) {
+        if (need <= *cap) return (int)RA_OK;
+        const int rcg = dev_grow(e, buf, need, false);
+        if (!rcg) *cap = need;
+        return rcg;
+    };
     for (int start = 0; start < n; start += RA_XS_BATCH) {
-        const int cn = std::min(RA_XS_BATCH, n - start);
-        // runs per segment: ~1024 workgroups, at least ~8 members per run on average
-        int nrun = std::max(1, std::min(512, (1024 + nseg - 1) / nseg));
-        if (tiles) nrun = std::max(1, std::min(64, 2048 / (nseg * ntile)));      // ntile workgroups per (segment, run) already
-        nrun = std::max(1, std::min(nrun, cn / (8 * nseg)));
-        const size_t need_m = (size_t)nseg * cn, need_p = (size_t)nrun * nseg * npix;
-        if (need_m > e->xs_cap_members) {
-            int rc = dev_grow(e, &e->d_xs_members, need_m, false);
-            if (rc) return rc;
-            e->xs_cap_members = need_m;
-        }
-        if (!e->d_xs_mcount) { int rc = dev_alloc(e, &e->d_xs_mcount, (size_t)nseg, true); if (rc) return rc; }
-        if ((size_t)cn > e->xs_cap_trig) {
-            int rc = dev_grow(e, &e->d_xs_trig, (size_t)cn, false);
-            if (rc) return rc;
-            e->xs_cap_trig = cn;
-        }
-        hipLaunchKernelGGL(transform_trig_kernel, dim3((cn + 255) / 256), dim3(256), 0, e->stream, d_result + start, cn, e->d_xs_trig);
+        const int cn = std::min(RA_XS_BATCH, n - start), nrun = xs_runs(p, nseg, cn);
+        if ((rc = reserve(&cs.xs_members, &cs.cap_members, (size_t)nseg * cn)) || (rc = reserve(&cs.xs_trig, &cs.cap_trig, (size_t)cn)) ||
+            (rc = reserve(&cs.xs_partial, &cs.cap_partial, (size_t)nrun * nseg * npix)) ||
+            (!cs.xs_mcount && (rc = dev_alloc(e, &cs.xs_mcount, (size_t)nseg, true)))) return rc;
+        const float *part = d_particles + (size_t)start * npix;
+        const ra_result *res = d_result + start;
+        const float2 *trig = cs.xs_trig;
+        const int *members = cs.xs_members, *mcount = cs.xs_mcount;
+        hipLaunchKernelGGL(transform_trig_kernel, dim3((cn + 255) / 256), dim3(256), 0, e->stream, res, cn, cs.xs_trig);
         RA_HIP(hipGetLastError());
-        if (need_p > e->xs_cap_partial) {
-            int rc = dev_grow(e, &e->d_xs_partial, need_p, false);
-            if (rc) return rc;
-            e->xs_cap_partial = need_p;
-        }
-        hipLaunchKernelGGL(class_members_wide_kernel, dim3(nseg), dim3(1024), 0, e->stream, d_result + start, cn, index0 + start,
-                           e->d_xs_members, e->d_xs_mcount, cn, d_counts);
+        hipLaunchKernelGGL(class_members_wide_kernel, dim3(nseg), dim3(1024), 0, e->stream, res, cn, index0 + start, cs.xs_members, cs.xs_mcount, cn,
+                           d_counts);
         RA_HIP(hipGetLastError());
-        if (dbfn) {
+        if (p.kind == XsPlan::TWO_COPY) {
             // a small surplus of work items over whole rounds of resident workgroups would hold a round of its own: those
             // items run as row bands, a third of the sweeps each, behind the full ones
-            const int items = nseg * nrun, over = items % e->xs_slots;
-            XsGrid gr{nseg, nrun, items, sb0, nb0, sb0, 1};
-            if (nb0 == 1 && npf >= 2 && items > e->xs_slots && over > 0 && over * 8 <= e->xs_slots) {
-                gr.sb1 = (npf + 2) / 3; gr.nb1 = (npf + gr.sb1 - 1) / gr.sb1; gr.nfull = items - over;
+            const int items = nseg * nrun, over = items % cs.xs_slots;
+            XsGrid gr{nseg, nrun, items, p.sb0, p.nb0, p.sb0, 1};
+            if (p.nb0 == 1 && p.npf >= 2 && items > cs.xs_slots && over > 0 && over * 8 <= cs.xs_slots) {
+                gr.sb1 = (p.npf + 2) / 3; gr.nb1 = (p.npf + gr.sb1 - 1) / gr.sb1; gr.nfull = items - over;
             }
-            hipLaunchKernelGGL(dbfn, dim3(gr.nfull * gr.nb0 + (items - gr.nfull) * gr.nb1), dim3(RA_XS_THREADS), 2 * xs_lds, e->stream, nx,
-                               d_particles + (size_t)start * npix, d_result + start, (const float2 *)e->d_xs_trig, (const int *)e->d_xs_members,
-                               (const int *)e->d_xs_mcount, cn, e->d_xs_partial, gr);
-        } else
-            hipLaunchKernelGGL(fn, dim3(nseg, nrun, tiles ? ntile : nband), dim3(tiles ? RA_XT_THREADS : RA_XS_THREADS), xs_lds, e->stream, nx,
-                               d_particles + (size_t)start * npix, cn, index0 + start, d_result + start, (const float2 *)e->d_xs_trig, (const int *)e->d_xs_members,
-                               (const int *)e->d_xs_mcount, cn, e->d_xs_partial);
+            hipLaunchKernelGGL(p.dbfn, dim3(gr.nfull * gr.nb0 + (items - gr.nfull) * gr.nb1), dim3(p.threads), p.lds, e->stream, nx, part, res, trig,
+                               members, mcount, cn, cs.xs_partial, gr);
+        } else          // (segment, run, row band | output tile)
+            hipLaunchKernelGGL(p.fn, dim3(nseg, nrun, p.kind == XsPlan::TILE ? p.ntile : p.nband), dim3(p.threads), p.lds, e->stream, nx, part, res, trig,
+                               members, mcount, cn, cs.xs_partial);
         RA_HIP(hipGetLastError());
         hipLaunchKernelGGL(class_sum_combine_kernel, dim3((unsigned)(((size_t)nseg * npix + 255) / 256)), dim3(256), 0, e->stream, npix, nseg, nrun,
-                           (const float *)e->d_xs_partial, d_sums);
+                           (const float *)cs.xs_partial, d_sums);
         RA_HIP(hipGetLastError());
     }
     return RA_OK;
@@ -2029,59 +2053,37 @@ extern "C" int ra_transform_accumulate(ra_engine *e, const float *d_particles, i
     if (n == 0) return RA_OK;
     if (!d_particles || !d_result) { g_last_error = "null argument"; return RA_ERR_ARG; }
     const int nx = e->geo.nx, npix = nx * nx;
-    if (!d_sums || e->atomic_sums) {
-        if (e->xf_generic)
-            // (a handful of images -- the references of an update step -- are cut into more row blocks: 10 images x 8 blocks left the GPU idle)
-            hipLaunchKernelGGL(transform_generic_kernel, dim3(n, std::max(8, std::min((npix + 255) / 256, (2048 + n - 1) / n))), dim3(256), 0, e->stream, nx, d_particles, n, index0,
-                               d_result, d_aligned, d_sums, d_counts);
-        else
-            hipLaunchKernelGGL(transform_kernel, dim3(n), dim3(RA_XF_THREADS), e->lds_xf, e->stream, nx, d_particles, n, index0,
-                               d_result, d_aligned, d_sums, d_counts);
-        RA_HIP(hipGetLastError());
-        return RA_OK;
-    }
+    if (!d_sums || e->atomic_sums) return launch_transform(e->stream, e, nx, d_particles, n, index0, d_result, d_aligned, d_sums, d_counts);
     if (!d_aligned && xs_usable(e)) return transform_sum(e, d_particles, n, index0, d_result, d_sums, d_counts);
-    // aligned images wanted as well (or an image too large for the LDS): aligned images of a chunk, then particle-order sums per
+    // aligned images wanted as well (or no one-pass kernel for the box): aligned images of a chunk, then particle-order sums per
     // (class, parity)
-    if (!d_aligned && !e->d_alscratch) {
-        int rca = dev_alloc(e, &e->d_alscratch, e->wp.alscratch_floats, false);
-        if (rca) return rca;
-    }
+    auto &cs = e->cs;
+    int rc;
+    if (!d_aligned && !e->d_alscratch && (rc = dev_alloc(e, &e->d_alscratch, e->wp.alscratch_floats, false))) return rc;
+    // member lists once per chunk; every (class, parity) list is then cut into runs so that ~4000 workgroups share the additions
+    const int nseg = 2 * e->cfg.nref, ntile = (npix + 255) / 256;
+    const bool glists = (size_t)nseg * e->chunk * sizeof(int) <= ((size_t)256 << 20);
+    const int nrun = std::min(16, std::max(1, (glists ? 4096 : 1024) / (nseg * ntile)));
+    if (glists && !cs.members &&
+        ((rc = dev_alloc(e, &cs.members, (size_t)nseg * e->chunk, false)) || (rc = dev_alloc(e, &cs.mcount, (size_t)nseg, true)))) return rc;
+    if (nrun > 1 && !cs.sumpart && (rc = dev_alloc(e, &cs.sumpart, (size_t)16 * nseg * npix, false))) return rc;
     for (int start = 0; start < n; start += e->chunk) {
         const int cn = std::min(e->chunk, n - start);
         float *al = d_aligned ? d_aligned + (size_t)start * npix : e->d_alscratch;
-        if (e->xf_generic)
-            hipLaunchKernelGGL(transform_generic_kernel, dim3(cn, 8), dim3(256), 0, e->stream, nx, d_particles + (size_t)start * npix,
-                               cn, index0 + start, d_result + start, al, (float *)nullptr, (int *)nullptr);
-        else
-            hipLaunchKernelGGL(transform_kernel, dim3(cn), dim3(RA_XF_THREADS), e->lds_xf, e->stream, nx, d_particles + (size_t)start * npix,
-                               cn, index0 + start, d_result + start, al, (float *)nullptr, (int *)nullptr);
-        RA_HIP(hipGetLastError());
-        // member lists once per chunk (class_members_kernel); every (class, parity) list is then cut into runs so that ~4000
-        // workgroups share the additions
-        const int nseg = 2 * e->cfg.nref, ntile = (npix + 255) / 256;
-        const bool glists = (size_t)nseg * e->chunk * sizeof(int) <= ((size_t)256 << 20);
-        if (glists && !e->d_members) {
-            int rcm = dev_alloc(e, &e->d_members, (size_t)nseg * e->chunk, false);
-            if (!rcm) rcm = dev_alloc(e, &e->d_mcount, (size_t)nseg, true);
-            if (rcm) return rcm;
-        }
-        const int nrun = std::min(16, std::max(1, (glists ? 4096 : 1024) / (nseg * ntile)));
-        if (nrun > 1 && !e->d_sumpart) {
-            int rcp = dev_alloc(e, &e->d_sumpart, (size_t)16 * nseg * npix, false);
-            if (rcp) return rcp;
-        }
-        if (glists) {
-            hipLaunchKernelGGL(class_members_kernel, dim3(nseg), dim3(64), 0, e->stream, d_result + start, cn, index0 + start, e->d_members, e->d_mcount);
+        if ((rc = launch_transform(e->stream, e, nx, d_particles + (size_t)start * npix, cn, index0 + start, d_result + start, al, nullptr, nullptr)))
+            return rc;
+        if (glists) {          // (the counts are class_sum_kernel's to add on this path)
+            hipLaunchKernelGGL(class_members_wide_kernel, dim3(nseg), dim3(1024), 0, e->stream, d_result + start, cn, index0 + start, cs.members,
+                               cs.mcount, cn, (int *)nullptr);
             RA_HIP(hipGetLastError());
         }
         hipLaunchKernelGGL(class_sum_kernel, dim3(nseg, ntile, nrun), dim3(256), glists ? 0 : (size_t)cn * sizeof(int), e->stream, npix, al,
-                           d_result + start, cn, index0 + start, d_sums, d_counts, nrun > 1 ? e->d_sumpart : (float *)nullptr,
-                           glists ? (const int *)e->d_members : (const int *)nullptr, (const int *)e->d_mcount);
+                           d_result + start, cn, index0 + start, d_sums, d_counts, nrun > 1 ? cs.sumpart : (float *)nullptr,
+                           (const int *)cs.members, (const int *)cs.mcount);
         RA_HIP(hipGetLastError());
         if (nrun > 1) {
             hipLaunchKernelGGL(class_sum_combine_kernel, dim3((unsigned)(((size_t)nseg * npix + 255) / 256)), dim3(256), 0, e->stream, npix, nseg, nrun,
-                               (const float *)e->d_sumpart, d_sums);
+                               (const float *)cs.sumpart, d_sums);
             RA_HIP(hipGetLastError());
         }
     }
@@ -2431,17 +2433,5 @@ extern "C" int ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result 
     if (n == 0) return RA_OK;
     if (!d_in || !d_params || !d_out) { g_last_error = "ra_rot_shift2d: null argument"; return RA_ERR_ARG; }
     // the kernel and grid ra_transform_accumulate picks for the same box without sums
-    const int npix = nx * nx;
-    const size_t lds = (size_t)((npix + 3) & ~3) * sizeof(float);
-    hipError_t he = hipSuccess;
-    if (lds > (size_t)160 * 1024) {
-        hipLaunchKernelGGL(transform_generic_kernel, dim3(n, std::max(8, std::min((npix + 255) / 256, (2048 + n - 1) / n))), dim3(256), 0, stream,
-                           nx, d_in, n, 0, d_params, d_out, (float *)nullptr, (int *)nullptr);
-    } else {
-        if (const int rc = RA_LDS(nullptr, transform_kernel, lds)) return rc;
-        hipLaunchKernelGGL(transform_kernel, dim3(n), dim3(RA_XF_THREADS), lds, stream, nx, d_in, n, 0, d_params, d_out,
-                           (float *)nullptr, (int *)nullptr);
-    }
-    if (he == hipSuccess) he = hipGetLastError();
-    return he == hipSuccess ? RA_OK : hip_error("ra_rot_shift2d", he);
+    return launch_transform(stream, nullptr, nx, d_in, n, 0, d_params, d_out, nullptr, nullptr);
 }

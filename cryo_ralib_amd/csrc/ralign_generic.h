@@ -14,7 +14,7 @@
 //                                scratch (they do not fit LDS at maxrin >= 512), are inverse
 //                                transformed in LDS a few pairs at a time and reduced by a
 //                                wavefront argmax.
-//   transform_generic_kernel     rot_shift2D reading the image from global memory.
+// (rot_shift2D for images beyond the LDS, transform_generic_kernel, is ralign_xform.h's.)
 #pragma once
 
 #include <type_traits>
@@ -822,48 +822,6 @@ __global__ void ref_dc_weights_kernel(DevGeom g, const float *__restrict__ refsp
         s += (float)ri.z * refspec[(size_t)ref * g.lring + ri.x] * g.ent_wgt[e] * inv;
     }
     cdc[ref] = s;
-}
-
-// rot_shift2D for images that do not fit LDS: quadri_background reads global memory
-// (test_mref_gpu_align.py:1055; arithmetic of transform_kernel)
-__global__ __launch_bounds__(256) void transform_generic_kernel(int nx, const float *__restrict__ particles, int n,
-                                                                int index0, const ra_result *__restrict__ res,
-                                                                float *__restrict__ aligned, float *__restrict__ sums,
-                                                                int *__restrict__ counts)
-{
-#pragma clang fp contract(off)
-    const int p = blockIdx.x, tid = threadIdx.x, npix = nx * nx;
-    if (p >= n) return;
-    const float *img = particles + (size_t)p * npix;
-    const ra_result r = res[p];
-    const float ang = r.alpha * (float)M_PI / 180.0f;
-    float delx = r.sx, dely = r.sy;
-    while (delx >= (float)nx) delx -= nx;
-    while (delx <= -(float)nx) delx += nx;
-    while (dely >= (float)nx) dely -= nx;
-    while (dely <= -(float)nx) dely += nx;
-    const int xc = nx / 2, yc = nx / 2;
-    const float shiftxc = xc + delx, shiftyc = yc + dely;
-    const float cang = (float)cos((double)ang), sang = (float)sin((double)ang);
-    float *dsum = sums ? sums + ((size_t)r.ref_id * 2 + ((index0 + p) & 1)) * npix : nullptr;
-    float *dal = aligned ? aligned + (size_t)p * npix : nullptr;
-    const int mstart = 1 - nx % 2;
-    for (int i = blockIdx.y * blockDim.x + tid; i < npix; i += gridDim.y * blockDim.x) {
-        const int iy = i / nx, ix = i - iy * nx;
-        float y = (float)iy - shiftyc;
-        float ycang = y * cang + yc;
-        float ysang = -y * sang + xc;
-        float x = (float)ix - shiftxc;
-        float xold = x * cang + ysang;
-        float yold = x * sang + ycang;
-        float v = quadri_background_1b(img, nx, nx, xold + 1.0f, yold + 1.0f, ix + 1, iy + 1);
-        int ox = ix;
-        if (r.mirror && ix >= mstart) ox = mstart + (nx - 1) - ix;
-        const int o = iy * nx + ox;
-        if (dal) dal[o] = v;
-        if (dsum) atomicAdd(dsum + o, v);
-    }
-    if (counts && tid == 0 && blockIdx.y == 0) atomicAdd(counts + r.ref_id, 1);
 }
 
 }  // namespace ralign

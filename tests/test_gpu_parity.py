@@ -17,6 +17,7 @@ import torch
 from cryo_ralib_amd import api, geometry, synth
 from cryo_ralib_amd.mref import MrefAligner, RefFreeAligner
 from oracle import oracle as orc
+from xsum_cases import xs_runs
 
 pytestmark = pytest.mark.gpu
 
@@ -661,14 +662,6 @@ def test_command_line_entry_points(tmp_path):
     assert "EMAN.xform.align2d" in at[0] and int(at[5]["EMAN.source_n"]) == 5
 
 
-def _xs_runs(n, nseg, nx=0):
-    """runs per (class, parity) list of transform_sum_kernel / transform_sum_tile_kernel (ralign_engine.hip: transform_sum)"""
-    nrun = max(1, min(512, (1024 + nseg - 1) // nseg))
-    if nx > 141:          # output tiles of 64 x 64 pixels: that many workgroups per run already
-        nrun = max(1, min(64, 2048 // (nseg * ((nx + 63) // 64) ** 2)))
-    return max(1, min(nrun, n // (8 * nseg)))
-
-
 @pytest.mark.parametrize("nx,ou,xr", [(90, 36, 3), (33, 12, 2), (64, 24, 3), (130, 52, 3),
                                       (200, 40, 3), (161, 45, 2), (256, 30, 4)])      # transform_sum_tile_kernel: even, odd, 16 full tiles
 def test_class_sums_are_bitwise_reproducible(nx, ou, xr):
@@ -725,7 +718,7 @@ def test_class_sums_are_bitwise_reproducible(nx, ou, xr):
         return want
 
     # transform_sum_kernel: one batch (n < 65536), runs from a zero partial sum even when there is one run only
-    nrun = _xs_runs(n, 2 * nref, nx)
+    nrun = xs_runs(n, 2 * nref, nx)
     want = np.zeros((nref, 2, nx, nx), np.float32)
     for c in range(nref):
         for par in range(2):

@@ -1,5 +1,5 @@
-"""The class-sum pass (rot_shift2D + class sums without the aligned stack: transform_sum_db_kernel, transform_sum_kernel,
-transform_sum_tile_kernel, class_sum_combine_kernel) entry by entry at its edges.
+"""The class-sum pass (csrc/ralign_xform.h; rot_shift2D + class sums without the aligned stack: transform_sum_db_kernel,
+transform_sum_kernel, transform_sum_tile_kernel, class_sum_combine_kernel) entry by entry at its edges.
 
 No search is run: the result records are written directly (as bench.py::generate_shard does), with poses chosen to hit the
 mirror, shifts beyond +-nx (the wrap loops), sources outside the image (the background rule) and angles at multiples of 90
@@ -24,19 +24,13 @@ import pytest
 import torch
 
 from cryo_ralib_amd import api
+from oracle import oracle as orc
+from xsum_cases import edge_poses, xs_runs
 
 pytestmark = pytest.mark.gpu
 
 BOXES = [32, 33, 64, 90, 91, 93, 94, 99, 100, 130, 140, 141, 142, 161]
 INDEX0 = 3
-
-
-def xs_runs(n, nseg, nx):
-    """runs per (class, parity) list (ralign_engine.hip: transform_sum; restated in test_gpu_parity.py::_xs_runs)"""
-    nrun = max(1, min(512, (1024 + nseg - 1) // nseg))
-    if nx > 141:          # output tiles of 64 x 64 pixels: that many workgroups per run already
-        nrun = max(1, min(64, 2048 // (nseg * ((nx + 63) // 64) ** 2)))
-    return max(1, min(nrun, n // (8 * nseg)))
 
 
 def edge_records(n, nx, nref, seg_counts, seed):
@@ -48,9 +42,7 @@ def edge_records(n, nx, nref, seg_counts, seed):
     rec["sx"] = rng.uniform(-3.0, 3.0, n).astype(np.float32)
     rec["sy"] = rng.uniform(-3.0, 3.0, n).astype(np.float32)
     rec["mirror"] = rng.integers(0, 2, n)
-    edge = [(0.0, 0.0, 0.0), (90.0, 0.5, -0.5), (180.0, 1.0, 2.0), (270.0, -1.5, 0.25), (360.0, 0.0, 0.0), (-90.0, 2.0, -2.0),
-            (12.5, nx + 1.25, 0.5), (200.0, -0.75, -(2 * nx + 0.5)), (45.0, float(nx), -float(nx)), (33.0, -(nx + 2.0), 3 * nx + 0.125),
-            (45.0, nx / 2 - 1.0, nx / 2 - 1.0), (135.0, -(nx / 2 - 1.5), 0.0), (0.0, 0.5, 0.5), (90.0, nx - 0.5, 0.0)]
+    edge = edge_poses(nx)
     for i in range(n):
         if i % 3 != 1:
             a, sx, sy = edge[(i // 3 + i) % len(edge)]
@@ -166,3 +158,58 @@ def test_twenty_segments_of_fifty_two_runs(nx):
     np.testing.assert_array_equal(got[0][0], got[1][0])
     np.testing.assert_array_equal(got[0][1], cnt.sum(axis=1))
     np.testing.assert_array_equal(got[0][0], restate(a, rec["ref_id"], nref, 52, start))
+
+
+@pytest.mark.parametrize("nx", [202, 203])
+def test_both_transform_kernels_at_the_lds_edge(nx):
+    """transform_kernel keeps the image in LDS up to 202 pixels (163 216 of a workgroup's 163 840 bytes); from 203 on
+    transform_generic_kernel reads it from global memory: the one rule of launch_transform (ralign_engine.hip).  On both sides of
+    it api.rot_shift2d (no engine) and Engine.transform_accumulate (aligned images alone) give the same bits, and those of the
+    oracle's rot_shift2d, which test_oracle.py pins to tests/golden/rot_shift2d_ref.npz."""
+    n = 6
+    rec = edge_records(n, nx, 1, {}, 800 + nx)
+    rng = np.random.default_rng(900 + nx)
+    parts = rng.standard_normal((n, nx, nx)).astype(np.float32)
+    eng = api.Engine(nx, 30, 1, 1, 1.0, 1, api.RA_MODE_MREF)
+    tp = torch.from_numpy(parts).to(eng.dev)
+    for mirror in (0, 1):
+        rec["mirror"] = mirror
+        res = torch.from_numpy(rec.view(np.int32).reshape(n, 8).copy()).to(eng.dev)
+        al = torch.zeros((n, nx, nx), device=eng.dev)
+        eng.transform_accumulate(tp, res, INDEX0, al, None, None)
+        eng.sync()
+        prm = np.stack([rec["alpha"], rec["sx"], rec["sy"], rec["mirror"]], axis=1)
+        free = api.rot_shift2d(tp, prm)
+        torch.cuda.synchronize(eng.dev)
+        want = np.stack([orc.rot_shift2d(parts[i], float(rec["alpha"][i]), float(rec["sx"][i]), float(rec["sy"][i]), mirror)
+                         for i in range(n)])
+        np.testing.assert_array_equal(al.cpu().numpy(), free.cpu().numpy())
+        np.testing.assert_array_equal(al.cpu().numpy(), want)
+    eng.close()
+
+
+def test_class_sum_kernel_compacts_its_own_list_beyond_256_mb_of_lists():
+    """2 x 1025 member lists of a chunk of 32768 exceed the 256 MB the engine spends on them: class_sum_kernel then runs without
+    class_members_wide_kernel, every workgroup compacting its segment's list into LDS (xf_compact), one run.  Aligned images
+    and sums of one call against the float32 restatement on those images."""
+    nx, nref, n = 32, 1025, 300
+    assert 2 * nref * 32768 * 4 > 256 << 20
+    rec = edge_records(n, nx, nref, {(0, 0): 1, (7, 1): 3, (1000, 0): 5}, 1100)
+    rng = np.random.default_rng(1101)
+    parts = rng.standard_normal((n, nx, nx)).astype(np.float32)
+    start = rng.standard_normal((nref, 2, nx, nx)).astype(np.float32)
+    eng = api.Engine(nx, 12, 1, 1, 1.0, nref, api.RA_MODE_MREF, chunk=32768)
+    tp = torch.from_numpy(parts).to(eng.dev)
+    res = torch.from_numpy(rec.view(np.int32).reshape(n, 8).copy()).to(eng.dev)
+    gs = torch.from_numpy(start.copy()).to(eng.dev)
+    gc = torch.zeros(nref, dtype=torch.int32, device=eng.dev)
+    al = torch.zeros((n, nx, nx), device=eng.dev)
+    eng.transform_accumulate(tp, res, INDEX0, al, gs, gc)
+    eng.sync()
+    a, got, cnt = al.cpu().numpy(), gs.cpu().numpy(), gc.cpu().numpy()
+    eng.close()
+    np.testing.assert_array_equal(cnt, np.bincount(rec["ref_id"], minlength=nref))
+    want = start.copy()
+    for i in range(n):          # one run: every member straight onto the sums, in particle order
+        want[rec["ref_id"][i], (INDEX0 + i) % 2] += a[i]
+    np.testing.assert_array_equal(got, want)
