@@ -12,6 +12,8 @@ import os
 
 import numpy as np
 
+from ._common import Launcher, ptr
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RALIGN_LIB") or os.path.join(_HERE, "libralign_hip.so")   # RALIGN_LIB: another build of the same library (kernel experiments)
 
@@ -254,10 +256,9 @@ def phase_flip(images, ctf, pad=True):
     tab = np.ascontiguousarray(ctf, np.float32)
     if tab.shape != (n, 9):
         raise EngineError("phase_flip: the CTF table is [%d][9], got %s" % (n, tab.shape))
-    stream = torch.cuda.current_stream(images.device)
+    L = Launcher(images)
     with torch.cuda.device(images.device):
-        _check(load_library().ra_phase_flip(ctypes.c_void_p(images.data_ptr()), n, nx, tab.ctypes.data_as(float_ptr),
-                                            int(bool(pad)), ctypes.c_void_p(stream.cuda_stream)), "ra_phase_flip")
+        L.call("ra_phase_flip", ptr(images), n, nx, tab.ctypes.data_as(float_ptr), int(bool(pad)))
     return images
 
 
@@ -280,10 +281,9 @@ def rot_shift2d(images, params, out=None):
         out = torch.empty_like(images)
     assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.shape == images.shape, "out: like images"
     d_rec = torch.from_numpy(rec.view(np.uint8)).to(images.device)
-    stream = torch.cuda.current_stream(images.device)
+    L = Launcher(images)
     with torch.cuda.device(images.device):
-        _check(load_library().ra_rot_shift2d(ctypes.c_void_p(images.data_ptr()), n, nx, ctypes.c_void_p(d_rec.data_ptr()),
-                                             ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream.cuda_stream)), "ra_rot_shift2d")
+        L.call("ra_rot_shift2d", ptr(images), n, nx, ptr(d_rec), ptr(out))
     return out
 
 
@@ -301,10 +301,9 @@ def fourier_resize(images, m, out=None):
         out = torch.empty((n, m, m), dtype=torch.float32, device=images.device)
     assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and out.device == images.device \
         and tuple(out.shape) == (n, m, m), "out: contiguous float32 [n][m][m] on the images' device"
-    stream = torch.cuda.current_stream(images.device)
+    L = Launcher(images)
     with torch.cuda.device(images.device):
-        _check(load_library().ra_fourier_resize(ctypes.c_void_p(images.data_ptr()), n, nx, m, ctypes.c_void_p(out.data_ptr()),
-                                                ctypes.c_void_p(stream.cuda_stream)), "ra_fourier_resize")
+        L.call("ra_fourier_resize", ptr(images), n, nx, m, ptr(out))
     return out
 
 

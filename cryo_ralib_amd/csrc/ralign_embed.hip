@@ -2,6 +2,7 @@
 // ralign_dbscan.h, ralign_hdbscan.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_* and ra_hdbscan_* entry points of
 // libralign_hip.so, each on the caller's stream.
 #include "ralign_host.h"
+#include "ralign_scratch.h"
 #include "ralign_kmeans.h"
 #include "ralign_validity.h"
 #include "ralign_dbscan.h"
@@ -118,13 +119,27 @@ static bool km_shape_ok(const char *what, int n, int d, int k)
     return true;
 }
 
-// carves aligned pieces out of one stream-ordered allocation
-struct KmScratch {
-    size_t off = 0;
-    unsigned char *base = nullptr;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-    template <class T> T *at(size_t o) { return (T *)(base + o); }
-};
+// the stable member lists of the labels: count [k], start [k], run0 [k + 1] (runs of L members), members [n]
+static hipError_t km_member_lists(const int *labels, int n, int k, int L, const KmLists &M, hipStream_t stream)
+{
+    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK;
+    int *bcnt = M.bcnt(), *cnt = M.cnt(), *start = M.start();
+    hipLaunchKernelGGL(km_hist_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, labels, n, k, bcnt);
+    hipError_t he = hipGetLastError();
+    RA_LAUNCH(he, km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt);
+    RA_LAUNCH(he, km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, M.run0());
+    RA_LAUNCH(he, km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, labels, n, k, (const int *)bcnt, (const int *)start, M.mem());
+    return he;
+}
+
+// the squared norms the MFMA E-step reads (d > KM_SMALL_D): the caller's, or computed into the scratch piece `own`
+static hipError_t km_norms(const float *x, int n, int d, const float *&nrm, float *own, hipStream_t stream)
+{
+    if (nrm || d <= KM_SMALL_D) return hipSuccess;
+    nrm = own;
+    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, x, n, d, own);
+    return hipGetLastError();
+}
 
 extern "C" int ra_kmeans_sqnorm(const float *d_x, int n, int d, float *d_nrm, void *hip_stream)
 {
@@ -175,14 +190,9 @@ extern "C" int ra_kmeans_labels(const float *d_x, int n, int d, const float *d_n
     const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_labels", scratch.status());
-    hipError_t he = hipSuccess;
     double *dist = S.at<double>(o_dist);
     const float *nrm = d_nrm;
-    if (big && !d_nrm) {
-        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3(nb), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
-        he = hipGetLastError();
-        nrm = S.at<float>(o_nrm);
-    }
+    hipError_t he = km_norms(d_x, n, d, nrm, S.at<float>(o_nrm), stream);
     if (he == hipSuccess) {
         if (assign) {
             he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, nullptr, S.at<float>(o_cf), S.at<float>(o_cn), stream);
@@ -206,33 +216,24 @@ extern "C" int ra_kmeans_lloyd(const float *d_x, int n, int d, const float *d_nr
     if (!d_x || !d_centers || !d_centers_new || !d_labels || !d_stats || d_centers_new == d_centers)
         return arg_error("ra_kmeans_lloyd: null argument, or d_centers_new == d_centers");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, L = km_run_len(n), rmax = (n + L - 1) / L + k;
+    const int L = km_run_len(n), rmax = (n + L - 1) / L + k;
     const bool big = d > KM_SMALL_D;
     KmScratch S;
-    const size_t o_dist = S.take((size_t)n * 8), o_ints = S.take(2 * 4), o_bcnt = S.take((size_t)nb * k * 4);
-    const size_t o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4), o_run0 = S.take((size_t)(k + 1) * 4);
-    const size_t o_mem = S.take((size_t)n * 4), o_part = S.take((size_t)rmax * d * 8), o_sums = S.take((size_t)k * d * 8);
-    const size_t o_wt = S.take((size_t)k * 8), o_shift = S.take((size_t)k * 8);
+    const KmLists M(S, n, k, KM_BLOCK);
+    const size_t o_dist = S.take((size_t)n * 8), o_ints = S.take(2 * 4), o_part = S.take((size_t)rmax * d * 8);
+    const size_t o_sums = S.take((size_t)k * d * 8), o_wt = S.take((size_t)k * 8), o_shift = S.take((size_t)k * 8);
     const size_t o_cf = S.take(big ? (size_t)k * d * 4 : 0), o_cn = S.take(big ? (size_t)k * 4 : 0);
     const size_t o_nrm = S.take(big && !d_nrm ? (size_t)n * 4 : 0);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_lloyd", scratch.status());
-    int *ints = S.at<int>(o_ints), *bcnt = S.at<int>(o_bcnt), *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start);
-    int *run0 = S.at<int>(o_run0), *mem = S.at<int>(o_mem);
+    int *ints = S.at<int>(o_ints), *cnt = M.cnt(), *start = M.start(), *run0 = M.run0(), *mem = M.mem();
     double *dist = S.at<double>(o_dist), *part = S.at<double>(o_part), *sums = S.at<double>(o_sums), *wt = S.at<double>(o_wt);
     double *shift = S.at<double>(o_shift);
     const float *nrm = d_nrm;
     hipError_t he = hipMemsetAsync(ints, 0, 2 * sizeof(int), stream);
-    if (he == hipSuccess && big && !d_nrm) {
-        hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, S.at<float>(o_nrm));
-        he = hipGetLastError();
-        nrm = S.at<float>(o_nrm);
-    }
+    if (he == hipSuccess) he = km_norms(d_x, n, d, nrm, S.at<float>(o_nrm), stream);
     if (he == hipSuccess) he = km_assign(d_x, n, d, nrm, d_centers, k, d_labels, dist, ints, S.at<float>(o_cf), S.at<float>(o_cn), stream);
-    RA_LAUNCH(he, km_hist_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, bcnt);
-    RA_LAUNCH(he, km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt);
-    RA_LAUNCH(he, km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, run0);
-    RA_LAUNCH(he, km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, (const int *)d_labels, n, k, (const int *)bcnt, (const int *)start, mem);
+    if (he == hipSuccess) he = km_member_lists(d_labels, n, k, L, M, stream);
     RA_LAUNCH(he, km_runsum_kernel, dim3(rmax), dim3(256), 0, stream, d_x, n, d, k, L, (const int *)mem, (const int *)cnt, (const int *)start,
                   (const int *)run0, part);
     RA_LAUNCH(he, km_combine_kernel, dim3(k), dim3(256), 0, stream, (const double *)part, d, (const int *)cnt, (const int *)run0, sums, wt);
@@ -280,34 +281,21 @@ extern "C" int ra_kmeans_seed(const float *d_x, int n, int d, const int *d_cand,
 
 // ---- cluster validity (ralign_validity.h)
 
-// the stable member lists of the labels: count [k], start [k], run0 [k + 1] (runs of L members), members [n]
-static hipError_t km_member_lists(const int *labels, int n, int k, int L, int *bcnt, int *cnt, int *start, int *run0, int *mem, hipStream_t stream)
-{
-    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK;
-    hipLaunchKernelGGL(km_hist_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, labels, n, k, bcnt);
-    hipError_t he = hipGetLastError();
-    RA_LAUNCH(he, km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt);
-    RA_LAUNCH(he, km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, run0);
-    RA_LAUNCH(he, km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, labels, n, k, (const int *)bcnt, (const int *)start, mem);
-    return he;
-}
-
 extern "C" int ra_kmeans_silhouette(const float *d_x, int n, int d, const int *d_labels, int k, double *d_out, int *d_nearest, void *hip_stream)
 {
     if (n < 3 || n > VAL_MAX_N || d < 1 || d > KM_MAX_D || k < 2 || k > KM_MAX_K)
         return arg_error("ra_kmeans_silhouette: need 3 <= n <= 262144, 1 <= d <= 2048 and 2 <= k <= 256");
     if (!d_x || !d_labels || !d_out || !d_nearest) return arg_error("ra_kmeans_silhouette: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, cap = n + k * VAL_TC;
+    const int cap = n + k * VAL_TC;
     KmScratch S;
-    const size_t o_bcnt = S.take((size_t)nb * k * 4), o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4);
-    const size_t o_run0 = S.take((size_t)(k + 1) * 4), o_mem = S.take((size_t)n * 4), o_pstart = S.take((size_t)(k + 1) * 4);
-    const size_t o_cols = S.take((size_t)cap * 4);
+    const KmLists M(S, n, k, KM_BLOCK);
+    const size_t o_pstart = S.take((size_t)(k + 1) * 4), o_cols = S.take((size_t)cap * 4);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_silhouette", scratch.status());
-    int *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start), *mem = S.at<int>(o_mem), *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols);
+    int *cnt = M.cnt(), *start = M.start(), *mem = M.mem(), *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols);
     hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);          // every column invalid (-1) until a member lands on it
-    if (he == hipSuccess) he = km_member_lists(d_labels, n, k, km_run_len(n), S.at<int>(o_bcnt), cnt, start, S.at<int>(o_run0), mem, stream);
+    if (he == hipSuccess) he = km_member_lists(d_labels, n, k, km_run_len(n), M, stream);
     RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, pstart);
     RA_LAUNCH(he, val_cols_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt,
               (const int *)pstart, n, k, cap, cols);
@@ -325,16 +313,16 @@ extern "C" int ra_kmeans_dispersion(const float *d_x, int n, int d, const int *d
         return arg_error("ra_kmeans_dispersion: need 1 <= n <= 4194304, 1 <= d <= 2048 and 1 <= k <= 256");
     if (!d_x || !d_labels || !d_centroids || !d_counts || !d_sq || !d_abs) return arg_error("ra_kmeans_dispersion: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, L = km_run_len(n), rmax = (n + L - 1) / L + k;
+    const int L = km_run_len(n), rmax = (n + L - 1) / L + k;
     KmScratch S;
-    const size_t o_bcnt = S.take((size_t)nb * k * 4), o_cnt = S.take((size_t)k * 4), o_start = S.take((size_t)k * 4);
-    const size_t o_run0 = S.take((size_t)(k + 1) * 4), o_mem = S.take((size_t)n * 4), o_part = S.take((size_t)rmax * d * 8);
-    const size_t o_sums = S.take((size_t)k * d * 8), o_wt = S.take((size_t)k * 8), o_dist = S.take((size_t)n * 8);
+    const KmLists M(S, n, k, KM_BLOCK);
+    const size_t o_part = S.take((size_t)rmax * d * 8), o_sums = S.take((size_t)k * d * 8), o_wt = S.take((size_t)k * 8);
+    const size_t o_dist = S.take((size_t)n * 8);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_dispersion", scratch.status());
-    int *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start), *run0 = S.at<int>(o_run0), *mem = S.at<int>(o_mem);
+    int *cnt = M.cnt(), *start = M.start(), *run0 = M.run0(), *mem = M.mem();
     double *part = S.at<double>(o_part), *sums = S.at<double>(o_sums), *dist = S.at<double>(o_dist);
-    hipError_t he = km_member_lists(d_labels, n, k, L, S.at<int>(o_bcnt), cnt, start, run0, mem, stream);
+    hipError_t he = km_member_lists(d_labels, n, k, L, M, stream);
     RA_LAUNCH(he, km_runsum_kernel, dim3(rmax), dim3(256), 0, stream, d_x, n, d, k, L, (const int *)mem, (const int *)cnt, (const int *)start,
               (const int *)run0, part);
     RA_LAUNCH(he, km_combine_kernel, dim3(k), dim3(256), 0, stream, (const double *)part, d, (const int *)cnt, (const int *)run0, sums,
@@ -375,20 +363,20 @@ extern "C" int ra_dbscan_step(const float *d_x, int n, int d, double eps, const 
     if (!d_x || !d_count || !d_label || !d_label_out || !d_changed || d_label_out == d_label)
         return arg_error("ra_dbscan_step: null argument, or d_label_out == d_label");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int nb = (n + KM_BLOCK - 1) / KM_BLOCK, nt = (n + 255) / 256, cap = n + 2 * DBS_TC;
+    const int nt = (n + 255) / 256, cap = n + 2 * DBS_TC;
     KmScratch S;
-    const size_t o_flag = S.take((size_t)n * 4), o_bcnt = S.take((size_t)nb * 2 * 4), o_cnt = S.take(2 * 4), o_start = S.take(2 * 4);
-    const size_t o_run0 = S.take(3 * 4), o_mem = S.take((size_t)n * 4), o_pstart = S.take(3 * 4), o_cols = S.take((size_t)cap * 4);
+    const KmLists M(S, n, 2, KM_BLOCK);
+    const size_t o_flag = S.take((size_t)n * 4), o_pstart = S.take(3 * 4), o_cols = S.take((size_t)cap * 4);
     const size_t o_m = S.take((size_t)n * 4), o_p = S.take((size_t)n * 4);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_dbscan_step", scratch.status());
-    int *flag = S.at<int>(o_flag), *cnt = S.at<int>(o_cnt), *start = S.at<int>(o_start), *mem = S.at<int>(o_mem);
+    int *flag = S.at<int>(o_flag), *cnt = M.cnt(), *start = M.start(), *mem = M.mem();
     int *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols), *m = S.at<int>(o_m), *P = S.at<int>(o_p);
     // the core points in index order: the member list of "cluster" 0 of the flags, padded to the column tile with -1
     hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);
     if (he == hipSuccess) he = hipMemsetAsync(d_changed, 0, sizeof(int), stream);
     RA_LAUNCH(he, dbs_flag_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, flag);
-    if (he == hipSuccess) he = km_member_lists(flag, n, 2, km_run_len(n), S.at<int>(o_bcnt), cnt, start, S.at<int>(o_run0), mem, stream);
+    if (he == hipSuccess) he = km_member_lists(flag, n, 2, km_run_len(n), M, stream);
     RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, 2, pstart);
     RA_LAUNCH(he, val_cols_kernel, dim3(nt), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt, (const int *)pstart,
               n, 2, cap, cols);

@@ -43,12 +43,13 @@ ra_tsne_knn, whose domain it has: n >= 2 and min_samples - 1 <= 301 (the numpy b
 (kdistances <= eps) ties the two kernels together.
 """
 import argparse
-import ctypes
 import math
-import numbers
 import sys
 
 import numpy as np
+
+from . import _common
+from ._common import Launcher, d2_rows, is_int, is_real, ptr, row_chunks
 
 MAX_N, MAX_D, MAX_KNN = 262144, 2048, 301
 MAX_AVERAGES = 256          # kmeans.class_averages' limit on the number of classes
@@ -72,69 +73,19 @@ class DbscanResult:
         return int(np.count_nonzero(self.labels < 0))
 
 
-def _is_int(v):
-    return isinstance(v, (numbers.Integral, np.integer)) and not isinstance(v, bool)
-
-
-def _is_real(v):
-    return isinstance(v, (numbers.Real, np.number)) and not isinstance(v, bool)
-
-
 def check_domain(n, d, eps, min_samples):
     """raise DbscanError unless the shape and parameters are inside the supported domain"""
     def need(ok, msg):
         if not ok:
             raise DbscanError(msg)
-    need(_is_int(min_samples), "min_samples must be an integer, got %r" % (min_samples,))
+    need(is_int(min_samples), "min_samples must be an integer, got %r" % (min_samples,))
     need(1 <= n <= MAX_N, "need 1 <= n <= %d points, got %d" % (MAX_N, n))
     need(1 <= d <= MAX_D, "need 1 <= d <= %d features, got %d" % (MAX_D, d))
-    need(_is_real(eps) and math.isfinite(eps) and eps > 0, "need a finite eps > 0, got %r" % (eps,))
+    need(is_real(eps) and eps > 0, "need a finite eps > 0, got %r" % (eps,))
     need(min_samples >= 1, "need min_samples >= 1, got %d" % min_samples)
 
 
-def _as_input(X, backend):
-    if backend == "device":
-        import torch
-        if isinstance(X, np.ndarray):
-            if X.ndim != 2:
-                raise DbscanError("X is [n][d], got shape %s" % (X.shape,))
-            X = torch.from_numpy(np.ascontiguousarray(X, np.float32)).to(torch.device("cuda", torch.cuda.current_device()))
-        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
-            raise DbscanError("backend 'device' takes a contiguous float32 CUDA tensor [n][d] (or a numpy array, copied)")
-        if X.ndim != 2:
-            raise DbscanError("X is [n][d], got shape %s" % (tuple(X.shape),))
-        return X
-    if backend != "numpy":
-        raise DbscanError("backend is 'device' or 'numpy', got %r" % (backend,))
-    if not isinstance(X, np.ndarray) and hasattr(X, "detach"):
-        X = X.detach().cpu().numpy()
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise DbscanError("X is [n][d], got shape %s" % (X.shape,))
-    return np.asarray(X, np.float32)
-
-
-def _check_finite(X, backend):
-    ok = bool(X.isfinite().all().item()) if backend == "device" else bool(np.all(np.isfinite(X)))
-    if not ok:
-        raise DbscanError("X holds NaN or infinite values")
-
-
 # ---- CPU checker (float64 numpy)
-
-def _row_chunks(n):
-    ch = max(1, (1 << 22) // n)
-    return [(s, min(n, s + ch)) for s in range(0, n, ch)]
-
-
-def _d2_rows(X, s0, s1):
-    """D2 [s1 - s0][n] of rule 2: differences in float64, the features in order, multiply and add unfused"""
-    D = np.zeros((s1 - s0, X.shape[0]))
-    for t in range(X.shape[1]):
-        df = X[s0:s1, t, None] - X[None, :, t]
-        D += df * df
-    return D
-
 
 def _components(n, ea, eb):
     """label [n] = the lowest index of the connected component under the edges (ea, eb): minimum, hook, compress, as the device"""
@@ -163,14 +114,14 @@ def _dbscan_numpy(X, eps, min_samples):
     X = np.asarray(X, np.float64)
     n = X.shape[0]
     eps2 = float(eps) * float(eps)
-    chunks = _row_chunks(n)
+    chunks = row_chunks(n)
     counts = np.empty(n, np.int64)
     for s0, s1 in chunks:
-        counts[s0:s1] = np.count_nonzero(_d2_rows(X, s0, s1) <= eps2, axis=1)
+        counts[s0:s1] = np.count_nonzero(d2_rows(X, s0, s1) <= eps2, axis=1)
     core = counts >= min_samples
     ea, eb = [], []                     # pairs (i, j) with j core: i < j for a core i, every j for a non-core i
     for s0, s1 in chunks:
-        N = _d2_rows(X, s0, s1) <= eps2
+        N = d2_rows(X, s0, s1) <= eps2
         N &= core[None, :]
         i, j = np.nonzero(N)
         i += s0
@@ -190,32 +141,24 @@ def _dbscan_numpy(X, eps, min_samples):
 
 # ---- device
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 def _dbscan_device(X, eps, min_samples, raw=False):
-    import torch
-    from . import api
-    lib = api.load_library()
+    L = Launcher(X)
+    torch, dev = L.torch, L.dev
     n, d = (int(s) for s in X.shape)
-    dev = X.device
     ms = int(min(min_samples, 2 ** 31 - 1))
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         counts = torch.empty(n, dtype=torch.int32, device=dev)
         label = torch.empty(n, dtype=torch.int32, device=dev)
         other = torch.empty(n, dtype=torch.int32, device=dev)
         changed = torch.empty(1, dtype=torch.int32, device=dev)
-        api._check(lib.ra_dbscan_count(_ptr(X), n, d, float(eps), ms, _ptr(counts), _ptr(label), stream), "ra_dbscan_count")
+        L.call("ra_dbscan_count", ptr(X), n, d, float(eps), ms, ptr(counts), ptr(label))
         core = counts >= ms
         cap = int(core.sum().item()) + 1
         rounds = 0
         while True:
             if rounds >= cap:
                 raise RuntimeError("dbscan: %d merging rounds for %d core points: every unfinished round lowers a label" % (rounds, cap - 1))
-            api._check(lib.ra_dbscan_step(_ptr(X), n, d, float(eps), _ptr(counts), ms, _ptr(label), _ptr(other), _ptr(changed), stream),
-                       "ra_dbscan_step")
+            L.call("ra_dbscan_step", ptr(X), n, d, float(eps), ptr(counts), ms, ptr(label), ptr(other), ptr(changed))
             rounds += 1
             label, other = other, label
             if int(changed.item()) == 0:
@@ -237,10 +180,10 @@ def dbscan(X, eps, min_samples=5, backend="device"):
     """DBSCAN of X [n][d] by the rules at the top of this module: DbscanResult(labels int32 [n] with -1 for noise, core_mask,
     core_sample_indices, n_clusters, counts, n_rounds).  Euclidean metric only; no sample_weight, no precomputed or sparse input,
     one GPU, at most 262144 points."""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, DbscanError, numpy_dtype=np.float32)
     n, d = (int(s) for s in X.shape)
     check_domain(n, d, eps, min_samples)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, DbscanError)
     if backend == "numpy":
         return _dbscan_numpy(X, eps, int(min_samples))
     return _dbscan_device(X, eps, int(min_samples))
@@ -250,10 +193,10 @@ def kdistances(X, min_samples, backend="device"):
     """float64 [n]: for each point the least eps at which it is a core point, i.e. the distance to its (min_samples - 1)-th nearest
     other point; 0 for min_samples = 1, inf for min_samples > n.  The device reads the last column of ra_tsne_knn and has its
     domain: n >= 2 and min_samples - 1 <= 301."""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, DbscanError, numpy_dtype=np.float32)
     n, d = (int(s) for s in X.shape)
     check_domain(n, d, 1.0, min_samples)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, DbscanError)
     k = int(min_samples) - 1
     if k == 0:
         return np.zeros(n)
@@ -262,19 +205,17 @@ def kdistances(X, min_samples, backend="device"):
     if backend == "numpy":
         Xd = np.asarray(X, np.float64)
         out = np.empty(n)
-        for s0, s1 in _row_chunks(n):
-            out[s0:s1] = np.partition(_d2_rows(Xd, s0, s1), k, axis=1)[:, k]        # the point itself is the 0-th
+        for s0, s1 in row_chunks(n):
+            out[s0:s1] = np.partition(d2_rows(Xd, s0, s1), k, axis=1)[:, k]        # the point itself is the 0-th
         return np.sqrt(out)
     if k > MAX_KNN:
         raise DbscanError("the device takes min_samples - 1 <= %d, got min_samples = %d" % (MAX_KNN, min_samples))
-    import torch
-    from . import api
-    lib = api.load_library()
+    L = Launcher(X)
+    torch = L.torch
     with torch.cuda.device(X.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
         idx = torch.empty((n, k), dtype=torch.int32, device=X.device)
         d2 = torch.empty((n, k), dtype=torch.float64, device=X.device)
-        api._check(lib.ra_tsne_knn(_ptr(X), n, d, k, _ptr(idx), _ptr(d2), stream), "ra_tsne_knn")
+        L.call("ra_tsne_knn", ptr(X), n, d, k, ptr(idx), ptr(d2))
         return torch.sqrt(d2[:, k - 1]).cpu().numpy()
 
 
@@ -283,26 +224,18 @@ def kdistances(X, min_samples, backend="device"):
 def main(argv=None):
     from . import kmeans
     ap = argparse.ArgumentParser(prog="python -m cryo_ralib_amd.dbscan")
-    ap.add_argument("input", help="OUT.npz of the tsne or sdr tool, or an [n][d] .npy")
-    ap.add_argument("output", help="OUT.npz")
+    _common.add_cluster_arguments(ap, ("input", "output"), "embedding", True)
     ap.add_argument("--eps", type=float, default=None, help="neighbourhood radius (optional with --kdist)")
     ap.add_argument("--min_samples", type=int, default=5, help="neighbours, itself included, that make a core point")
-    ap.add_argument("--key", default="embedding", help="array of an .npz input (default embedding; factors for the sdr tool)")
-    ap.add_argument("--backend", default="device", choices=("device", "numpy"))
+    _common.add_cluster_arguments(ap, ("--key", "--backend"), "embedding", True)
     ap.add_argument("--kdist", action="store_true", help="store the sorted k-distances as kdist and print their quantiles")
-    ap.add_argument("--truth", default=None, help="int .npy or params.txt: purity, c_purity and contingency over the non-noise points")
-    ap.add_argument("--stack", default=None, help="stack for --averages (.hdf, .mrcs or .npy)")
-    ap.add_argument("--params", default=None, help="params.txt or initial2Dparams.txt of the stack")
-    ap.add_argument("--ou", type=int, default=None, help="outer radius of the averages' mask")
-    ap.add_argument("--averages", default=None, help="REFS.{hdf,mrcs,npy}: the class averages of the non-noise particles")
-    ap.add_argument("--device", type=int, default=0)
+    _common.add_cluster_arguments(ap, ("--truth", "--stack", "--params", "--ou", "--averages", "--device"), "embedding", True)
     args = ap.parse_args(argv)
     if args.eps is None and not args.kdist:
         ap.error("one of --eps and --kdist is needed")
     if args.eps is not None and not (math.isfinite(args.eps) and args.eps > 0):
         ap.error("--eps must be a finite number > 0")
-    if args.averages and not (args.stack and args.params and args.ou):
-        ap.error("--averages needs --stack, --params and --ou")
+    _common.check_averages_arguments(ap, args)
     if args.averages and args.eps is None:
         ap.error("--averages needs --eps")
     try:
@@ -313,13 +246,8 @@ def main(argv=None):
     except (ValueError, OSError) as e:
         raise SystemExit("error: %s" % e)
     if args.backend == "device" or args.averages:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU visible: use --backend numpy for the CPU checker (--averages needs the GPU)")
-    Xb = X
-    if args.backend == "device":
-        import torch
-        Xb = torch.from_numpy(X).to(torch.device("cuda", args.device))
+        _common.require_gpu(_common.NO_GPU)
+    Xb = _common.to_device(X, args.device) if args.backend == "device" else X
     out = dict(min_samples=np.int64(args.min_samples), key=np.str_(args.key), backend=np.str_(args.backend),
                eps=np.float64(np.nan if args.eps is None else args.eps))
     try:
@@ -344,27 +272,9 @@ def main(argv=None):
                                                                                res.n_rounds)
         keep = res.labels >= 0
         if truth is not None:
-            if keep.any():
-                out["purity"] = np.float64(kmeans.purity_score(truth[keep], res.labels[keep]))
-                out["c_purity"] = np.float64(kmeans.c_purity_score(truth[keep], res.labels[keep]))
-                out["contingency"] = kmeans.contingency_matrix(truth[keep], res.labels[keep])
-            else:
-                out["purity"], out["c_purity"], out["contingency"] = np.float64(np.nan), np.float64(np.nan), np.zeros((0, 0), np.int64)
-            msg += ", purity %.4f, c_purity %.4f" % (out["purity"], out["c_purity"])
+            msg += _common.truth_scores(out, truth, res.labels, keep)
         if args.averages:
-            from . import sdr, stackio
-            try:
-                if not 1 <= res.n_clusters <= MAX_AVERAGES:
-                    raise DbscanError("--averages takes 1 to %d clusters, got %d" % (MAX_AVERAGES, res.n_clusters))
-                stack = np.ascontiguousarray(stackio.read_stack(args.stack), np.float32)
-                if stack.ndim != 3 or stack.shape[0] != n:
-                    raise DbscanError("%s: need a stack of %d images, got shape %s" % (args.stack, n, stack.shape))
-                prm = sdr.read_params(args.params, n)
-                refs = kmeans.class_averages(stack[keep], prm[keep], res.labels[keep], res.n_clusters, args.ou, device=args.device)
-            except (ValueError, OSError) as e:
-                raise SystemExit("error: %s" % e)
-            stackio.write_stack(args.averages, refs)
-            msg += ", averages -> %s" % args.averages
+            msg += _common.write_averages(args, n, res.labels, res.n_clusters, keep, DbscanError, MAX_AVERAGES)
     np.savez(args.output, **out)
     print(msg)
     return 0

@@ -41,15 +41,14 @@ Domain: 1 <= k <= 256, k <= n <= 4194304, n k <= 2^28, 1 <= d <= 256 (full) or 2
 reg_covar >= 0, finite input.  Anything else raises GmmError before anything is launched.
 """
 import argparse
-import ctypes
-import math
-import numbers
 import sys
 import warnings
 
 import numpy as np
 
+from . import _common
 from . import kmeans as _km
+from ._common import Launcher, is_int, is_real, ptr
 from .kmeans import ConvergenceWarning, check_random_state
 
 MAX_N, MAX_K, MAX_D_FULL, MAX_D_DIAG, MAX_NK = 4194304, 256, 256, 2048, 1 << 28
@@ -77,14 +76,6 @@ class GmmResult:
         self.lower_bounds, self.labels, self.init_labels, self.log_prob, self.proba_max = lower_bounds, labels, init_labels, log_prob, proba_max
 
 
-def _is_int(v):
-    return isinstance(v, (numbers.Integral, np.integer)) and not isinstance(v, bool)
-
-
-def _is_real(v):
-    return isinstance(v, (numbers.Real, np.number)) and not isinstance(v, bool) and math.isfinite(v)
-
-
 def check_domain(n, d, n_components, covariance_type="full", max_iter=100, tol=1e-3, reg_covar=1e-6, n_init=1):
     """raise GmmError unless the shape and parameters are inside the supported domain"""
     def need(ok, msg):
@@ -92,7 +83,7 @@ def check_domain(n, d, n_components, covariance_type="full", max_iter=100, tol=1
             raise GmmError(msg)
     need(covariance_type in COV_TYPES, "covariance_type is 'full' or 'diag', got %r" % (covariance_type,))
     for name, v in (("n", n), ("d", d), ("n_components", n_components), ("max_iter", max_iter), ("n_init", n_init)):
-        need(_is_int(v), "%s must be an integer, got %r" % (name, v))
+        need(is_int(v), "%s must be an integer, got %r" % (name, v))
     need(1 <= n_components <= MAX_K, "need 1 <= n_components <= %d, got %d" % (MAX_K, n_components))
     need(n_components <= n <= MAX_N, "need n_components = %d <= n <= %d points, got %d" % (n_components, MAX_N, n))
     need(n * n_components <= MAX_NK, "need n * n_components <= 2^28, got %d x %d" % (n, n_components))
@@ -100,8 +91,8 @@ def check_domain(n, d, n_components, covariance_type="full", max_iter=100, tol=1
     need(1 <= d <= dmax, "need 1 <= d <= %d features (%s), got %d" % (dmax, covariance_type, d))
     need(max_iter >= 1, "need max_iter >= 1, got %d" % max_iter)
     need(n_init >= 1, "need n_init >= 1, got %d" % n_init)
-    need(_is_real(tol) and tol >= 0, "need a finite tol >= 0, got %r" % (tol,))
-    need(_is_real(reg_covar) and reg_covar >= 0, "need a finite reg_covar >= 0, got %r" % (reg_covar,))
+    need(is_real(tol) and tol >= 0, "need a finite tol >= 0, got %r" % (tol,))
+    need(is_real(reg_covar) and reg_covar >= 0, "need a finite reg_covar >= 0, got %r" % (reg_covar,))
 
 
 def n_parameters(model):
@@ -226,18 +217,13 @@ class _Numpy:
 
 # ---- device
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class _Device:
     """thin launcher of ra_gmm_estep / ra_gmm_mstep on the current stream of X's device"""
 
     def __init__(self, X, k, covariance_type):
-        import torch
-        from . import api
-        self.torch, self.api, self.lib, self.dev = torch, api, api.load_library(), X.device
-        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        L = Launcher(X)
+        torch = L.torch
+        self.torch, self.api, self.lib, self.dev, self.stream, self.call = torch, L.api, L.lib, L.dev, L.stream, L.call
         self.X = X
         self.n, self.d = (int(s) for s in X.shape)
         self.k, self.ct, self.ctype = k, covariance_type, COV_TYPES[covariance_type]
@@ -258,14 +244,13 @@ class _Device:
 
     def estep(self, p):
         means, pc, off = self._up(p.means), self._up(p.pc), self._up(p.offset)
-        self.api._check(self.lib.ra_gmm_estep(_ptr(self.X), self.n, self.d, self.k, self.ctype, _ptr(means), _ptr(pc), _ptr(off),
-                                              _ptr(self.log_resp), _ptr(self.log_prob), _ptr(self.labels), _ptr(self.sum), self.stream),
-                        "ra_gmm_estep")
+        self.call("ra_gmm_estep", ptr(self.X), self.n, self.d, self.k, self.ctype, ptr(means), ptr(pc), ptr(off), ptr(self.log_resp),
+                  ptr(self.log_prob), ptr(self.labels), ptr(self.sum))
         return float(self.sum.item()) / self.n
 
     def mstep(self, resp, log_domain, reg):
-        self.api._check(self.lib.ra_gmm_mstep(_ptr(self.X), self.n, self.d, self.k, self.ctype, _ptr(resp), int(bool(log_domain)), float(reg),
-                                              _ptr(self.nk), _ptr(self.means), _ptr(self.cov), self.stream), "ra_gmm_mstep")
+        self.call("ra_gmm_mstep", ptr(self.X), self.n, self.d, self.k, self.ctype, ptr(resp), int(bool(log_domain)), float(reg),
+                  ptr(self.nk), ptr(self.means), ptr(self.cov))
         return self.nk.cpu().numpy(), self.means.cpu().numpy(), self.cov.cpu().numpy()
 
     def mstep_log(self, reg):
@@ -332,20 +317,6 @@ def _fit(B, k, covariance_type, tol, reg_covar, max_iter, n_init, init, random_s
                      B.labels_numpy(), init_labels, B.log_prob_numpy(), np.exp(B.log_resp_max()))
 
 
-def _as_input(X, backend):
-    try:
-        return _km._as_input(X, backend)
-    except _km.KMeansError as e:
-        raise GmmError(str(e))
-
-
-def _check_finite(X, backend):
-    try:
-        _km._check_finite(X, backend)
-    except _km.KMeansError as e:
-        raise GmmError(str(e))
-
-
 def _resolve_init(init, n, k):
     if isinstance(init, str):
         if init not in ("kmeans", "random"):
@@ -366,15 +337,12 @@ def _backend(X, k, covariance_type, backend):
 def gmm(X, n_components, covariance_type="full", tol=1e-3, reg_covar=1e-6, max_iter=100, n_init=1, init_params="kmeans",
         random_state=None, backend="device"):
     """Gaussian mixture of X [n][d] (a contiguous float32 CUDA tensor; a numpy array is copied to the device): GmmResult"""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, GmmError)
     n, d = (int(s) for s in X.shape)
     check_domain(n, d, n_components, covariance_type, max_iter, tol, reg_covar, n_init)
     init = _resolve_init(init_params, n, n_components)
-    try:
-        check_random_state(random_state)
-    except _km.KMeansError as e:
-        raise GmmError(str(e))
-    _check_finite(X, backend)
+    _common.check_random_state(random_state, GmmError)
+    _common.check_finite(X, backend, GmmError)
     if backend == "numpy":
         return _fit(_Numpy(X, n_components, covariance_type), n_components, covariance_type, tol, reg_covar, max_iter, n_init, init, random_state)
     import torch
@@ -393,13 +361,13 @@ class _Model:
 
 
 def _evaluate(X, model, backend):
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, GmmError)
     n, d = (int(s) for s in X.shape)
     k = int(model.means.shape[0])
     if model.means.shape != (k, d):
         raise GmmError("the model has %d features, X has %d" % (model.means.shape[1], d))
     check_domain(n, d, k, model.covariance_type)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, GmmError)
     if backend == "numpy":
         B = _Numpy(X, k, model.covariance_type)
         B.estep(_Model(model))
@@ -482,7 +450,7 @@ def sweep(X, ks, backend="device", **gmm_kwargs):
     ks = [int(v) for v in ks]
     if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 1:
         raise GmmError("a sweep needs increasing k >= 1, got %r" % (ks,))
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, GmmError)
     n, d = (int(s) for s in X.shape)
     for k in ks:
         check_domain(n, d, k, gmm_kwargs.get("covariance_type", "full"))
@@ -493,27 +461,22 @@ def sweep(X, ks, backend="device", **gmm_kwargs):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cryo_ralib_amd.gmm")
-    ap.add_argument("input", help="OUT.npz of the sdr or tsne tool, or an [n][d] .npy")
-    ap.add_argument("output", help="OUT.npz")
+    _common.add_cluster_arguments(ap, ("input", "output"), "factors", False)
     ap.add_argument("--k", type=int, default=None, help="number of components (optional with --sweep)")
     ap.add_argument("--cov", default="full", choices=("full", "diag"), help="covariance_type")
-    ap.add_argument("--key", default="factors", help="array of an .npz input (default factors; embedding for the tsne tool)")
+    _common.add_cluster_arguments(ap, ("--key",), "factors", False)
     ap.add_argument("--init", default="kmeans", help="kmeans, random or an int [n] .npy of labels")
     ap.add_argument("--n_init", type=int, default=1)
     ap.add_argument("--max_iter", type=int, default=100)
     ap.add_argument("--tol", type=float, default=1e-3)
     ap.add_argument("--reg_covar", type=float, default=1e-6)
     ap.add_argument("--seed", type=int, default=None, help="random_state")
-    ap.add_argument("--backend", default="device", choices=("device", "numpy"))
+    _common.add_cluster_arguments(ap, ("--backend",), "factors", False)
     ap.add_argument("--sweep", default=None, help="K1,K2,... or LO:HI[:STEP]: a mixture with BIC and AIC for every k; the result "
                     "written is that of --k if given, else of the least BIC")
-    ap.add_argument("--truth", default=None, help="int .npy or params.txt: purity, c_purity and contingency in OUT.npz")
+    _common.add_cluster_arguments(ap, ("--truth",), "factors", False)
     ap.add_argument("--min_proba", type=float, default=None, help="P in (0, 1]: the mask keep = proba_max >= P in OUT.npz")
-    ap.add_argument("--stack", default=None, help="stack for --averages (.hdf, .mrcs or .npy)")
-    ap.add_argument("--params", default=None, help="params.txt or initial2Dparams.txt of the stack")
-    ap.add_argument("--ou", type=int, default=None, help="outer radius of the averages' mask")
-    ap.add_argument("--averages", default=None, help="REFS.{hdf,mrcs,npy}: the k class averages")
-    ap.add_argument("--device", type=int, default=0)
+    _common.add_cluster_arguments(ap, ("--stack", "--params", "--ou", "--averages", "--device"), "factors", False)
     args = ap.parse_args(argv)
     ks = None
     if args.k is None and args.sweep is None:
@@ -533,22 +496,16 @@ def main(argv=None):
             check_domain(n, d, kk, args.cov, args.max_iter, args.tol, args.reg_covar, args.n_init)
             _resolve_init(init, n, kk)
         truth = _km.read_truth(args.truth, n) if args.truth else None
-        if args.averages and not (args.stack and args.params and args.ou):
-            raise GmmError("--averages needs --stack, --params and --ou")
     except (GmmError, _km.KMeansError, OSError, ValueError) as e:
         raise SystemExit("error: %s" % e)
+    _common.check_averages_arguments(ap, args, usage=False)
     if args.backend == "device" or args.averages:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU visible: use --backend numpy for the CPU checker (--averages needs the GPU)")
+        _common.require_gpu(_common.NO_GPU)
     kw = dict(covariance_type=args.cov, tol=args.tol, reg_covar=args.reg_covar, max_iter=args.max_iter, n_init=args.n_init,
               init_params=init, random_state=args.seed)
     swept = None
     try:
-        Xb = X
-        if args.backend == "device":
-            import torch
-            Xb = torch.from_numpy(X).to(torch.device("cuda", args.device))
+        Xb = _common.to_device(X, args.device) if args.backend == "device" else X
         if ks:
             swept = sweep(Xb, ks, backend=args.backend, **kw)
             if args.k is None:
@@ -566,9 +523,7 @@ def main(argv=None):
     msg = "%s: %d points x %d, k = %d (%s), %d iterations%s, lower bound %.6g, BIC %.6g, AIC %.6g" % (
         args.output, n, d, args.k, args.cov, res.n_iter, "" if res.converged else " (not converged)", res.lower_bound, row.bic, row.aic)
     if truth is not None:
-        out["purity"], out["c_purity"] = np.float64(_km.purity_score(truth, res.labels)), np.float64(_km.c_purity_score(truth, res.labels))
-        out["contingency"] = _km.contingency_matrix(truth, res.labels)
-        msg += ", purity %.4f, c_purity %.4f" % (out["purity"], out["c_purity"])
+        msg += _common.truth_scores(out, truth, res.labels)
     if args.min_proba is not None:
         keep = res.proba_max >= args.min_proba
         out["keep"], out["min_proba"] = keep, np.float64(args.min_proba)
@@ -576,17 +531,7 @@ def main(argv=None):
             sel = res.labels == c
             print("class %3d: %7d members, %7d kept" % (c, int(sel.sum()), int((sel & keep).sum())))
     if args.averages:
-        from . import sdr, stackio
-        try:
-            stack = np.ascontiguousarray(stackio.read_stack(args.stack), np.float32)
-            if stack.ndim != 3 or stack.shape[0] != n:
-                raise GmmError("%s: need a stack of %d images, got shape %s" % (args.stack, n, stack.shape))
-            prm = sdr.read_params(args.params, n)
-            refs = _km.class_averages(stack, prm, res.labels, args.k, args.ou, device=args.device)
-        except (ValueError, sdr.SdrError, OSError) as e:
-            raise SystemExit("error: %s" % e)
-        stackio.write_stack(args.averages, refs)
-        msg += ", averages -> %s" % args.averages
+        msg += _common.write_averages(args, n, res.labels, args.k, None, GmmError)
     if swept is not None:
         out["sweep"], out["best_k"] = swept.table(), np.int64(swept.best_k)
         print("%5s %14s %7s %10s %14s %14s" % ("k", "lower bound", "n_iter", "converged", "BIC", "AIC"))

@@ -67,14 +67,14 @@ per step; it needs no GPU.  Rules 6 - 9 are one numpy implementation for both ba
 one union-find pass over the sorted edges, everything after it by pointer jumping over arrays, O(n log n).
 """
 import argparse
-import ctypes
 import math
 import sys
 import time
 
 import numpy as np
 
-from .dbscan import _d2_rows, _is_int, _ptr, _row_chunks
+from . import _common
+from ._common import Launcher, d2_rows, is_int, ptr, row_chunks
 
 MAX_N, MAX_D, MAX_MIN_SAMPLES = 262144, 2048, 302
 MAX_AVERAGES = 256          # kmeans.class_averages' limit on the number of classes
@@ -107,8 +107,8 @@ def check_domain(n, d, min_cluster_size=5, min_samples=None, method="eom", devic
     def need(ok, msg):
         if not ok:
             raise HdbscanError(msg)
-    need(_is_int(min_cluster_size), "min_cluster_size must be an integer, got %r" % (min_cluster_size,))
-    need(min_samples is None or _is_int(min_samples), "min_samples must be an integer or None, got %r" % (min_samples,))
+    need(is_int(min_cluster_size), "min_cluster_size must be an integer, got %r" % (min_cluster_size,))
+    need(min_samples is None or is_int(min_samples), "min_samples must be an integer or None, got %r" % (min_samples,))
     need(method in METHODS, "cluster_selection_method is 'eom' or 'leaf', got %r" % (method,))
     need(2 <= n <= MAX_N, "need 2 <= n <= %d points, got %d" % (MAX_N, n))
     need(1 <= d <= MAX_D, "need 1 <= d <= %d features, got %d" % (MAX_D, d))
@@ -116,34 +116,6 @@ def check_domain(n, d, min_cluster_size=5, min_samples=None, method="eom", devic
     ms = int(min_cluster_size if min_samples is None else min_samples)
     need(1 <= ms <= min(n, MAX_MIN_SAMPLES), "need 1 <= min_samples <= min(n, %d) = %d, got %d" % (MAX_MIN_SAMPLES, min(n, MAX_MIN_SAMPLES), ms))
     return ms
-
-
-def _as_input(X, backend):
-    if backend == "device":
-        import torch
-        if isinstance(X, np.ndarray):
-            if X.ndim != 2:
-                raise HdbscanError("X is [n][d], got shape %s" % (X.shape,))
-            X = torch.from_numpy(np.ascontiguousarray(X, np.float32)).to(torch.device("cuda", torch.cuda.current_device()))
-        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
-            raise HdbscanError("backend 'device' takes a contiguous float32 CUDA tensor [n][d] (or a numpy array, copied)")
-        if X.ndim != 2:
-            raise HdbscanError("X is [n][d], got shape %s" % (tuple(X.shape),))
-        return X
-    if backend != "numpy":
-        raise HdbscanError("backend is 'device' or 'numpy', got %r" % (backend,))
-    if not isinstance(X, np.ndarray) and hasattr(X, "detach"):
-        X = X.detach().cpu().numpy()
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise HdbscanError("X is [n][d], got shape %s" % (X.shape,))
-    return np.asarray(X, np.float32)
-
-
-def _check_finite(X, backend):
-    ok = bool(X.isfinite().all().item()) if backend == "device" else bool(np.all(np.isfinite(X)))
-    if not ok:
-        raise HdbscanError("X holds NaN or infinite values")
 
 
 def _sort_edges(lo, hi, w2):
@@ -160,8 +132,8 @@ def core2_numpy(X, min_samples):
     if k == 0:
         return np.zeros(n)
     out = np.empty(n)
-    for s0, s1 in _row_chunks(n):
-        out[s0:s1] = np.partition(_d2_rows(X, s0, s1), k, axis=1)[:, k]             # the point itself is the 0-th
+    for s0, s1 in row_chunks(n):
+        out[s0:s1] = np.partition(d2_rows(X, s0, s1), k, axis=1)[:, k]             # the point itself is the 0-th
     return out
 
 
@@ -177,7 +149,7 @@ def mst_numpy(X, core2):
     u = 0
     for e in range(n - 1):
         intree[u] = True
-        w = np.maximum(np.maximum(_d2_rows(X, u, u + 1)[0], core2[u]), core2)
+        w = np.maximum(np.maximum(d2_rows(X, u, u + 1)[0], core2[u]), core2)
         elo, ehi = np.minimum(idx, u), np.maximum(idx, u)
         less = (w < bw) | ((w == bw) & ((elo < blo) | ((elo == blo) & (ehi < bhi))))
         less &= ~intree
@@ -235,28 +207,24 @@ def boruvka_merge(comp, w2, lo, hi):
 
 
 def _mst_device(X, min_samples):
-    import torch
-    from . import api
-    lib = api.load_library()
+    L = Launcher(X)
+    torch, dev = L.torch, L.dev
     n, d = (int(s) for s in X.shape)
-    dev = X.device
     cap = max(1, math.ceil(math.log2(n))) + 1
     with torch.cuda.device(dev):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         core2 = torch.empty(n, dtype=torch.float64, device=dev)
         comp_d = torch.arange(n, dtype=torch.int32, device=dev)
         out_w = torch.empty(n, dtype=torch.float64, device=dev)
         out_lo = torch.empty(n, dtype=torch.int32, device=dev)
         out_hi = torch.empty(n, dtype=torch.int32, device=dev)
-        api._check(lib.ra_hdbscan_core(_ptr(X), n, d, int(min_samples), _ptr(core2), stream), "ra_hdbscan_core")
+        L.call("ra_hdbscan_core", ptr(X), n, d, int(min_samples), ptr(core2))
         comp = np.arange(n, dtype=np.int64)
         lo, hi, w2, rounds, left = [], [], [], 0, n
         while left > 1:
             if rounds >= cap:
                 raise RuntimeError("hdbscan: %d components left after %d rounds for %d points: every round at least halves them" % (
                     left, rounds, n))
-            api._check(lib.ra_hdbscan_round(_ptr(X), n, d, _ptr(core2), _ptr(comp_d), _ptr(out_w), _ptr(out_lo), _ptr(out_hi), stream),
-                       "ra_hdbscan_round")
+            L.call("ra_hdbscan_round", ptr(X), n, d, ptr(core2), ptr(comp_d), ptr(out_w), ptr(out_lo), ptr(out_hi))
             rounds += 1
             comp, elo, ehi, ew = boruvka_merge(comp, out_w.cpu().numpy(), out_lo.cpu().numpy(), out_hi.cpu().numpy())
             lo.append(elo)
@@ -417,10 +385,10 @@ def hdbscan(X, min_cluster_size=5, min_samples=None, cluster_selection_method="e
     tie_mask, n_clusters, core_distances, mst, condensed, stabilities, n_rounds).  Euclidean metric, allow_single_cluster=False,
     no cluster_selection_epsilon, max_cluster_size, alpha, store_centers or outlier scores, no precomputed or sparse input, one
     GPU, at most 262144 points."""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, HdbscanError, numpy_dtype=np.float32)
     n, d = (int(s) for s in X.shape)
     ms = check_domain(n, d, min_cluster_size, min_samples, cluster_selection_method)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, HdbscanError)
     if backend == "numpy":
         core2 = core2_numpy(X, ms)
         (lo, hi, w2), rounds = mst_numpy(X, core2), 0
@@ -437,25 +405,17 @@ def hdbscan(X, min_cluster_size=5, min_samples=None, cluster_selection_method="e
 def main(argv=None):
     from . import kmeans
     ap = argparse.ArgumentParser(prog="python -m cryo_ralib_amd.hdbscan")
-    ap.add_argument("input", help="OUT.npz of the tsne or sdr tool, or an [n][d] .npy")
-    ap.add_argument("output", help="OUT.npz")
+    _common.add_cluster_arguments(ap, ("input", "output"), "embedding", True)
     ap.add_argument("--min_cluster_size", type=int, default=5, help="the least number of points of a cluster")
     ap.add_argument("--min_samples", type=int, default=None, help="neighbours, itself included, of the core distance (default min_cluster_size)")
     ap.add_argument("--method", default="eom", choices=METHODS, help="cluster selection: excess of mass, or the leaves")
-    ap.add_argument("--key", default="embedding", help="array of an .npz input (default embedding; factors for the sdr tool)")
-    ap.add_argument("--backend", default="device", choices=("device", "numpy"))
-    ap.add_argument("--truth", default=None, help="int .npy or params.txt: purity, c_purity and contingency over the non-noise points")
+    _common.add_cluster_arguments(ap, ("--key", "--backend", "--truth"), "embedding", True)
     ap.add_argument("--min_proba", type=float, default=None, help="P in (0, 1]: store keep = probabilities >= P")
-    ap.add_argument("--stack", default=None, help="stack for --averages (.hdf, .mrcs or .npy)")
-    ap.add_argument("--params", default=None, help="params.txt or initial2Dparams.txt of the stack")
-    ap.add_argument("--ou", type=int, default=None, help="outer radius of the averages' mask")
-    ap.add_argument("--averages", default=None, help="REFS.{hdf,mrcs,npy}: the class averages of the non-noise particles")
-    ap.add_argument("--device", type=int, default=0)
+    _common.add_cluster_arguments(ap, ("--stack", "--params", "--ou", "--averages", "--device"), "embedding", True)
     args = ap.parse_args(argv)
     if args.min_proba is not None and not (0.0 < args.min_proba <= 1.0):
         ap.error("--min_proba must lie in (0, 1]")
-    if args.averages and not (args.stack and args.params and args.ou):
-        ap.error("--averages needs --stack, --params and --ou")
+    _common.check_averages_arguments(ap, args)
     if args.min_cluster_size < 2:
         ap.error("--min_cluster_size must be at least 2")
     if args.min_samples is not None and not 1 <= args.min_samples <= MAX_MIN_SAMPLES:
@@ -473,13 +433,8 @@ def main(argv=None):
     except (ValueError, OSError) as e:
         raise SystemExit("error: %s" % e)
     if args.backend == "device" or args.averages:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU visible: use --backend numpy for the CPU checker (--averages needs the GPU)")
-    Xb = X
-    if args.backend == "device":
-        import torch
-        Xb = torch.from_numpy(X).to(torch.device("cuda", args.device))
+        _common.require_gpu(_common.NO_GPU)
+    Xb = _common.to_device(X, args.device) if args.backend == "device" else X
     try:
         res = hdbscan(Xb, args.min_cluster_size, args.min_samples, args.method, backend=args.backend)
     except ValueError as e:
@@ -504,27 +459,9 @@ def main(argv=None):
         out["keep"] = res.probabilities >= args.min_proba
         msg += ", %d kept at probability >= %g" % (int(out["keep"].sum()), args.min_proba)
     if truth is not None:
-        if keep.any():
-            out["purity"] = np.float64(kmeans.purity_score(truth[keep], res.labels[keep]))
-            out["c_purity"] = np.float64(kmeans.c_purity_score(truth[keep], res.labels[keep]))
-            out["contingency"] = kmeans.contingency_matrix(truth[keep], res.labels[keep])
-        else:
-            out["purity"], out["c_purity"], out["contingency"] = np.float64(np.nan), np.float64(np.nan), np.zeros((0, 0), np.int64)
-        msg += ", purity %.4f, c_purity %.4f" % (out["purity"], out["c_purity"])
+        msg += _common.truth_scores(out, truth, res.labels, keep)
     if args.averages:
-        from . import sdr, stackio
-        try:
-            if not 1 <= res.n_clusters <= MAX_AVERAGES:
-                raise HdbscanError("--averages takes 1 to %d clusters, got %d" % (MAX_AVERAGES, res.n_clusters))
-            stack = np.ascontiguousarray(stackio.read_stack(args.stack), np.float32)
-            if stack.ndim != 3 or stack.shape[0] != n:
-                raise HdbscanError("%s: need a stack of %d images, got shape %s" % (args.stack, n, stack.shape))
-            prm = sdr.read_params(args.params, n)
-            refs = kmeans.class_averages(stack[keep], prm[keep], res.labels[keep], res.n_clusters, args.ou, device=args.device)
-        except (ValueError, OSError) as e:
-            raise SystemExit("error: %s" % e)
-        stackio.write_stack(args.averages, refs)
-        msg += ", averages -> %s" % args.averages
+        msg += _common.write_averages(args, n, res.labels, res.n_clusters, keep, HdbscanError, MAX_AVERAGES)
     np.savez(args.output, **out)
     print(msg)
     return 0

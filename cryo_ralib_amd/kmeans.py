@@ -45,13 +45,15 @@ Domain: 1 <= k <= min(256, n), 1 <= n <= 4194304, 1 <= d <= 2048, max_iter >= 1,
 KMeansError before anything is launched.
 """
 import argparse
-import ctypes
 import math
 import numbers
 import sys
 import warnings
 
 import numpy as np
+
+from . import _common
+from ._common import Launcher, is_int, ptr
 
 MAX_N, MAX_D, MAX_K = 4194304, 2048, 256
 
@@ -72,35 +74,25 @@ class KMeansResult:
         self.labels, self.centers, self.inertia, self.n_iter, self.init_indices = labels, centers, inertia, n_iter, init_indices
 
 
-def _is_int(v):
-    return isinstance(v, (numbers.Integral, np.integer)) and not isinstance(v, bool)
-
-
 def check_domain(n, d, n_clusters, max_iter=300, tol=1e-4, n_init="auto"):
     """raise KMeansError unless the shape and parameters are inside the supported domain"""
     def need(ok, msg):
         if not ok:
             raise KMeansError(msg)
     for name, v in (("n", n), ("d", d), ("n_clusters", n_clusters), ("max_iter", max_iter)):
-        need(_is_int(v), "%s must be an integer, got %r" % (name, v))
+        need(is_int(v), "%s must be an integer, got %r" % (name, v))
     need(1 <= n <= MAX_N, "need 1 <= n <= %d points, got %d" % (MAX_N, n))
     need(1 <= d <= MAX_D, "need 1 <= d <= %d features, got %d" % (MAX_D, d))
     need(1 <= n_clusters <= min(MAX_K, n), "need 1 <= n_clusters <= min(%d, n = %d), got %d" % (MAX_K, n, n_clusters))
     need(max_iter >= 1, "need max_iter >= 1, got %d" % max_iter)
     need(isinstance(tol, (numbers.Real, np.number)) and not isinstance(tol, bool) and math.isfinite(tol) and tol >= 0,
          "need a finite tol >= 0, got %r" % (tol,))
-    need(n_init == "auto" or (_is_int(n_init) and n_init >= 1), "n_init is 'auto' or an integer >= 1, got %r" % (n_init,))
+    need(n_init == "auto" or (is_int(n_init) and n_init >= 1), "n_init is 'auto' or an integer >= 1, got %r" % (n_init,))
 
 
 def check_random_state(seed):
     """sklearn.utils.check_random_state"""
-    if seed is None or seed is np.random:
-        return np.random.mtrand._rand
-    if _is_int(seed):
-        return np.random.RandomState(seed)
-    if isinstance(seed, np.random.RandomState):
-        return seed
-    raise KMeansError("random_state is None, an integer or a numpy RandomState, got %r" % (seed,))
+    return _common.check_random_state(seed, KMeansError)
 
 
 def n_local_trials(k):
@@ -214,22 +206,17 @@ class _Numpy:
 
 # ---- device
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class _Device:
     """thin launcher of the ra_kmeans_* entries on the current stream of X's device"""
 
     def __init__(self, X):
-        import torch
-        from . import api
-        self.torch, self.api, self.lib, self.dev = torch, api, api.load_library(), X.device
-        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        L = Launcher(X)
+        torch = L.torch
+        self.torch, self.api, self.lib, self.dev, self.stream, self.call = torch, L.api, L.lib, L.dev, L.stream, L.call
         self.X = X
         self.n, self.d = (int(s) for s in X.shape)
         self.nrm = torch.empty(self.n, dtype=torch.float32, device=self.dev)
-        self.api._check(self.lib.ra_kmeans_sqnorm(_ptr(X), self.n, self.d, _ptr(self.nrm), self.stream), "ra_kmeans_sqnorm")
+        self.call("ra_kmeans_sqnorm", ptr(X), self.n, self.d, ptr(self.nrm))
         self.labels = torch.empty(self.n, dtype=torch.int32, device=self.dev)
         self.stats = torch.empty(3, dtype=torch.float64, device=self.dev)
         self.closest = None
@@ -256,8 +243,7 @@ class _Device:
         if self.closest is None:
             self.closest = torch.empty(self.n, dtype=torch.float64, device=self.dev)
         out = torch.empty(m + 2, dtype=torch.float64, device=self.dev)
-        self.api._check(self.lib.ra_kmeans_seed(_ptr(self.X), self.n, self.d, _ptr(cand), m, _ptr(self.closest), int(bool(first)),
-                                                _ptr(out), self.stream), "ra_kmeans_seed")
+        self.call("ra_kmeans_seed", ptr(self.X), self.n, self.d, ptr(cand), m, ptr(self.closest), int(bool(first)), ptr(out))
         o = out[:2].cpu().numpy()
         return int(o[0]), float(o[1])
 
@@ -265,22 +251,20 @@ class _Device:
         torch = self.torch
         v = torch.from_numpy(np.ascontiguousarray(vals, np.float64)).to(self.dev)
         idx = torch.empty(int(v.numel()), dtype=torch.int32, device=self.dev)
-        self.api._check(self.lib.ra_kmeans_search(_ptr(self.closest), self.n, _ptr(v), int(v.numel()), _ptr(idx), self.stream),
-                        "ra_kmeans_search")
+        self.call("ra_kmeans_search", ptr(self.closest), self.n, ptr(v), int(v.numel()), ptr(idx))
         return idx
 
     def lloyd(self, C):
         k = int(C.shape[0])
         Cn = self.torch.empty_like(C)
-        self.api._check(self.lib.ra_kmeans_lloyd(_ptr(self.X), self.n, self.d, _ptr(self.nrm), _ptr(C), k, _ptr(Cn), _ptr(self.labels),
-                                                 _ptr(self.stats), self.stream), "ra_kmeans_lloyd")
+        self.call("ra_kmeans_lloyd", ptr(self.X), self.n, self.d, ptr(self.nrm), ptr(C), k, ptr(Cn), ptr(self.labels), ptr(self.stats))
         s = self.stats.cpu().numpy()
         return Cn, float(s[0]), int(s[1])
 
     def finish(self, C, assign):
         out = self.torch.empty(1, dtype=self.torch.float64, device=self.dev)
-        self.api._check(self.lib.ra_kmeans_labels(_ptr(self.X), self.n, self.d, _ptr(self.nrm), _ptr(C), int(C.shape[0]), _ptr(self.labels),
-                                                  int(bool(assign)), _ptr(out), self.stream), "ra_kmeans_labels")
+        self.call("ra_kmeans_labels", ptr(self.X), self.n, self.d, ptr(self.nrm), ptr(C), int(C.shape[0]), ptr(self.labels),
+                  int(bool(assign)), ptr(out))
         return float(out.item())
 
     def labels_numpy(self):
@@ -356,32 +340,6 @@ def _fit(B, k, init, n_init, max_iter, tol_abs, random_state):
     return KMeansResult(labels, B.to_numpy(C), float(inertia), int(n_iter), idx)
 
 
-def _as_input(X, backend):
-    if backend == "device":
-        import torch
-        if isinstance(X, np.ndarray):
-            X = torch.from_numpy(np.ascontiguousarray(X, np.float32)).to(torch.device("cuda", torch.cuda.current_device()))
-        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
-            raise KMeansError("backend 'device' takes a contiguous float32 CUDA tensor [n][d] (or a numpy array, copied)")
-        if X.ndim != 2:
-            raise KMeansError("X is [n][d], got shape %s" % (tuple(X.shape),))
-        return X
-    if backend != "numpy":
-        raise KMeansError("backend is 'device' or 'numpy', got %r" % (backend,))
-    if not isinstance(X, np.ndarray) and hasattr(X, "detach"):
-        X = X.detach().cpu().numpy()
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise KMeansError("X is [n][d], got shape %s" % (X.shape,))
-    return X
-
-
-def _check_finite(X, backend):
-    ok = bool(X.isfinite().all().item()) if backend == "device" else bool(np.all(np.isfinite(X)))
-    if not ok:
-        raise KMeansError("X holds NaN or infinite values")
-
-
 def _resolve_init(init, k, d):
     if isinstance(init, str):
         if init not in ("k-means++", "random"):
@@ -397,12 +355,12 @@ def _resolve_init(init, k, d):
 
 def kmeans(X, n_clusters, init="k-means++", n_init="auto", max_iter=300, tol=1e-4, random_state=None, backend="device"):
     """k-means of X [n][d]: KMeansResult(labels int32 [n], centers float64 [k][d], inertia, n_iter, init_indices)"""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, KMeansError)
     n, d = (int(s) for s in X.shape)
     check_domain(n, d, n_clusters, max_iter, tol, n_init)
     init = _resolve_init(init, n_clusters, d)
     check_random_state(random_state)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, KMeansError)
     if n_init == "auto":
         n_init = 10 if isinstance(init, str) and init == "random" else 1
     if not isinstance(init, str) and n_init != 1:
@@ -419,12 +377,12 @@ def kmeans(X, n_clusters, init="k-means++", n_init="auto", max_iter=300, tol=1e-
 
 def labels_for(X, centers, backend="device"):
     """(labels int32 [n], inertia) of the given centers [k][d]: the E-step alone"""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, KMeansError)
     n, d = (int(s) for s in X.shape)
     C = np.asarray(centers, np.float64)
     check_domain(n, d, int(C.shape[0]) if C.ndim == 2 else 0)
     C = _resolve_init(C, C.shape[0], d)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, KMeansError)
     if backend == "numpy":
         B = _Numpy(X)
         inertia = B.finish(C, True)
@@ -520,7 +478,7 @@ def _as_labels(labels, n, k):
     lab = lab.astype(np.int64)
     if k is None:
         k = int(lab.max()) + 1
-    if not (_is_int(k) and 1 <= k <= MAX_K):
+    if not (is_int(k) and 1 <= k <= MAX_K):
         raise KMeansError("need 1 <= k <= %d, got %r" % (MAX_K, k))
     if lab.min() < 0 or lab.max() >= k:
         raise KMeansError("labels are integers in 0 .. k - 1 = %d, got %d .. %d" % (k - 1, lab.min(), lab.max()))
@@ -528,7 +486,7 @@ def _as_labels(labels, n, k):
 
 
 def _validity_input(X, labels, k, backend):
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, KMeansError)
     n, d = (int(s) for s in X.shape)
     if not (1 <= n <= MAX_N and 1 <= d <= MAX_D):
         raise KMeansError("need 1 <= n <= %d points of 1 <= d <= %d features, got %d x %d" % (MAX_N, MAX_D, n, d))
@@ -540,7 +498,7 @@ def _sample(n, sample_size, random_state):
     """sklearn's silhouette_score subsample: check_random_state(rs).permutation(n)[:sample_size]; None without sample_size"""
     if sample_size is None:
         return None
-    if not (_is_int(sample_size) and 1 <= sample_size):
+    if not (is_int(sample_size) and 1 <= sample_size):
         raise KMeansError("sample_size is None or an integer >= 1, got %r" % (sample_size,))
     return check_random_state(random_state).permutation(n)[:sample_size]
 
@@ -585,16 +543,14 @@ def _device_labels(X, lab):
 
 
 def _silhouette_device(X, lab, k):
-    import torch
-    from . import api
-    lib = api.load_library()
+    L = Launcher(X)
+    torch = L.torch
     n, d = (int(s) for s in X.shape)
     with torch.cuda.device(X.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
         labels = _device_labels(X, lab)
         out = torch.empty((n, 3), dtype=torch.float64, device=X.device)
         near = torch.empty(n, dtype=torch.int32, device=X.device)
-        api._check(lib.ra_kmeans_silhouette(_ptr(X), n, d, _ptr(labels), k, _ptr(out), _ptr(near), stream), "ra_kmeans_silhouette")
+        L.call("ra_kmeans_silhouette", ptr(X), n, d, ptr(labels), k, ptr(out), ptr(near))
         o = out.cpu().numpy()
         return o[:, 0].copy(), o[:, 1].copy(), o[:, 2].copy(), near.cpu().numpy()
 
@@ -609,7 +565,7 @@ def _take(X, idx, backend):
 def _silhouette(X, lab, k, backend):
     n, d = (int(s) for s in X.shape)
     _check_silhouette_domain(n, d, k, lab)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, KMeansError)
     return _silhouette_device(X, lab, k) if backend == "device" else _silhouette_numpy(X, lab, k)
 
 
@@ -640,7 +596,7 @@ def _dispersion(X, lab, k, backend):
     """(centroids [k][d], counts [k], sum |x - mu_c|^2 [k], sum |x - mu_c| [k]) from the labels, float64"""
     n, d = (int(s) for s in X.shape)
     check_number_of_labels(int(np.count_nonzero(np.bincount(lab, minlength=k))), n)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, KMeansError)
     if backend == "numpy":
         Xd = np.asarray(X, np.float64)
         cnt = np.bincount(lab, minlength=k)
@@ -649,18 +605,15 @@ def _dispersion(X, lab, k, backend):
         cen = sums / np.maximum(cnt, 1)[:, None]
         dist = np.sum((Xd - cen[lab]) ** 2, axis=1)
         return cen, cnt, np.bincount(lab, weights=dist, minlength=k), np.bincount(lab, weights=np.sqrt(dist), minlength=k)
-    import torch
-    from . import api
-    lib = api.load_library()
+    L = Launcher(X)
+    torch = L.torch
     with torch.cuda.device(X.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
         labels = _device_labels(X, lab)
         cen = torch.empty((k, d), dtype=torch.float64, device=X.device)
         cnt = torch.empty(k, dtype=torch.int32, device=X.device)
         sq = torch.empty(k, dtype=torch.float64, device=X.device)
         ab = torch.empty(k, dtype=torch.float64, device=X.device)
-        api._check(lib.ra_kmeans_dispersion(_ptr(X), n, d, _ptr(labels), k, _ptr(cen), _ptr(cnt), _ptr(sq), _ptr(ab), stream),
-                   "ra_kmeans_dispersion")
+        L.call("ra_kmeans_dispersion", ptr(X), n, d, ptr(labels), k, ptr(cen), ptr(cnt), ptr(sq), ptr(ab))
         return cen.cpu().numpy(), cnt.cpu().numpy().astype(np.int64), sq.cpu().numpy(), ab.cpu().numpy()
 
 
@@ -735,11 +688,11 @@ def sweep(X, ks, sample_size=None, random_state=None, backend="device", **kmeans
     ks = [int(v) for v in ks]
     if not ks or any(b <= a for a, b in zip(ks, ks[1:])) or ks[0] < 2:
         raise KMeansError("a sweep needs increasing k >= 2, got %r" % (ks,))
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, KMeansError)
     n, d = (int(s) for s in X.shape)
     for k in ks:
         check_domain(n, d, k)
-    if n > SIL_MAX_N and not (_is_int(sample_size) and sample_size <= SIL_MAX_N):
+    if n > SIL_MAX_N and not (is_int(sample_size) and sample_size <= SIL_MAX_N):
         raise KMeansError("more than %d points need sample_size <= %d for the silhouette" % (SIL_MAX_N, SIL_MAX_N))
     rows = []
     for k in ks:
@@ -768,7 +721,7 @@ def class_averages(images, params, labels, k, ou, min_count=1, preprocess=True, 
     lab = np.asarray(labels.detach().cpu().numpy() if hasattr(labels, "detach") else labels).astype(np.int64)
     if prm.shape != (n, 4):
         raise KMeansError("params is [%d][4] (alpha, sx, sy, mirror), got %s" % (n, prm.shape))
-    if lab.shape != (n,) or not (_is_int(k) and 1 <= k <= MAX_K) or lab.min() < 0 or lab.max() >= k:
+    if lab.shape != (n,) or not (is_int(k) and 1 <= k <= MAX_K) or lab.min() < 0 or lab.max() >= k:
         raise KMeansError("labels are [%d] integers in 0 .. k - 1 with 1 <= k <= %d" % (n, MAX_K))
     rec = np.zeros(n, api.RESULT_DTYPE)
     rec["alpha"], rec["sx"], rec["sy"] = prm[:, 0], prm[:, 1], prm[:, 2]
@@ -796,66 +749,30 @@ def class_averages(images, params, labels, k, ou, min_count=1, preprocess=True, 
 
 def read_input(path, key="factors"):
     """[n][d] float32 from an .npz (key) or an .npy"""
-    try:
-        if path.endswith(".npz"):
-            with np.load(path) as z:
-                if key not in z.files:
-                    raise KMeansError("%s has no array %r (it holds %s)" % (path, key, ", ".join(z.files)))
-                X = z[key]
-        else:
-            X = np.load(path)
-    except (OSError, ValueError) as e:
-        raise KMeansError("%s: %s" % (path, e))
-    X = np.ascontiguousarray(X, np.float32)
-    if X.ndim != 2:
-        raise KMeansError("%s: need an [n][d] array, got shape %s" % (path, X.shape))
-    return X
+    return _common.read_input(path, key, KMeansError)
 
 
 def read_truth(path, n):
     """[n] int classes from an int .npy or a params.txt (idx angle_psi shift_x shift_y mirror class, rows in any order)"""
-    try:
-        if path.endswith(".npy"):
-            y = np.load(path)
-            if y.shape != (n,) or not np.issubdtype(y.dtype, np.integer):
-                raise KMeansError("%s: need [%d] integers, got %s %s" % (path, n, y.dtype, y.shape))
-            return y.astype(np.int64)
-        rows = np.loadtxt(path, ndmin=2, dtype=np.float64)
-    except (OSError, ValueError) as e:
-        raise KMeansError("%s: %s" % (path, e))
-    if rows.shape != (n, 6):
-        raise KMeansError("%s: need %d rows of 6 columns (params.txt), got %s" % (path, n, rows.shape))
-    idx = rows[:, 0].astype(np.int64)
-    if not np.array_equal(np.sort(idx), np.arange(n)):
-        raise KMeansError("%s: the idx column is not a permutation of 0 .. %d" % (path, n - 1))
-    y = np.empty(n, np.int64)
-    y[idx] = rows[:, 5].astype(np.int64)
-    return y
+    return _common.read_truth(path, n, KMeansError)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m cryo_ralib_amd.kmeans")
-    ap.add_argument("input", help="OUT.npz of the sdr or tsne tool, or an [n][d] .npy")
-    ap.add_argument("output", help="OUT.npz")
+    _common.add_cluster_arguments(ap, ("input", "output"), "factors", False)
     ap.add_argument("--k", type=int, default=None, help="number of clusters (optional with --sweep)")
     ap.add_argument("--scores", action="store_true", help="silhouette (overall, per class, per sample), Calinski-Harabasz and "
                     "Davies-Bouldin of the result in OUT.npz, and one line per class")
     ap.add_argument("--sweep", default=None, help="K1,K2,... or LO:HI[:STEP]: k-means and the three scores for every k; the "
                     "result written is that of --k if given, else of the largest silhouette")
     ap.add_argument("--sample_size", type=int, default=None, help="evaluate the silhouette on sklearn's random subsample of this size")
-    ap.add_argument("--key", default="factors", help="array of an .npz input (default factors; embedding for the tsne tool)")
+    _common.add_cluster_arguments(ap, ("--key",), "factors", False)
     ap.add_argument("--init", default="k-means++", help="k-means++, random or a [k][d] .npy")
     ap.add_argument("--n_init", default="auto", help="'auto' or an integer")
     ap.add_argument("--max_iter", type=int, default=300)
     ap.add_argument("--tol", type=float, default=1e-4)
     ap.add_argument("--seed", type=int, default=None, help="random_state")
-    ap.add_argument("--backend", default="device", choices=("device", "numpy"))
-    ap.add_argument("--truth", default=None, help="int .npy or params.txt: purity, c_purity and contingency in OUT.npz")
-    ap.add_argument("--stack", default=None, help="stack for --averages (.hdf, .mrcs or .npy)")
-    ap.add_argument("--params", default=None, help="params.txt or initial2Dparams.txt of the stack")
-    ap.add_argument("--ou", type=int, default=None, help="outer radius of the averages' mask")
-    ap.add_argument("--averages", default=None, help="REFS.{hdf,mrcs,npy}: the k class averages")
-    ap.add_argument("--device", type=int, default=0)
+    _common.add_cluster_arguments(ap, ("--backend", "--truth", "--stack", "--params", "--ou", "--averages", "--device"), "factors", False)
     args = ap.parse_args(argv)
     ks = None
     if args.sample_size is not None and not (args.scores or args.sweep is not None):
@@ -879,21 +796,14 @@ def main(argv=None):
         if (args.scores or ks) and n > SIL_MAX_N and not (args.sample_size and args.sample_size <= SIL_MAX_N):
             raise KMeansError("more than %d points need --sample_size <= %d for the silhouette" % (SIL_MAX_N, SIL_MAX_N))
         truth = read_truth(args.truth, n) if args.truth else None
-        if args.averages and not (args.stack and args.params and args.ou):
-            raise KMeansError("--averages needs --stack, --params and --ou")
     except (KMeansError, OSError, ValueError) as e:
         raise SystemExit("error: %s" % e)
+    _common.check_averages_arguments(ap, args, usage=False)
     if args.backend == "device" or args.averages:
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU visible: use --backend numpy for the CPU checker (--averages needs the GPU)")
+        _common.require_gpu(_common.NO_GPU)
     swept = val = None
     try:
-        Xb = X
-        if args.backend == "device":
-            import torch
-            dev = torch.device("cuda", args.device)
-            Xb = torch.from_numpy(X).to(dev)
+        Xb = _common.to_device(X, args.device) if args.backend == "device" else X
         if ks:
             swept = sweep(Xb, ks, args.sample_size, args.seed, args.backend, init=init, n_init=n_init, max_iter=args.max_iter, tol=args.tol)
             if args.k is None:
@@ -911,21 +821,9 @@ def main(argv=None):
                init=np.str_(args.init), seed=np.int64(-1 if args.seed is None else args.seed), backend=np.str_(args.backend))
     msg = "%s: %d points x %d, k = %d, %d iterations, inertia %.6g" % (args.output, n, d, args.k, res.n_iter, res.inertia)
     if truth is not None:
-        out["purity"], out["c_purity"] = np.float64(purity_score(truth, res.labels)), np.float64(c_purity_score(truth, res.labels))
-        out["contingency"] = contingency_matrix(truth, res.labels)
-        msg += ", purity %.4f, c_purity %.4f" % (out["purity"], out["c_purity"])
+        msg += _common.truth_scores(out, truth, res.labels)
     if args.averages:
-        from . import sdr, stackio
-        try:
-            stack = np.ascontiguousarray(stackio.read_stack(args.stack), np.float32)
-            if stack.ndim != 3 or stack.shape[0] != n:
-                raise KMeansError("%s: need a stack of %d images, got shape %s" % (args.stack, n, stack.shape))
-            prm = sdr.read_params(args.params, n)
-            refs = class_averages(stack, prm, res.labels, args.k, args.ou, device=args.device)
-        except (KMeansError, sdr.SdrError, OSError, ValueError) as e:
-            raise SystemExit("error: %s" % e)
-        stackio.write_stack(args.averages, refs)
-        msg += ", averages -> %s" % args.averages
+        msg += _common.write_averages(args, n, res.labels, args.k, None, KMeansError)
     if swept is not None:
         out["sweep"], out["best_k"] = swept.table(), np.int64(swept.best_k)
         print("%5s %14s %11s %14s %11s" % ("k", "inertia", "silhouette", "CH", "DB"))

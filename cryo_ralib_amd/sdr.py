@@ -17,11 +17,12 @@ Domain: 1 <= p, q <= 256; 1 <= p0 <= min(p, 64); 1 <= q0 <= min(q, 64); p0 q0 <=
 ARPACK (the reference) additionally needs p0 < p - 1 and q0 < q - 1; eigh has no such limit.
 """
 import argparse
-import ctypes
-import os
 import sys
 
 import numpy as np
+
+from . import _common
+from ._common import Launcher, ptr
 
 
 class SdrError(ValueError):
@@ -115,44 +116,35 @@ def _numpy_run(images, p0, q0, r, max_iter, tol):
 
 # ---- device
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr())
-
-
 class _Device:
     """thin launcher of the ra_sdr_* entries on the current stream of the images' device"""
 
     def __init__(self, images):
-        import torch
-        from . import api
-        self.torch, self.api, self.lib = torch, api, api.load_library()
-        self.x, self.dev = images, images.device
+        L = Launcher(images)
+        self.torch, self.api, self.lib, self.dev, self.stream, self.call = L.torch, L.api, L.lib, L.dev, L.stream, L.call
+        self.x = images
         self.n, self.p, self.q = (int(s) for s in images.shape)
-        self.stream = ctypes.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
 
     def _f32(self, M):
         return self.torch.from_numpy(np.ascontiguousarray(M, np.float32)).to(self.dev)
 
     def mean(self):
         m = self.torch.empty((self.p, self.q), dtype=self.torch.float32, device=self.dev)
-        self.api._check(self.lib.ra_sdr_mean(_ptr(self.x), self.n, self.p, self.q, _ptr(m), self.stream), "ra_sdr_mean")
+        self.call("ra_sdr_mean", ptr(self.x), self.n, self.p, self.q, ptr(m))
         return m
 
     def gram(self, x, n, p, q, mean, form, P=None):
         d = p if form == 1 else q
         g = self.torch.empty((d, d), dtype=self.torch.float64, device=self.dev)
         Pd = self._f32(P) if P is not None else None
-        self.api._check(self.lib.ra_sdr_gram(_ptr(x), n, p, q, _ptr(mean) if mean is not None else None, form,
-                                             _ptr(Pd) if Pd is not None else None, 0 if P is None else int(P.shape[1]),
-                                             _ptr(g), self.stream), "ra_sdr_gram")
+        self.call("ra_sdr_gram", ptr(x), n, p, q, ptr(mean), form, ptr(Pd), 0 if P is None else int(P.shape[1]), ptr(g))
         return g.cpu().numpy()
 
     def project(self, mean, A, B):
         p0, q0 = A.shape[1], B.shape[1]
         U = self.torch.empty((self.n, p0 * q0), dtype=self.torch.float32, device=self.dev)
         Ad, Bd = self._f32(A), self._f32(B)
-        self.api._check(self.lib.ra_sdr_project(_ptr(self.x), self.n, self.p, self.q, _ptr(mean), _ptr(Ad), p0, _ptr(Bd), q0,
-                                                _ptr(U), self.stream), "ra_sdr_project")
+        self.call("ra_sdr_project", ptr(self.x), self.n, self.p, self.q, ptr(mean), ptr(Ad), p0, ptr(Bd), q0, ptr(U))
         return U
 
     def factors(self, U, G):
@@ -160,7 +152,7 @@ class _Device:
         r = G.shape[1]
         F = self.torch.empty((n, r), dtype=self.torch.float32, device=self.dev)
         Gd = self._f32(G)
-        self.api._check(self.lib.ra_sdr_factors(_ptr(U), n, m, _ptr(Gd), r, _ptr(F), self.stream), "ra_sdr_factors")
+        self.call("ra_sdr_factors", ptr(U), n, m, ptr(Gd), r, ptr(F))
         return F
 
 
@@ -215,22 +207,7 @@ def mpca(images, p0, q0, max_iter=30, tol=1e-7, backend="device"):
 def read_params(path, n):
     """[n][4] (alpha, sx, sy, mirror) from a params.txt (idx angle_psi shift_x shift_y mirror class, rows in any order) or an
     initial2Dparams.txt (alpha sx sy mirror, in stack order)"""
-    try:
-        rows = np.loadtxt(path, ndmin=2, dtype=np.float64)
-    except ValueError as e:
-        raise SdrError("%s: not a params file (%s)" % (path, e))
-    if rows.shape[0] != n:
-        raise SdrError("%s has %d rows, the stack %d images" % (path, rows.shape[0], n))
-    if rows.shape[1] == 4:
-        return rows
-    if rows.shape[1] == 6:
-        idx = rows[:, 0].astype(np.int64)
-        if not np.array_equal(np.sort(idx), np.arange(n)) or not np.array_equal(idx, rows[:, 0]):
-            raise SdrError("%s: the idx column is not a permutation of 0 .. %d" % (path, n - 1))
-        out = np.empty((n, 4))
-        out[idx] = rows[:, 1:5]
-        return out
-    raise SdrError("%s: rows of %d columns; expected 6 (params.txt) or 4 (initial2Dparams.txt)" % (path, rows.shape[1]))
+    return _common.read_params(path, n, SdrError)
 
 
 def main(argv=None):
@@ -243,10 +220,9 @@ def main(argv=None):
     ap.add_argument("--max_iter", type=int, default=30); ap.add_argument("--tol", type=float, default=1e-7)
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    _common.require_gpu("no GPU visible: the reduction has no CPU path outside backend='numpy'")
     import torch
     from . import api, stackio
-    if not torch.cuda.is_available():
-        raise SystemExit("no GPU visible: the reduction has no CPU path outside backend='numpy'")
     data = np.ascontiguousarray(stackio.read_stack(args.stack), np.float32)
     if data.ndim != 3:
         raise SystemExit("%s: not a stack of 2-D images" % args.stack)
@@ -265,7 +241,7 @@ def main(argv=None):
     if need > free:
         raise SystemExit("error: the stack needs about %.2f GB on the device, %.2f GB are free; the reduction does not chunk"
                          % (need / 1e9, free / 1e9))
-    x = torch.from_numpy(data).to(dev)
+    x = _common.to_device(data, args.device)
     with torch.cuda.device(dev):
         if prm is not None:
             x = api.rot_shift2d(x, prm)

@@ -22,12 +22,13 @@ Domain: 2 <= n <= 262144, 1 <= d <= 2048, 0 < perplexity <= 100 and perplexity <
 needs d >= 2.  Anything else raises TsneError before anything is launched; so does non-finite input.
 """
 import argparse
-import ctypes
 import math
 import sys
 
 import numpy as np
 
+from . import _common
+from ._common import Launcher, ptr
 from .sdr import fix_signs
 
 N_ITER_CHECK = 50          # sklearn TSNE._N_ITER_CHECK
@@ -81,14 +82,8 @@ def resolve_learning_rate(learning_rate, n, early_exaggeration):
 
 
 def check_random_state(seed):
-    """sklearn.utils.check_random_state"""
-    if seed is None or seed is np.random:
-        return np.random.mtrand._rand
-    if isinstance(seed, (int, np.integer)):
-        return np.random.RandomState(seed)
-    if isinstance(seed, np.random.RandomState):
-        return seed
-    raise TsneError("random_state is None, an integer or a numpy RandomState, got %r" % (seed,))
+    """sklearn.utils.check_random_state; a bool counts as the integer it is"""
+    return _common.check_random_state(int(seed) if isinstance(seed, bool) else seed, TsneError)
 
 
 def random_init(n, random_state=None):
@@ -231,30 +226,24 @@ class _NumpyState:
 
 # ---- device
 
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
-
-
 class _Device:
     """thin launcher of the ra_tsne_* entries on the current stream of X's device"""
 
     def __init__(self, dev):
-        import torch
-        from . import api
-        self.torch, self.api, self.lib, self.dev = torch, api, api.load_library(), dev
-        self.stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        L = Launcher(dev)
+        self.torch, self.api, self.lib, self.dev, self.stream, self.call = L.torch, L.api, L.lib, L.dev, L.stream, L.call
 
     def knn(self, X, k):
         n, d = (int(s) for s in X.shape)
         idx = self.torch.empty((n, k), dtype=self.torch.int32, device=self.dev)
         d2 = self.torch.empty((n, k), dtype=self.torch.float64, device=self.dev)
-        self.api._check(self.lib.ra_tsne_knn(_ptr(X), n, d, k, _ptr(idx), _ptr(d2), self.stream), "ra_tsne_knn")
+        self.call("ra_tsne_knn", ptr(X), n, d, k, ptr(idx), ptr(d2))
         return idx, d2
 
     def affinity(self, d2, perplexity):
         n, k = (int(s) for s in d2.shape)
         pc = self.torch.empty((n, k), dtype=self.torch.float64, device=self.dev)
-        self.api._check(self.lib.ra_tsne_affinity(_ptr(d2), n, k, float(perplexity), _ptr(pc), self.stream), "ra_tsne_affinity")
+        self.call("ra_tsne_affinity", ptr(d2), n, k, float(perplexity), ptr(pc))
         return pc
 
     def symmetrize(self, idx, pc):
@@ -280,8 +269,7 @@ class _Device:
         n = int(y.shape[0])
         g = self.torch.empty((n, 2), dtype=self.torch.float32, device=self.dev)
         st = self.torch.empty(2, dtype=self.torch.float64, device=self.dev)
-        self.api._check(self.lib.ra_tsne_error(_ptr(y), n, _ptr(indptr), _ptr(indices), _ptr(p32), int(p32.numel()),
-                                               float(exaggeration), _ptr(g), _ptr(st), self.stream), "ra_tsne_error")
+        self.call("ra_tsne_error", ptr(y), n, ptr(indptr), ptr(indices), ptr(p32), int(p32.numel()), float(exaggeration), ptr(g), ptr(st))
         return float(st[0].item()), g
 
 
@@ -303,10 +291,9 @@ class _DeviceState:
         self.gains.fill_(1.0)
 
     def step(self, exaggeration, momentum, learning_rate, want):
-        D = self.D
-        D.api._check(D.lib.ra_tsne_step(_ptr(self.y), _ptr(self.y2), _ptr(self.update), _ptr(self.gains), self.n, _ptr(self.indptr),
-                                        _ptr(self.indices), _ptr(self.p), int(self.p.numel()), float(exaggeration), float(momentum),
-                                        float(learning_rate), _ptr(self.stats) if want else None, D.stream), "ra_tsne_step")
+        self.D.call("ra_tsne_step", ptr(self.y), ptr(self.y2), ptr(self.update), ptr(self.gains), self.n, ptr(self.indptr),
+                    ptr(self.indices), ptr(self.p), int(self.p.numel()), float(exaggeration), float(momentum), float(learning_rate),
+                    ptr(self.stats) if want else None)
         self.y, self.y2 = self.y2, self.y
         if not want:
             return None
@@ -348,36 +335,12 @@ def _optimise(state, max_iter, early_exaggeration, learning_rate, n_iter_without
     return float(error), int(it), np.asarray(errors, np.float64)
 
 
-def _as_input(X, backend):
-    if backend == "device":
-        import torch
-        if not (isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float32 and X.is_contiguous()):
-            raise TsneError("backend 'device' takes a contiguous float32 CUDA tensor [n][d]")
-        if X.ndim != 2:
-            raise TsneError("X is [n][d], got shape %s" % (tuple(X.shape),))
-        return X
-    if backend != "numpy":
-        raise TsneError("backend is 'device' or 'numpy', got %r" % (backend,))
-    if not isinstance(X, np.ndarray) and hasattr(X, "detach"):
-        X = X.detach().cpu().numpy()
-    X = np.asarray(X)
-    if X.ndim != 2:
-        raise TsneError("X is [n][d], got shape %s" % (X.shape,))
-    return X
-
-
-def _check_finite(X, backend):
-    ok = bool(X.isfinite().all().item()) if backend == "device" else bool(np.all(np.isfinite(X)))
-    if not ok:
-        raise TsneError("X holds NaN or infinite values")
-
-
 def affinities(X, perplexity=30.0, backend="device"):
     """(indptr [n + 1], indices, P float64) of the symmetric joint probabilities, as numpy arrays"""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, TsneError, numpy_on_device=False)
     n, d = (int(s) for s in X.shape)
     check_domain(n, d, perplexity)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, TsneError)
     k = n_neighbors(n, perplexity)
     if backend == "numpy":
         idx, d2 = knn_numpy(X, k)
@@ -392,7 +355,7 @@ def affinities(X, perplexity=30.0, backend="device"):
 
 def knn(X, k, backend="device"):
     """(idx [n][k], dist2 [n][k] float64) of the k nearest neighbours of every row, as numpy arrays"""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, TsneError, numpy_on_device=False)
     n, d = (int(s) for s in X.shape)
     if not (2 <= n <= MAX_N and 1 <= d <= MAX_D and 1 <= k <= min(n - 1, 301)):
         raise TsneError("need 2 <= n <= %d, 1 <= d <= %d and 1 <= k <= min(n - 1, 301)" % (MAX_N, MAX_D))
@@ -418,20 +381,20 @@ def _pca_init_device(X, D):
     torch = D.torch
     n, d = (int(s) for s in X.shape)
     mean = torch.empty(d, dtype=torch.float32, device=D.dev)
-    D.api._check(D.lib.ra_sdr_mean(_ptr(X), n, 1, d, _ptr(mean), D.stream), "ra_sdr_mean")
+    D.call("ra_sdr_mean", ptr(X), n, 1, d, ptr(mean))
     g = torch.empty((d, d), dtype=torch.float64, device=D.dev)
-    D.api._check(D.lib.ra_sdr_gram(_ptr(X), n, 1, d, _ptr(mean), 0, None, 0, _ptr(g), D.stream), "ra_sdr_gram")
+    D.call("ra_sdr_gram", ptr(X), n, 1, d, ptr(mean), 0, None, 0, ptr(g))
     _, V = sdr.top_eig(g.cpu().numpy(), 2)
     Vd = torch.from_numpy(np.ascontiguousarray(V, np.float32)).to(D.dev)
     F = torch.empty((n, 2), dtype=torch.float32, device=D.dev)
-    D.api._check(D.lib.ra_sdr_factors(_ptr(X), n, d, _ptr(Vd), 2, _ptr(F), D.stream), "ra_sdr_factors")
+    D.call("ra_sdr_factors", ptr(X), n, d, ptr(Vd), 2, ptr(F))
     shift = mean.cpu().numpy().astype(np.float64) @ V            # (x - mean) V = x V - mean V
     return _scale_pca(F.cpu().numpy().astype(np.float64) - shift)
 
 
 def initial_embedding(X, init="pca", random_state=None, backend="device"):
     """the [n][2] float32 start of the optimisation (sklearn's init)"""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, TsneError, numpy_on_device=False)
     n, d = (int(s) for s in X.shape)
     if isinstance(init, str):
         if init == "random":
@@ -456,10 +419,10 @@ def initial_embedding(X, init="pca", random_state=None, backend="device"):
 def tsne(X, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_iter=1000, n_iter_without_progress=300,
          min_grad_norm=1e-7, init="pca", random_state=None, n_components=2, backend="device"):
     """t-SNE of X [n][d]: TsneResult(embedding [n][2] float32, kl_divergence, n_iter, errors)"""
-    X = _as_input(X, backend)
+    X = _common.as_input(X, backend, TsneError, numpy_on_device=False)
     n, d = (int(s) for s in X.shape)
     check_domain(n, d, perplexity, max_iter, n_components, early_exaggeration, learning_rate)
-    _check_finite(X, backend)
+    _common.check_finite(X, backend, TsneError)
     lr = resolve_learning_rate(learning_rate, n, early_exaggeration)
     Y0 = initial_embedding(X, init, random_state, backend)
     k = n_neighbors(n, perplexity)
@@ -538,20 +501,7 @@ def trustworthiness(X, Y, n_neighbors=10):
 
 def read_input(path, key="factors"):
     """[n][d] float32 from an .npz (key) or an .npy"""
-    try:
-        if path.endswith(".npz"):
-            with np.load(path) as z:
-                if key not in z.files:
-                    raise TsneError("%s has no array %r (it holds %s)" % (path, key, ", ".join(z.files)))
-                X = z[key]
-        else:
-            X = np.load(path)
-    except (OSError, ValueError) as e:
-        raise TsneError("%s: %s" % (path, e))
-    X = np.ascontiguousarray(X, np.float32)
-    if X.ndim != 2:
-        raise TsneError("%s: need an [n][d] array, got shape %s" % (path, X.shape))
-    return X
+    return _common.read_input(path, key, TsneError)
 
 
 def main(argv=None):
@@ -576,13 +526,8 @@ def main(argv=None):
     except (TsneError, OSError, ValueError) as e:
         raise SystemExit("error: %s" % e)
     if args.backend == "device":
-        import torch
-        if not torch.cuda.is_available():
-            raise SystemExit("no GPU visible: use --backend numpy for the CPU checker")
-        dev = torch.device("cuda", args.device)
-        x = torch.from_numpy(X).to(dev)
-    else:
-        x = X
+        _common.require_gpu("no GPU visible: use --backend numpy for the CPU checker")
+    x = _common.to_device(X, args.device) if args.backend == "device" else X
     try:
         if args.backend == "device":
             import torch

@@ -64,6 +64,7 @@ import sys
 import numpy as np
 
 from . import ctf as _ctf
+from ._common import Launcher, ptr
 
 MAX_K = 1024
 
@@ -441,7 +442,6 @@ def accumulate(images, params, labels, k, table, num, den, counts, pad=True, fli
     """ra_wiener_accumulate on the current stream: add the weighted spectra of images [n][nx][nx] (contiguous float32 CUDA
     tensor) into num / den / counts (new_sums).  params [n][4], labels [n] and table [n][9] go to the device unchecked apart from
     their shapes: the library refuses bad labels, non-finite params and bad table rows (api.EngineError) and then adds nothing"""
-    import ctypes
     import torch
     from . import api
     assert images.is_cuda and images.is_contiguous() and images.dtype == torch.float32, "images: contiguous float32 CUDA tensor"
@@ -462,29 +462,22 @@ def accumulate(images, params, labels, k, table, num, den, counts, pad=True, fli
     rec["mirror"] = (prm[:, 3] != 0).astype(np.int32)
     rec["ref_id"] = np.clip(lab, -2 ** 31, 2 ** 31 - 1).astype(np.int32)
     d_rec = torch.from_numpy(rec.view(np.uint8)).to(images.device)
-    stream = torch.cuda.current_stream(images.device)
+    L = Launcher(images)
     with torch.cuda.device(images.device):
-        api._check(api.load_library().ra_wiener_accumulate(
-            ctypes.c_void_p(images.data_ptr()), n, nx, ctypes.c_void_p(d_rec.data_ptr()), tab.ctypes.data_as(api.float_ptr),
-            int(bool(pad)), int(bool(flipped)), int(k), ctypes.c_void_p(num.data_ptr()), ctypes.c_void_p(den.data_ptr()),
-            ctypes.c_void_p(counts.data_ptr()), ctypes.c_void_p(stream.cuda_stream)), "ra_wiener_accumulate")
+        L.call("ra_wiener_accumulate", ptr(images), n, nx, ptr(d_rec), tab.ctypes.data_as(api.float_ptr), int(bool(pad)),
+               int(bool(flipped)), int(k), ptr(num), ptr(den), ptr(counts))
 
 
 def finalize(num, den, counts, nx, pad=True, snr=1.0, min_count=1, out=None):
     """ra_wiener_finalize on the current stream: [k][nx][nx] float32 CUDA tensor of the averages"""
-    import ctypes
     import torch
-    from . import api
     k = int(counts.shape[0])
     if out is None:
         out = torch.empty((k, nx, nx), dtype=torch.float32, device=num.device)
     assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (k, nx, nx)
-    stream = torch.cuda.current_stream(num.device)
+    L = Launcher(num)
     with torch.cuda.device(num.device):
-        api._check(api.load_library().ra_wiener_finalize(
-            ctypes.c_void_p(num.data_ptr()), ctypes.c_void_p(den.data_ptr()), ctypes.c_void_p(counts.data_ptr()), k, int(nx),
-            int(bool(pad)), float(snr), int(min_count), ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(stream.cuda_stream)),
-            "ra_wiener_finalize")
+        L.call("ra_wiener_finalize", ptr(num), ptr(den), ptr(counts), k, int(nx), int(bool(pad)), float(snr), int(min_count), ptr(out))
     return out
 
 
@@ -522,28 +515,22 @@ def accumulate_halves(images, params, labels, k, table, num2, den2, counts2, ind
 
 def frc(num2, den2, counts2, nx, pad=True, snr=1.0, min_count=1, ssnr_floor=SSNR_FLOOR):
     """ra_wiener_frc on the current stream: (frc [k][P/2 + 1] float64, reg [k][P/2 + 1] float32) CUDA tensors from the half sums"""
-    import ctypes
     import torch
-    from . import api
     k = int(counts2.shape[0])
     _flat_halves(num2, den2, counts2)
     S = (2 * nx if pad else nx) // 2 + 1
     f = torch.empty((k, S), dtype=torch.float64, device=num2.device)
     r = torch.empty((k, S), dtype=torch.float32, device=num2.device)
-    stream = torch.cuda.current_stream(num2.device)
+    L = Launcher(num2)
     with torch.cuda.device(num2.device):
-        api._check(api.load_library().ra_wiener_frc(
-            ctypes.c_void_p(num2.data_ptr()), ctypes.c_void_p(den2.data_ptr()), ctypes.c_void_p(counts2.data_ptr()), k, int(nx),
-            int(bool(pad)), float(snr), int(min_count), float(ssnr_floor), ctypes.c_void_p(f.data_ptr()), ctypes.c_void_p(r.data_ptr()),
-            ctypes.c_void_p(stream.cuda_stream)), "ra_wiener_frc")
+        L.call("ra_wiener_frc", ptr(num2), ptr(den2), ptr(counts2), k, int(nx), int(bool(pad)), float(snr), int(min_count),
+               float(ssnr_floor), ptr(f), ptr(r))
     return f, r
 
 
 def finalize_ssnr(num2, den2, counts2, reg, nx, pad=True, min_count=1, out=None):
     """ra_wiener_finalize_ssnr on the current stream: [k][nx][nx] float32 CUDA tensor of the SSNR-weighted averages"""
-    import ctypes
     import torch
-    from . import api
     k = int(counts2.shape[0])
     _flat_halves(num2, den2, counts2)
     S = (2 * nx if pad else nx) // 2 + 1
@@ -551,12 +538,9 @@ def finalize_ssnr(num2, den2, counts2, reg, nx, pad=True, min_count=1, out=None)
     if out is None:
         out = torch.empty((k, nx, nx), dtype=torch.float32, device=num2.device)
     assert out.is_cuda and out.is_contiguous() and out.dtype == torch.float32 and tuple(out.shape) == (k, nx, nx)
-    stream = torch.cuda.current_stream(num2.device)
+    L = Launcher(num2)
     with torch.cuda.device(num2.device):
-        api._check(api.load_library().ra_wiener_finalize_ssnr(
-            ctypes.c_void_p(num2.data_ptr()), ctypes.c_void_p(den2.data_ptr()), ctypes.c_void_p(counts2.data_ptr()),
-            ctypes.c_void_p(reg.data_ptr()), k, int(nx), int(bool(pad)), int(min_count), ctypes.c_void_p(out.data_ptr()),
-            ctypes.c_void_p(stream.cuda_stream)), "ra_wiener_finalize_ssnr")
+        L.call("ra_wiener_finalize_ssnr", ptr(num2), ptr(den2), ptr(counts2), ptr(reg), k, int(nx), int(bool(pad)), int(min_count), ptr(out))
     return out
 
 
@@ -630,7 +614,6 @@ def score(images, params, labels, k, table, num, den, counts, snr=1.0, reg=None,
     read).  reg: the per-shell term [k][P/2 + 1] (float32 CUDA tensor, `frc`'s) instead of 1/snr; band: (s_lo, s_hi), default
     (1, P/2).  The band, snr, k and reg's shape are checked here (WienerError) before anything is launched; labels, params and
     table rows as by `accumulate`"""
-    import ctypes
     import torch
     from . import api
     assert images.is_cuda and images.is_contiguous() and images.dtype == torch.float32, "images: contiguous float32 CUDA tensor"
@@ -661,14 +644,10 @@ def score(images, params, labels, k, table, num, den, counts, snr=1.0, reg=None,
     rec["ref_id"] = lab.astype(np.int32)
     d_rec = torch.from_numpy(rec.view(np.uint8)).to(images.device)
     sums = torch.zeros((n, 3), dtype=torch.float64, device=images.device)
-    stream = torch.cuda.current_stream(images.device)
+    L = Launcher(images)
     with torch.cuda.device(images.device):
-        api._check(api.load_library().ra_wiener_score(
-            ctypes.c_void_p(images.data_ptr()), n, nx, ctypes.c_void_p(d_rec.data_ptr()), tab.ctypes.data_as(api.float_ptr),
-            int(bool(pad)), int(bool(flipped)), int(k), ctypes.c_void_p(num.data_ptr()), ctypes.c_void_p(den.data_ptr()),
-            ctypes.c_void_p(counts.data_ptr()), float(snr), ctypes.c_void_p(reg.data_ptr()) if reg is not None else None,
-            int(bool(leave_one_out)), lo, hi, ctypes.c_void_p(sums.data_ptr()), ctypes.c_void_p(stream.cuda_stream)),
-            "ra_wiener_score")
+        L.call("ra_wiener_score", ptr(images), n, nx, ptr(d_rec), tab.ctypes.data_as(api.float_ptr), int(bool(pad)), int(bool(flipped)),
+               int(k), ptr(num), ptr(den), ptr(counts), float(snr), ptr(reg), int(bool(leave_one_out)), lo, hi, ptr(sums))
         h_sums, h_counts = sums.cpu().numpy(), counts.cpu().numpy()
     cc, scale = scores_from_sums(h_sums, lab, h_counts, leave_one_out, min_count)
     return {"cc": cc, "scale": scale, "sums": h_sums}
