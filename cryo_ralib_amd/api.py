@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
     "ra_hdbscan_core", "ra_hdbscan_round",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
+    "ra_prep_normalize", "ra_prep_filter",
 ]
 
 _lib = None
@@ -191,6 +192,8 @@ def load_library(path=None):
     L.ra_wiener_frc.argtypes = [vp, vp, vp, ci, ci, ci, ctypes.c_float, ci, ctypes.c_float, vp, vp, vp]
     L.ra_wiener_finalize_ssnr.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, vp, vp]
     L.ra_wiener_score.argtypes = [vp, ci, ci, vp, float_ptr, ci, ci, ci, vp, vp, vp, ctypes.c_float, vp, ci, ci, ci, vp, vp]
+    L.ra_prep_normalize.argtypes = [vp, ci, ci, ctypes.c_double, ci, ci, vp, vp]
+    L.ra_prep_filter.argtypes = [vp, ci, ci, ci, ci, ctypes.c_double, ctypes.c_double, ci, ctypes.c_double, ctypes.c_double, vp]
     L.ra_sdr_mean.argtypes = [vp, ci, ci, ci, vp, vp]
     L.ra_sdr_gram.argtypes = [vp, ci, ci, ci, vp, ci, vp, ci, vp, vp]
     L.ra_sdr_project.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
@@ -305,6 +308,18 @@ def fourier_resize(images, m, out=None):
     with torch.cuda.device(images.device):
         L.call("ra_fourier_resize", ptr(images), n, nx, m, ptr(out))
     return out
+
+
+def normalize_background(images, bg_radius, **kw):
+    """Background normalisation of a stack, with optional plane removal and contrast inversion (prep.normalize)."""
+    from . import prep
+    return prep.normalize(images, bg_radius, **kw)
+
+
+def fourier_filter(images, **kw):
+    """Low-pass / high-pass / band-pass Fourier filter of a stack (prep.fourier_filter)."""
+    from . import prep
+    return prep.fourier_filter(images, **kw)
 
 
 def wiener_averages(images, params, labels, k, ctf, **kw):

@@ -23,6 +23,10 @@ subtraction, and the CTF-free alignment follows.  TABLE is a [N][9] .npy or a RE
 gives the pixel size where the .star has none, --phase_flip_nopad flips without the 2x zero padding.  --CTF itself, which
 reads the parameters from the stack's EMAN.ctf headers, stays rejected.
 
+--norm_bg R normalises every particle's background outside radius R to mean 0 and sigma 1 once at setup, BEFORE the masked-mean
+subtraction and the flip (cryo_ralib_amd.prep); --norm_ramp (needs --norm_bg) subtracts the least-squares plane of the background
+first, --invert inverts the contrast (alone: times -1).  Without them every output is bit for bit what it was.
+
 --wiener_averages (with --phase_flip and --snr > 0) writes, after the last iteration, CTF-corrected class averages of the
 flipped particles with the final parameters (cryo_ralib_amd.wiener, flipped weights |c|, the flip's padding):
 multi_ref_wiener.<ext> (one per class) or aqfinal_wiener.<ext> (one image).  Ranks sum their spectra before the division.
@@ -59,6 +63,11 @@ def _common(p):
                         "reference's --CTF does on its GPU path")
     p.add_argument("--apix", type=float, default=None, help="pixel size (A) for a --phase_flip .star file that gives none")
     p.add_argument("--phase_flip_nopad", action="store_true", help="flip at the box size instead of in a 2x zero-padded image")
+    p.add_argument("--norm_bg", type=float, default=None, metavar="R",
+                   help="normalise every particle's background outside radius R to mean 0, sigma 1 at setup (prep.normalize), "
+                        "before the masked-mean subtraction and the phase flip")
+    p.add_argument("--norm_ramp", action="store_true", help="with --norm_bg: subtract the least-squares plane of the background first")
+    p.add_argument("--invert", action="store_true", help="invert the particles' contrast at setup (with --norm_bg: in the same pass)")
     p.add_argument("--wiener_averages", action="store_true",
                    help="after the last iteration also write CTF-corrected (Wiener) class averages, sum c^2 + 1/snr in the "
                         "denominator: multi_ref_wiener.<ext> / aqfinal_wiener.<ext>; needs --phase_flip")
@@ -161,6 +170,16 @@ def _ctf_shard(args, total, nx, lo, hi):
         return ctf.load_table(args.phase_flip, total, nx, args.apix, lo, hi)
     except (ctf.CtfTableError, OSError) as e:
         raise SystemExit("--phase_flip: %s" % e)
+
+
+def _check_prep(p, args):
+    """--norm_bg / --norm_ramp / --invert as the aligners' keyword arguments; a usage error (exit status 2) before anything is read"""
+    import math
+    if args.norm_ramp and args.norm_bg is None:
+        p.error("--norm_ramp needs --norm_bg R")
+    if args.norm_bg is not None and not (math.isfinite(args.norm_bg) and args.norm_bg >= 1.0):
+        p.error("--norm_bg needs a finite radius >= 1, got %g" % args.norm_bg)
+    return dict(normalize_bg=args.norm_bg, normalize_ramp=args.norm_ramp, invert=args.invert)
 
 
 def _check_wiener(p, args):
@@ -273,6 +292,7 @@ def main_mref(argv=None):
     args = p.parse_args(argv)
     _reject_unimplemented(args, reffree=False)
     _check_wiener(p, args)
+    prep_kw = _check_prep(p, args)
     rank, local, world = _setup(args)
     from . import stackio, dist as rdist
     from .mref import MrefAligner
@@ -288,7 +308,7 @@ def main_mref(argv=None):
     xr, yr, ts = _first(args.xr), _first(args.yr), _first(args.ts)
     al = MrefAligner(data, refs, ou, xr, yr, ts, int(args.ir), int(args.rs), device=local, index0=lo,
                      total_nima=total, rand_seed=args.rand_seed, preprocess=True, mask=mask,
-                     ctf=_ctf_shard(args, total, nx, lo, hi), ctf_pad=not args.phase_flip_nopad)
+                     ctf=_ctf_shard(args, total, nx, lo, hi), ctf_pad=not args.phase_flip_nopad, **prep_kw)
     if rank == 0:
         os.makedirs(args.outdir, exist_ok=True)
     maxit = int(args.maxit) if int(args.maxit) > 0 else 10
@@ -363,6 +383,7 @@ def main_reffree(argv=None):
     args = p.parse_args(argv)
     _reject_unimplemented(args, reffree=True)
     _check_wiener(p, args)
+    prep_kw = _check_prep(p, args)
     rank, local, world = _setup(args)
     from . import stackio, dist as rdist
     from .mref import RefFreeAligner
@@ -375,7 +396,7 @@ def main_reffree(argv=None):
     # "--xr '4 2 1 1' --ts '2 1 0.5 0.25'": one stage per entry, --maxit iterations each; --maxit 0 = 10 with auto-stop
     al = RefFreeAligner(data, ou, args.xr, args.yr, args.ts, int(args.ir), int(args.rs), device=local, index0=lo,
                         total_nima=total, nomirror=args.nomirror, mask=mask,
-                        ctf=_ctf_shard(args, total, nx, lo, hi), ctf_pad=not args.phase_flip_nopad)
+                        ctf=_ctf_shard(args, total, nx, lo, hi), ctf_pad=not args.phase_flip_nopad, **prep_kw)
     max_iter = 10 if int(args.maxit) == 0 else int(args.maxit)
     auto_stop = args.auto_stop and int(args.maxit) == 0
     al.track_pixel_error = True

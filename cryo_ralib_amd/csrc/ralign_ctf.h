@@ -16,6 +16,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 namespace ralign {
 
 #define PF_MAX_RADICES 24
@@ -73,6 +75,20 @@ __host__ __device__ constexpr PfPlan pf_make_plan(int nx, int pad)
     pl.nb = (int)nb;
     pl.lds = (int)((P + 2 * P * nb + (pl.gblk ? 0 : blk)) * 8);
     return pl;
+}
+
+// The boxes (nx, pad) with kernels specialised for their pf_make_plan plan -- the common ones -- in every kernel family that
+// runs these passes (phase flip, Wiener forward transform, particle filter)
+#define PF_FIXED_BOXES(X) X(90, 1) X(90, 0) X(100, 1) X(128, 1) X(130, 1) X(256, 1)
+
+#define PF_GBLK_BYTES ((size_t)512 << 20)      // global scratch of the large-box route: the grid is sized to stay within it
+
+// workgroups of the global-block route: as many as fit on the chip at this LDS size (256 CUs), within PF_GBLK_BYTES of scratch
+inline int pf_gblk_grid(const PfPlan &pl, int n)
+{
+    const size_t blk_bytes = (size_t)pl.nx * pl.H * sizeof(float2);
+    const size_t resident = (size_t)256 * std::max(1, std::min(4, (int)((size_t)160 * 1024 / pl.lds)));     // <= 32 waves per CU
+    return (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(resident, PF_GBLK_BYTES / blk_bytes)));
 }
 
 // per-particle constants of the CTF sign, from the [9] row (D, Apix, DefocusU, DefocusV, DefocusAngle, Voltage, Cs, w,

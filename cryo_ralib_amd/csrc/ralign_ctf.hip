@@ -7,8 +7,6 @@ using namespace ralign;
 
 // ---- CTF phase flip (ralign_ctf.h)
 
-#define PF_GBLK_BYTES ((size_t)512 << 20)      // global scratch of the large-box route: the grid is sized to stay within it
-
 // the [n][9] CTF rows (host memory) within the ranges the flip and the Wiener averages accept; sets the last error naming the row
 static bool pf_rows_ok(const char *what, const float *ctf, int n)
 {
@@ -27,9 +25,8 @@ static bool pf_rows_ok(const char *what, const float *ctf, int n)
     return true;
 }
 
-// The boxes (nx, pad) with kernels specialised for their pf_make_plan plan -- the common ones -- for the phase flip and for the
-// Wiener forward transform alike; nullptr: any other box runs the kernel that takes the plan as an argument.
-#define PF_FIXED_BOXES(X) X(90, 1) X(90, 0) X(100, 1) X(128, 1) X(130, 1) X(256, 1)
+// The kernels specialised for the boxes (nx, pad) of PF_FIXED_BOXES, for the phase flip and for the Wiener forward transform
+// alike; nullptr: any other box runs the kernel that takes the plan as an argument.
 static const void *pf_fixed_fn(int nx, int pad, bool wiener)
 {
     switch (nx * 2 + pad) {
@@ -39,14 +36,6 @@ static const void *pf_fixed_fn(int nx, int pad, bool wiener)
 #undef PF_FIXED_CASE
     default: return nullptr;
     }
-}
-
-// workgroups of the global-block route: as many as fit on the chip at this LDS size (256 CUs), within PF_GBLK_BYTES of scratch
-static int pf_gblk_grid(const PfPlan &pl, int n)
-{
-    const size_t blk_bytes = (size_t)pl.nx * pl.H * sizeof(float2);
-    const size_t resident = (size_t)256 * std::max(1, std::min(4, (int)((size_t)160 * 1024 / pl.lds)));     // <= 32 waves per CU
-    return (int)std::min<size_t>((size_t)n, std::max<size_t>(1, std::min<size_t>(resident, PF_GBLK_BYTES / blk_bytes)));
 }
 
 extern "C" int ra_phase_flip(float *d_images, int n, int nx, const float *ctf, int pad, void *hip_stream)

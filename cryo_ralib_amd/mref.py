@@ -63,10 +63,21 @@ class _Lagged:
         return self._done
 
 
+def _prepare_particles(particles, normalize_bg, normalize_ramp, invert):
+    """the aligners' normalize_bg / normalize_ramp / invert, in place on the rank's particles; nothing without them"""
+    if normalize_ramp and normalize_bg is None:
+        raise ValueError("normalize_ramp needs normalize_bg")
+    if normalize_bg is not None:
+        from . import prep
+        prep.normalize(particles, normalize_bg, ramp=bool(normalize_ramp), invert=bool(invert))
+    elif invert:
+        particles.neg_()
+
+
 class MrefAligner:
     def __init__(self, particles, refs, ou, xr, yr, ts=1.0, ir=1, rs=1, device=0, index0=0, total_nima=None,
                  rand_seed=1000, preprocess=True, chunk=0, myid=0, main_node=0, mask=None, state_roundtrip=True, refine=None,
-                 ctf=None, ctf_pad=True):
+                 ctf=None, ctf_pad=True, normalize_bg=None, normalize_ramp=False, invert=False):
         """particles: [n][nx][nx] float32 numpy array or CUDA tensor holding THIS rank's shard;
         refs: [R][nx][nx]; index0 = global index of particles[0] (even/odd split).
         state_roundtrip: rebuild the shift every search starts from out of the float32 (alpha, sx, sy) of the previous
@@ -76,11 +87,15 @@ class MrefAligner:
         particle: alpha / sx / sy then equal the CPU path's to the last bit wherever the integer winner agrees).
         ctf: [n][9] CTF table of this shard (ctf.load_table): the particles are phase-flipped once, right after the masked-mean
         subtraction (api.phase_flip, pad 2x unless ctf_pad=False), as the reference's GPU driver does with --CTF
-        (test_mref_gpu_align.py:303-308, 341-345); everything after it is unchanged."""
+        (test_mref_gpu_align.py:303-308, 341-345); everything after it is unchanged.
+        normalize_bg / normalize_ramp / invert: background normalisation of the particles outside that radius, with the plane
+        removed and the contrast inverted if asked (prep.normalize), once, BEFORE the masked-mean subtraction and the flip;
+        invert alone multiplies the particles by -1."""
         self.state_roundtrip = bool(state_roundtrip)
         self._have_params = False
         self.dev = torch.device("cuda", device)
         self.particles = self._to_dev(particles)
+        _prepare_particles(self.particles, normalize_bg, normalize_ramp, invert)
         self.refs = self._to_dev(refs).clone()
         self.n, self.nx = self.particles.shape[0], self.particles.shape[-1]
         self.nref = self.refs.shape[0]
@@ -279,14 +294,16 @@ class RefFreeAligner:
     (test_reffree_gpu_align.py:215-216); `set_stage(i)` switches the engine to stage i (reset_shifts, :355-357).
     The engine is sized once for the stage with the most search offsets and the widest range.
     ctf / ctf_pad: phase flip of the particles at setup as in MrefAligner, after the masked-mean subtraction, which then runs
-    even with preprocess=False."""
+    even with preprocess=False.  normalize_bg / normalize_ramp / invert: as in MrefAligner, before both."""
 
     def __init__(self, particles, ou, xr, yr, ts=1.0, ir=1, rs=1, device=0, index0=0, total_nima=None,
-                 preprocess=False, chunk=0, nomirror=False, mask=None, refine=None, ctf=None, ctf_pad=True):
+                 preprocess=False, chunk=0, nomirror=False, mask=None, refine=None, ctf=None, ctf_pad=True,
+                 normalize_bg=None, normalize_ramp=False, invert=False):
         self.dev = torch.device("cuda", device)
         if isinstance(particles, np.ndarray):
             particles = torch.from_numpy(np.ascontiguousarray(particles, np.float32))
         self.particles = particles.to(self.dev, dtype=torch.float32).contiguous()
+        _prepare_particles(self.particles, normalize_bg, normalize_ramp, invert)
         self.n, self.nx = self.particles.shape[0], self.particles.shape[-1]
         self.ou = int(ou)
         self.index0 = int(index0)

@@ -328,6 +328,29 @@ int  ra_phase_flip(float *d_images, int n, int nx, const float *h_ctf, int pad, 
  * independent of the others and of its place in the batch. */
 int  ra_fourier_resize(const float *d_in, int n, int nx, int m, float *d_out, void *hip_stream);
 
+/* Particle preprocessing without an engine, in place on d_images [n][nx][nx] (device, float32); DESIGN.md section 4.17, contract:
+ * cryo_ralib_amd/prep.py.  Centre c = nx/2, u = col - c, v = row - c; every particle is independent of the others and of its
+ * place in the batch.
+ *   ra_prep_normalize  background set B = {u^2 + v^2 > bg_radius^2}.  ramp != 0: (a, b, c) = the least-squares plane of x over B
+ *                      (theta = G^-1 m, G = sum_B [1,u,v]^T [1,u,v] inverted in double on the host, m = sum_B x [1,u,v]);
+ *                      e = x - (a + b u + c v) on all pixels, theta = 0 without ramp.  mu = sum_B e / |B|, sigma^2 =
+ *                      sum_B (e - mu)^2 / |B| (two passes), y = s (e - mu) / sigma with s = -1 for invert != 0, formed in double
+ *                      and rounded to float32 once; sigma == 0 gives s (e - mu).  d_stats (may be NULL): [n][5] double
+ *                      (a, b, c, mu, sigma).  A particle with a non-finite pixel gets NaN pixels and statistics.  Every sum is
+ *                      double in an order fixed by (nx, bg_radius): no atomics, bitwise reproducible call to call and stream to
+ *                      stream.  Domain: 4 <= nx <= 1024, 1 <= bg_radius <= nx/2 (finite), ramp and invert 0 or 1.
+ *   ra_prep_filter     embed at (P - nx) / 2 in a P x P zero image (P = 2 nx with pad != 0, else nx), real 2-D DFT, multiply by
+ *                      g(d) = LP (1 - HP), d = sqrt(ix^2 + iy^2) / P cycles per pixel, inverse DFT, keep the nx x nx window: the
+ *                      passes of ra_phase_flip with g read from a table built once per call (g in double, rounded to float32).
+ *                      kind 0: absent (LP = 1, HP = 0); kind 1, tanl(fl = a, aa = b): 1/2 [tanh(k (d + fl)) - tanh(k (d - fl))],
+ *                      k = pi / (2 aa fl), 0 < fl < 1, aa > 0; kind 2, gauss(sigma = a): exp(-d^2 / (2 sigma^2)), sigma > 0.
+ *                      Domain: 2 <= nx <= 1024, pad 0 or 1, at least one of LP and HP present, finite parameters.
+ * RA_ERR_ARG, with nothing launched, for anything outside the domains, n < 0 or a null d_images with n > 0; n == 0 is a no-op.
+ * Asynchronous on hip_stream (a hipStream_t; NULL = default stream), scratch allocated and freed on that stream. */
+int  ra_prep_normalize(float *d_images, int n, int nx, double bg_radius, int ramp, int invert, double *d_stats, void *hip_stream);
+int  ra_prep_filter(float *d_images, int n, int nx, int pad, int lp_kind, double lp_a, double lp_b, int hp_kind, double hp_a,
+                    double hp_b, void *hip_stream);
+
 /* CTF-corrected (Wiener-filtered) class averages without an engine (contract: cryo_ralib_amd/wiener.py
  * wiener_reference).  Per particle i: Y_i = rfft2 of rot_shift2D(x_i) (d_params[i]: alpha, sx, sy, mirror as ra_rot_shift2d;
  * ref_id = the class) embedded at o = (P - nx) / 2 in a P x P zero image (P = 2 nx with pad = 1, nx with pad = 0); c_i = the CTF
