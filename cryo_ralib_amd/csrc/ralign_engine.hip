@@ -109,6 +109,21 @@ struct LdsRow {
     int stat, dyn, limit;          // the code object's static LDS, the dynamic LDS asked for, the device's limit per workgroup (bytes)
 };
 
+// The kernel of the particle-resident search (ra_align, ra_align_classes, ra_debug_spectra), recorded where its dynamic LDS is raised
+// (setup_fused, setup_solo) and cleared where `fused` / `solo` are, so that what is launched is what was prepared.  The two kernel
+// types differ in their last argument: const int *cls, the class of every particle (search_fused_kernel, search_tiled_kernel; null
+// outside the class-resident mode), or float *raw, the debug output of the polar stage (the solo, duo and pair kernels).
+typedef void (*fused_fn)(DevGeom, FusedGeom, const float *, const float *, int, const float *, int, CandT *, const int *);
+typedef void (*solo_fn)(DevGeom, FusedGeom, const float *, const float *, int, const float *, int, CandT *, float *);
+typedef void (*ccf_fn)(DevGeom, const float *, const float *, int, int, int, CandT *);
+struct SearchPlan {
+    fused_fn fused = nullptr;      // search_fused_kernel / search_tiled_kernel (over a crop or not) ...
+    fused_fn pack = nullptr;       // ... and search_fused_kernel's dense-offset variant where it exists: the launch picks one (pack_ok)
+    solo_fn solo = nullptr;        // or search_solo_kernel / search_duo_kernel / search_pair_kernel ...
+    solo_fn debug = nullptr;       // ... and the instantiation ra_debug_spectra runs the polar stage through
+    size_t lds = 0;                // dynamic LDS of a workgroup (FusedPlanHost::lds_bytes)
+};
+
 struct ra_engine {
     ra_config cfg{};
     std::vector<LdsRow> lds_rows;
@@ -165,7 +180,7 @@ struct ra_engine {
     bool tcrop = false;                 // generic class, but the search runs search_tiled_kernel over a CROP of the image (tcrop_wanted)
     int crop_S = 0;                     // ... whose side was planned for search shifts of up to this many pixels
     int crop_pst = 0;                   // ... and its row stride in LDS (tcrop_wanted)
-    float2 *d_zscr = nullptr;           // [g_nblk][maxrin][64 TM TR] CCF spectra scratch of ccf_generic_kernel
+    float2 *d_zscr = nullptr;           // [RA_GCCF_NWG][maxrin][64 TM TR] CCF spectra scratch of ccf_generic_kernel
     // polar stage with the image in LDS, ring zone by ring zone (ralign_zone.h); the global-tap kernel stays underneath
     ZonePlanHost zplan;
     ZonePlanDev zdev{};
@@ -179,7 +194,7 @@ struct ra_engine {
     float *d_cls_refspec = nullptr, *d_cls_Bf = nullptr;      // class-resident mode: [cls_cap][lring], [cls_cap][b_floats]
     int cls_cap = 0, cls_ready = 0;
     float *d_gcdc = nullptr;            // [nref] DC weights of the references (generic and fused paths)
-    int g_nblk = 0, g_P = 0;
+    int g_P = 0;
     size_t lds_gpolar = 0, lds_gccf = 0;
     // reference-update workspace (ralign_refine.h), allocated on first use
     int rf_cap = 0;                     // images the workspace holds
@@ -196,6 +211,8 @@ struct ra_engine {
     bool solo = false;                  // search_solo_kernel (ralign_solo.h: maxrin 512, one offset resident per pass) on top of the generic tables
     bool duo = false;                   // ... as search_duo_kernel (ralign_duo.h): two offsets per pass through the one ring buffer
     bool pair = false;                  // ... search_pair_kernel (ralign_pair.h): maxrin 256 in boxes too large for four ring buffers, two per pass
+    SearchPlan search;                  // the kernel behind those flags
+    ccf_fn ccf = nullptr;               // ccf_kernel<maxrin> of the kernel pair (LDS-resident class)
     float *d_Bf = nullptr;
     int *d_fbsrc = nullptr;
     size_t f_cap_b = 0;
@@ -246,14 +263,16 @@ static int raise_dynamic_lds(ra_engine *e, const void *fn, const char *name, siz
     return RA_OK;
 }
 
-template <typename T> static int upload(ra_engine *e, const std::vector<T> &h, const T **dptr)
+// a host table in a device buffer of its own (freed at destroy), through the typed pointer the caller keeps (P: T, const T, or a
+// vector type over T such as int4)
+template <typename T, typename P> static int upload(ra_engine *e, const std::vector<T> &h, P **dptr)
 {
     void *d = nullptr;
     size_t bytes = std::max<size_t>(h.size(), 1) * sizeof(T);
     RA_HIP(hipMalloc(&d, bytes));
     e->owned.push_back(d);
     if (!h.empty()) RA_HIP(hipMemcpy(d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    *dptr = (const T *)d;
+    *dptr = (P *)d;
     return RA_OK;
 }
 
@@ -280,7 +299,6 @@ static gpolar_fn gpolar_kernel(const ra_engine *e, bool refs)
                 : (q ? (gpolar_fn)polar_generic_kernel<false, true> : (gpolar_fn)polar_generic_kernel<false, false>);
 }
 
-typedef void (*fused_fn)(DevGeom, FusedGeom, const float *, const float *, int, const float *, int, CandT *, const int *);
 static fused_fn select_tiled(int nh, int sbuf);
 static fused_fn select_fused(int maxrin, int nref, int nzr, int sbuf, bool pack = false, bool crop = false);
 // search_tiled_kernel for an engine of the size-generic class: rings of 256 samples (ou <= 36) in a box so much larger than the rings
@@ -570,17 +588,9 @@ static int build_device_geometry(ra_engine *e, const PlanRequest &rq)
     if ((rc = upload(e, g.bin_offp, &d.bin_offp))) return rc;
     if ((rc = upload(e, g.ent_src, &d.ent_src))) return rc;
     if ((rc = upload(e, g.ent_wgt, &d.ent_wgt))) return rc;
-    {
-        const int *tmp_a;
-        if ((rc = upload(e, g.a_src, &tmp_a))) return rc;
-        d.a_src4 = reinterpret_cast<const int4 *>(tmp_a);
-    }
+    if ((rc = upload(e, g.a_src, &d.a_src4))) return rc;
     if ((rc = upload(e, g.b_src, &d.b_src))) return rc;
-    {
-        const int *tmp_p;
-        if ((rc = upload(e, g.ent_apos, &tmp_p))) return rc;
-        d.ent_apos = reinterpret_cast<const int2 *>(tmp_p);
-    }
+    if ((rc = upload(e, g.ent_apos, &d.ent_apos))) return rc;
     if ((rc = upload(e, g.bin_first, &d.bin_first))) return rc;
     // shift tables are sized for the create-time window; ra_reset_shifts rewrites them
     std::vector<float> sx(g.shift_x), sy(g.shift_y);
@@ -597,10 +607,9 @@ static int build_device_geometry(ra_engine *e, const PlanRequest &rq)
     if ((rc = upload(e, qtab, &d.qtab))) return rc;
     if ((rc = upload(e, ringinfo, &d.ringinfo))) return rc;
     if ((rc = upload(e, ringw, &d.ringw))) return rc;
-    const int *tmp_i; const float *tmp_f;
-    if ((rc = upload(e, g.ring_off, &tmp_i))) return rc; e->d_ring_off = (int *)tmp_i;
-    if ((rc = upload(e, g.numr, &tmp_i))) return rc; e->d_numr = (int *)tmp_i;
-    if ((rc = upload(e, g.wr, &tmp_f))) return rc; e->d_wr = (float *)tmp_f;
+    if ((rc = upload(e, g.ring_off, &e->d_ring_off))) return rc;
+    if ((rc = upload(e, g.numr, &e->d_numr))) return rc;
+    if ((rc = upload(e, g.wr, &e->d_wr))) return rc;
     return RA_OK;
 }
 
@@ -680,6 +689,34 @@ static bool refine_rings_global(const Geometry &g, const PlanRequest &rq)
     return refine_resident_lds(g) + RA_EXACT_STATIC_LDS > RA_LDS_PER_WORKGROUP;
 }
 
+// The block shape of the size-generic contraction (ralign_generic.h), described here and nowhere else: TM tiles of 8 particle-offsets
+// x TR tiles of 8 references per block.  2 x 2; TM x 7 when the reference tiles come in sevens (gccf_wide_blocks), the B stream then
+// read once per 8 TM particle-offsets, with TM of gccf_tm (tm: the value of RALIGN_GCCF_TM, 0 when not set) -- up to 2 in
+// ccf_generic_kernel<TM, TR>, which contracts and transforms.  split (maxrin 1024, RALIGN_GCCF_SPLIT): ccf_generic_kernel<TM, TR, true>
+// contracts a slice of blocks into the scratch and gccf_ifft_kernel<TM, TR> transforms it.
+#define RA_GCCF_NWG 512      // persistent workgroups of ccf_generic_kernel (two per CU)
+struct GccfShape {
+    int TM, TR;
+    int nwg;               // workgroups of the contraction; 4 x 7 blocks: one per CU (256 registers)
+    int nblk;              // split: blocks per slice, gccf_blocks_per_wg() to a workgroup (the scratch holds a slice)
+    size_t zscr_recs;      // the scratch: 64 TM TR spectra of maxrin / 2 + 1 bins of two values per workgroup, sized for 2 x 7 (= 4 x 7 in half
+                           // the workgroups) or for 1 x 7 (which holds 2 x 2)
+    size_t lds_ifft;       // dynamic LDS of gccf_ifft_kernel
+    long long blocks(long long n_mtile, int nrtile) const { return ((n_mtile + TM - 1) / TM) * ((nrtile + TR - 1) / TR); }
+};
+static GccfShape gccf_shape(int nrtile, int maxrin, bool split, int tm)
+{
+    const bool wide = gccf_wide_blocks(nrtile);
+    GccfShape s{};
+    s.TM = !wide ? 2 : split ? gccf_tm(nrtile, maxrin, tm) : std::min(2, gccf_tm(nrtile, maxrin, tm));
+    s.TR = wide ? 7 : 2;
+    s.nwg = s.TM >= 4 ? RA_GCCF_NWG / 2 : RA_GCCF_NWG;
+    s.nblk = s.nwg * gccf_blocks_per_wg();
+    s.zscr_recs = (size_t)RA_GCCF_NWG * (s.TM * s.TR >= 14 ? RA_GCCF_ZPAIRS_MAX : RA_GCCF_ZPAIRS_MAX / 2) * (maxrin + 2) * (maxrin == 1024 ? gccf_blocks_per_wg() : 1);
+    s.lds_ifft = ((size_t)8 * RA_IFFT3_PSTRIDE + 16 * 16 + 16 * 64) * sizeof(float2);
+    return s;
+}
+
 static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, const PlanRequest &rq, bool generic)
 {
     WorkspacePlan w{};
@@ -687,6 +724,7 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, con
     int chunk = cfg.chunk > 0 ? cfg.chunk : 8192;
     chunk = std::min((chunk + 1) & ~1, 32768);      // class_sum_kernel keeps a chunk's member list in LDS
     const int ngroup = g.nshift_pad / 4;
+    const GccfShape gs = gccf_shape(nrtile, g.maxrin, g.maxrin == 1024 && rq.sw.gccf_split, rq.sw.gccf_tm);
     {   // keep the spectra workspace of one chunk within ~12 GB (large boxes: tens of MB per particle)
         const size_t per_particle = (size_t)ngroup * a_blk * sizeof(float);
         const size_t cap = std::max<size_t>(2, ((size_t)12 << 30) / per_particle);
@@ -696,13 +734,11 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, con
         // split contraction: a chunk is walked in slices of nblk blocks, one block per workgroup, and a slice takes its time
         // whether it is full or not (341 particles = 2580 blocks of 4 x 7 tiles = 10 slices of 256 + one of 20): take the chunk
         // size, up to 64 particles below the cap, with the most particles per slice
-        const bool wide = gccf_wide_blocks(nrtile);
-        const int tm = wide ? gccf_tm(nrtile, g.maxrin, rq.sw.gccf_tm) : 2, tr = wide ? 7 : 2, nblk = (tm >= 4 ? 256 : 512) * gccf_blocks_per_wg();
         int best = chunk;
         double best_pps = 0.0;
         for (int cn = chunk; cn >= std::max(2, chunk - 64); cn -= 2) {
-            const long long n_mtile = ((long long)cn * (generic ? g.nshift : g.nshift_pad) + 7) / 8;      // (the generic class packs its entries densely)
-            const long long ntask = ((n_mtile + tm - 1) / tm) * ((nrtile + tr - 1) / tr), slices = (ntask + nblk - 1) / nblk;
+            const long long n_mtile = ((long long)cn * g.nshift + 7) / 8;      // (the generic class packs its entries densely)
+            const long long ntask = gs.blocks(n_mtile, nrtile), slices = (ntask + gs.nblk - 1) / gs.nblk;
             const double pps = (double)cn / (double)slices;
             if (pps > best_pps) { best_pps = pps; best = cn; }
         }
@@ -714,10 +750,7 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, con
     w.refspec_floats = (size_t)cfg.nref * g.lring;
     w.b_floats = (size_t)nrtile * g.LBP * 16;
     w.alscratch_floats = (size_t)chunk * g.nx * g.nx;
-    // CCF-spectra scratch of ccf_generic_kernel: 64 pairs x 7 tiles per workgroup, x 14 for the 2 x 7 blocks (gccf_tm; 4 x 7: half the workgroups)
-    const bool wide2 = generic && gccf_tm(nrtile, g.maxrin, rq.sw.gccf_tm) >= 2;
-    w.zscr_recs = generic ? (size_t)512 * (wide2 ? RA_GCCF_ZPAIRS_MAX : RA_GCCF_ZPAIRS_MAX / 2) * (g.maxrin + 2) : 0;      // + 2: N/2 + 1 bins of two values (split kernels); allocated on first use of the generic search
-    if (generic && g.maxrin == 1024) w.zscr_recs *= gccf_blocks_per_wg();
+    w.zscr_recs = generic ? gs.zscr_recs : 0;      // CCF-spectra scratch of ccf_generic_kernel, allocated on first use of the generic search
     const size_t nxh = g.nx / 2 + 1, rf_cap = 2 * (size_t)cfg.nref;
     const size_t refine = 2 * rf_cap * g.nx * nxh * sizeof(double2) + rf_cap * (nxh + 3) * sizeof(float) + (size_t)g.nx * sizeof(double2);
     const size_t tables = ((size_t)g.LBP * (8 + 16 + 2) + (size_t)g.lcirc * 4 + (size_t)g.nx * g.nx + (size_t)g.maxrin * 8 + (1 << 16)) * sizeof(float);
@@ -747,8 +780,6 @@ static WorkspacePlan plan_workspace(const Geometry &g, const ra_config &cfg, con
 
 extern "C" const char *ra_last_error(void) { return g_last_error.c_str(); }
 
-typedef void (*ccf_fn)(DevGeom, const float *, const float *, int, int, int, CandT *);
-static ccf_fn select_ccf(int maxrin);
 static ccf_fn select_ccf(int maxrin)
 {
     switch (maxrin) {
@@ -830,11 +861,8 @@ static fused_fn select_tiled(int nh, int sbuf)
 template <typename T> static int grow_upload(ra_engine *e, T **dptr, size_t *cap, const std::vector<T> &h)
 {
     if (h.size() > *cap || !*dptr) {
-        void *d = nullptr;
-        const size_t n = std::max<size_t>(h.size(), 1);
-        RA_HIP(hipMalloc(&d, n * sizeof(T)));
-        e->owned.push_back(d);
-        *dptr = (T *)d; *cap = n;
+        if (const int rc = dev_grow(e, dptr, h.size(), false)) return rc;
+        *cap = std::max<size_t>(h.size(), 1);
     }
     if (!h.empty()) RA_HIP(hipMemcpy(*dptr, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
     return RA_OK;
@@ -845,9 +873,8 @@ template <typename T> static int grow_upload(ra_engine *e, T **dptr, size_t *cap
 static bool pack_allowed() { return env_int("RALIGN_PACK", 1) != 0; }
 static bool pack_ok(const ra_engine *e)
 {
-    if (!e->fused || e->tiled || !pack_allowed()) return false;
-    if (e->geo.nshift % 4 == 0 || e->geo.nshift < 4) return false;      // (a pass holds the offsets of at most two particles)
-    return select_fused(e->geo.maxrin, e->cfg.nref, e->fplan.f.nzr, e->dg.sbuf, true, e->tcrop) != nullptr;
+    if (!e->search.pack || !pack_allowed()) return false;
+    return e->geo.nshift % 4 != 0 && e->geo.nshift >= 4;      // (a pass holds the offsets of at most two particles)
 }
 
 // the resident tables of the plan in e->fplan (fused, tiled, solo, duo, pair): the gather table of the B stream, the stream itself and
@@ -868,6 +895,7 @@ static int upload_resident_tables(ra_engine *e)
 static int setup_fused(ra_engine *e, const PlanRequest &rq)
 {
     e->fused = false; e->tiled = false;
+    e->search = SearchPlan{};
     e->fplan.f.on = 0;
     if (e->generic && !e->tcrop) return RA_OK;
     if (!rq.sw.fused) return RA_OK;
@@ -892,16 +920,17 @@ static int setup_fused(ra_engine *e, const PlanRequest &rq)
     if ((rc = upload_resident_tables(e))) return rc;
     for (int pk = 0; pk < (e->tiled ? 1 : 2); pk++) {
         const fused_fn fk = e->tiled ? select_tiled(fp.f.nh, e->dg.sbuf) : select_fused(g.maxrin, e->cfg.nref, fp.f.nzr, e->dg.sbuf, pk != 0, e->tcrop);
+        (pk ? e->search.pack : e->search.fused) = fk;
         if (!fk) continue;
         const std::string kn = std::string(e->tiled ? "search_tiled_kernel" : pk ? "search_fused_kernel<pack>" : "search_fused_kernel") + (e->tcrop ? " (crop)" : "");
         if ((rc = raise_dynamic_lds(e, (const void *)fk, kn.c_str(), fp.lds_bytes))) return rc;
     }
+    e->search.lds = fp.lds_bytes;
     if (rq.sw.info) fprintf(stderr, "libralign_hip: %s plan: %zu bytes of LDS (polar part %zu), sbuf %d, pst %d, nzr %d, rz %d\n", e->tiled ? "tiled" : "fused", fp.lds_bytes, e->lds_polar, e->dg.sbuf, e->dg.pst, fp.f.nzr, fp.f.rz);
     e->fused = true;
     return RA_OK;
 }
 
-typedef void (*solo_fn)(DevGeom, FusedGeom, const float *, const float *, int, const float *, int, CandT *, float *);
 static solo_fn select_solo(int maxrin, int nh, int ntile)
 {
     if (maxrin != 512) return nullptr;
@@ -938,6 +967,7 @@ static int plan_nqmax(const FusedGeom &f)
     return m;
 }
 
+// (profiling builds: RALIGN_DUO_NQT=16 asks for the wider slice; read when the plan is made -- setup_solo -- and at no launch)
 static solo_fn select_duo(int maxrin, int nh, int nqmax)
 {
     if (maxrin != 512) return nullptr;
@@ -965,6 +995,7 @@ static int setup_solo(ra_engine *e, const PlanRequest &rq)
     const Geometry &g = e->geo;
     FusedPlanHost &fp = e->fplan;
     if (e->fused) return RA_OK;          // tcrop: search_tiled_kernel over a crop of the image took this engine of the generic class
+    e->search = SearchPlan{};
     if (e->want.pair) {
         // maxrin 256 in a box too large for four ring buffers: two offsets per pass in two (ralign_pair.h)
         if (!build_pair_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job, rq.sw.crop, fp)) { fp.f.on = 0; return RA_OK; }
@@ -973,20 +1004,26 @@ static int setup_solo(ra_engine *e, const PlanRequest &rq)
         int rc;
         if ((rc = upload_resident_tables(e))) return rc;
         if ((rc = raise_dynamic_lds(e, (const void *)fk, "search_pair_kernel", fp.lds_bytes)) || (rc = raise_dynamic_lds(e, (const void *)search_pair_kernel<256, 1>, "search_pair_kernel<256, 1>", fp.lds_bytes))) return rc;
+        e->search.solo = fk; e->search.debug = search_pair_kernel<256, 1>; e->search.lds = fp.lds_bytes;
         if (rq.sw.info) fprintf(stderr, "libralign_hip: pair plan: %zu bytes of LDS, image %d x %d, 2 ring buffers of %d floats, %d jobs, %d tiles of 2 x %d reference pairs\n",
                                            fp.lds_bytes, fp.f.s_rows, fp.f.s_pst, fp.f.s_sbuf, e->dg.n_job, fp.f.ntile, fp.f.nrpw);
         e->solo = true; e->pair = true;
         return RA_OK;
     }
     if (!e->want.solo) return RA_OK;
-    e->duo = e->want.duo && build_duo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, rq.sw.crop, fp) && select_duo(g.maxrin, fp.f.nh, plan_nqmax(fp.f));
-    if (!e->duo && !build_solo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, rq.sw.crop, fp)) { fp.f.on = 0; return RA_OK; }
-    const solo_fn fk = e->duo ? select_duo(g.maxrin, fp.f.nh, plan_nqmax(fp.f)) : select_solo(g.maxrin, fp.f.nh, fp.f.ntile);
+    solo_fn fk = nullptr;
+    e->duo = e->want.duo && build_duo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, rq.sw.crop, fp) &&
+             (fk = select_duo(g.maxrin, fp.f.nh, plan_nqmax(fp.f)));
+    if (!e->duo) {
+        if (!build_solo_plan(g, e->cfg.nref, e->dg.n_qtab, e->dg.n_inst, e->dg.n_job + e->dg.n_job_b, rq.sw.crop, fp)) { fp.f.on = 0; return RA_OK; }
+        fk = select_solo(g.maxrin, fp.f.nh, fp.f.ntile);
+    }
     if (!fk) { fp.f.on = 0; return RA_OK; }
     int rc;
     if ((rc = upload_resident_tables(e))) return rc;
     if ((rc = raise_dynamic_lds(e, (const void *)fk, e->duo ? "search_duo_kernel" : "search_solo_kernel", fp.lds_bytes)) ||
         (rc = raise_dynamic_lds(e, (const void *)search_solo_kernel<512, 1, true>, "search_solo_kernel<512, 1, true>", fp.lds_bytes))) return rc;          // ra_debug_spectra: the polar stage through the solo kernel's debug path
+    e->search.solo = fk; e->search.debug = search_solo_kernel<512, 1, true>; e->search.lds = fp.lds_bytes;
     if (rq.sw.info) fprintf(stderr, "libralign_hip: %s plan:", e->duo ? "duo" : "solo");
     if (rq.sw.info) fprintf(stderr, " %zu bytes of LDS, image %d x %d, ring buffer %d floats, %d jobs, %d tiles of %d reference pairs\n",
                                        fp.lds_bytes, fp.f.s_rows, fp.f.s_pst, fp.f.s_sbuf, e->dg.n_job, fp.f.ntile, fp.f.nh);
@@ -1045,28 +1082,6 @@ static int update_live_mode(ra_engine *e, const PlanRequest &rq)
     return RA_OK;
 }
 
-// Polar2Dm + Normalize_ring statistics + Frngs of `cn` particles into the A blocks / d_gstats of the size-generic path
-static int launch_generic_polar(ra_engine *e, const float *part, const float *st, int cn, float *Abuf)
-{
-    const Geometry &g = e->geo;
-    if (e->dg.ent_base) {
-        hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, e->stream, e->dg, st, cn, e->d_ent_base, e->d_ent_total);
-        RA_HIP(hipGetLastError());
-    }
-    if (e->zones) {
-        hipLaunchKernelGGL(polar_zone_kernel<RA_ZONE_NW>, dim3((unsigned)cn * e->zdev.nzone * e->zdev.nchunk), dim3(64 * RA_ZONE_NW), e->zplan.lds_bytes, e->stream,
-                           e->dg, e->zdev, part, st, cn, Abuf, e->d_stats_part);
-        RA_HIP(hipGetLastError());
-        const int nent = cn * e->dg.ent_stride;
-        hipLaunchKernelGGL(polar_stats_kernel, dim3((nent + 255) / 256), dim3(256), 0, e->stream, e->dg, (const float2 *)e->d_stats_part, nent,
-                           e->zdev.nquad_total, e->d_gstats);
-    } else
-        hipLaunchKernelGGL(gpolar_kernel(e, false), dim3((unsigned)(((long long)cn * e->dg.ent_stride + 3) / 4)), dim3(RA_GEN_THREADS), e->lds_gpolar, e->stream, e->dg,
-                           part, st, cn, Abuf, e->d_gstats);
-    RA_HIP(hipGetLastError());
-    return RA_OK;
-}
-
 // tables and buffers of the sub-bin angle refinement (ralign_exact.h): twiddles (float) of the double-precision cos / sin for
 // every power-of-two length, as fftr_q's tables; exact reference spectra; the list of flagged particles of a chunk
 static int setup_refine(ra_engine *e, const PlanRequest &rq)
@@ -1104,10 +1119,8 @@ static int setup_refine(ra_engine *e, const PlanRequest &rq)
             tw.push_back((float)cos(a)); tw.push_back((float)sin(a));
         }
     }
-    const float *dtw = nullptr; const int *doff = nullptr;
     int rc;
-    if ((rc = upload(e, tw, &dtw)) || (rc = upload(e, off, &doff))) return rc;
-    e->d_twx = (float *)dtw; e->d_twxoff = (int *)doff;
+    if ((rc = upload(e, tw, &e->d_twx)) || (rc = upload(e, off, &e->d_twxoff))) return rc;
     if ((rc = dev_alloc(e, &e->d_refx, (size_t)e->cfg.nref * g.lcirc, true)) ||
         (rc = dev_alloc(e, &e->d_rlist, (size_t)e->chunk, false)) || (e->rlist_cap = e->chunk, 0) ||
         (rc = dev_alloc(e, &e->d_rcount, 1, true)) ||
@@ -1120,6 +1133,17 @@ static int setup_refine(ra_engine *e, const PlanRequest &rq)
         if ((rc = RA_LDS(e, refine_winner_kernel<false>, e->lds_refine)) || (rc = RA_LDS(e, refspec_exact_kernel<false>, e->lds_refine))) return rc;
     }
     e->refine_ok = true;
+    return RA_OK;
+}
+
+// refine_winner_kernel over the refine list of cn particles, one image per workgroup (ring buffers in LDS, or -- refine_gm -- in the
+// global scratch: setup_refine)
+static int launch_refine_winner(ra_engine *e, int cn, float *st, ra_result *res, const float *part, const float *refx, const int *cls)
+{
+    const auto k = e->refine_gm ? refine_winner_kernel<true> : refine_winner_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(std::min(cn, e->refine_grid)), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr, (const float *)e->d_twx,
+                       (const int *)e->d_twxoff, part, refx, (const RefineRec *)e->d_rlist, (const int *)e->d_rcount, res, cls, st, e->d_rscratch);
+    RA_HIP(hipGetLastError());
     return RA_OK;
 }
 
@@ -1143,18 +1167,7 @@ static int finalize_and_refine(ra_engine *e, const CandT *cand, int nrtile, int 
                            refine ? e->d_rlist : (RefineRec *)nullptr, e->d_rcount, e->refine_thr, p_base);
     RA_HIP(hipGetLastError());
     }
-    if (refine && deferred != 1) {
-        const int grid = std::min(cn, e->refine_grid);
-        if (e->refine_gm)
-            hipLaunchKernelGGL(refine_winner_kernel<true>, dim3(grid), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr,
-                               (const float *)e->d_twx, (const int *)e->d_twxoff, part, refx, (const RefineRec *)e->d_rlist, (const int *)e->d_rcount,
-                               res, cls, st, e->d_rscratch);
-        else
-            hipLaunchKernelGGL(refine_winner_kernel<false>, dim3(grid), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr,
-                               (const float *)e->d_twx, (const int *)e->d_twxoff, part, refx, (const RefineRec *)e->d_rlist, (const int *)e->d_rcount,
-                               res, cls, st, (float *)nullptr);
-        RA_HIP(hipGetLastError());
-    }
+    if (refine && deferred != 1) return launch_refine_winner(e, cn, st, res, part, refx, cls);
     return RA_OK;
 }
 
@@ -1193,7 +1206,6 @@ static int ensure_unfused_ws(ra_engine *e)
 
 // the LDS-resident kernels cover <= 48 rings of 8..256 samples and images whose padded copy plus four ring buffers
 // fit one CU's LDS; everything else runs the size-generic kernels
-static ccf_fn select_ccf(int maxrin);
 static bool fits_specialised_kernels(const Geometry &g0, const ra_config &cfg, const PlanRequest &rq)
 {
     bool fast = g0.nring <= 4 * RA_CCF_MAXNS && select_ccf(g0.maxrin) != nullptr && g0.numr[2] >= 8;
@@ -1325,7 +1337,8 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
     if (!e->generic) {
         if (!rc) rc = RA_LDS(e, polar_fft_kernel, e->lds_polar);
         if (!rc) rc = RA_LDS(e, ref_polar_fft_kernel, e->lds_ref);
-        if (!rc) rc = raise_dynamic_lds(e, (const void *)select_ccf(g.maxrin), "ccf_kernel", e->lds_ccf);
+        e->ccf = select_ccf(g.maxrin);
+        if (!rc) rc = raise_dynamic_lds(e, (const void *)e->ccf, "ccf_kernel", e->lds_ccf);
     } else {
         if (!rc) rc = raise_dynamic_lds(e, (const void *)gpolar_kernel(e, false), "polar_generic_kernel<false>", e->lds_gpolar);
         if (!rc) rc = raise_dynamic_lds(e, (const void *)gpolar_kernel(e, true), "polar_generic_kernel<true>", e->lds_gpolar);
@@ -1333,7 +1346,7 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
         if (!rc) rc = raise_dynamic_lds(e, (const void *)ccf_generic_kernel<1, 7>, "ccf_generic_kernel<1, 7>", e->lds_gccf);
         if (!rc) rc = raise_dynamic_lds(e, (const void *)ccf_generic_kernel<2, 7>, "ccf_generic_kernel<2, 7>", e->lds_gccf);
         if (g.maxrin == 1024) {
-            const size_t lds2 = ((size_t)8 * RA_IFFT3_PSTRIDE + 16 * 16 + 16 * 64) * sizeof(float2);
+            const size_t lds2 = gccf_shape(e->nrtile, g.maxrin, true, 0).lds_ifft;
             if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<1, 7>, "gccf_ifft_kernel<1, 7>", lds2);
             if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<2, 2>, "gccf_ifft_kernel<2, 2>", lds2);
             if (!rc) rc = raise_dynamic_lds(e, (const void *)gccf_ifft_kernel<2, 7>, "gccf_ifft_kernel<2, 7>", lds2);
@@ -1358,7 +1371,6 @@ static int create_engine(ra_engine **out, const ra_config *cfg, const ra_options
     }
     e->fcand_cap = wp.chunk;
     if (e->generic) {
-        e->g_nblk = 512;       // persistent workgroups of ccf_generic_kernel (two per CU)
         if ((rc = dev_alloc(e, &e->d_gstats, (size_t)wp.chunk * g.nshift_pad + 8, true)) ||
             (rc = dev_alloc(e, &e->d_gcdc, (size_t)cfg->nref, true))) { ra_destroy(e); return rc; }
     }
@@ -1512,6 +1524,22 @@ extern "C" int ra_reset_shifts(ra_engine *e, float xrng, float yrng, float step)
     return rc;
 }
 
+// refspec_exact_kernel: the spectra of `count` images with the CPU path's arithmetic into out [count][lcirc]; with global ring buffers (refine_gm)
+// as many images per launch as the scratch has blocks
+static int launch_refspec_exact(ra_engine *e, const float *d_imgs, int count, float *out)
+{
+    const auto k = e->refine_gm ? refspec_exact_kernel<true> : refspec_exact_kernel<false>;
+    const int cap = e->refine_gm ? std::max(e->refine_grid, e->cfg.nref) : count;
+    for (int c0 = 0; c0 < count; c0 += cap) {
+        const int cnt = std::min(cap, count - c0);
+        hipLaunchKernelGGL(k, dim3(cnt), dim3(RA_EXACT_THREADS), e->refine_gm ? 0 : e->lds_refine, e->stream, e->dg, (const int *)e->d_numr, (const float *)e->d_wr,
+                           (const float *)e->d_twx, (const int *)e->d_twxoff, d_imgs + (size_t)c0 * e->geo.nx * e->geo.nx, cnt, out + (size_t)c0 * e->geo.lcirc,
+                           e->d_rscratch);
+    }
+    RA_HIP(hipGetLastError());
+    return RA_OK;
+}
+
 extern "C" int ra_set_references(ra_engine *e, const float *d_refs)
 {
     if (!e || !d_refs) { g_last_error = "null argument"; return RA_ERR_ARG; }
@@ -1536,13 +1564,7 @@ extern "C" int ra_set_references(ra_engine *e, const float *d_refs)
         }
     }
     if (e->refine_ok && e->refine_thr != 0.f) {        // the same references with the CPU path's arithmetic, for the sub-bin angle refinement
-        if (e->refine_gm)
-            hipLaunchKernelGGL(refspec_exact_kernel<true>, dim3(e->cfg.nref), dim3(RA_EXACT_THREADS), 0, e->stream, e->dg, (const int *)e->d_numr,
-                               (const float *)e->d_wr, (const float *)e->d_twx, (const int *)e->d_twxoff, d_refs, e->cfg.nref, e->d_refx, e->d_rscratch);
-        else
-            hipLaunchKernelGGL(refspec_exact_kernel<false>, dim3(e->cfg.nref), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr,
-                               (const float *)e->d_wr, (const float *)e->d_twx, (const int *)e->d_twxoff, d_refs, e->cfg.nref, e->d_refx, (float *)nullptr);
-        RA_HIP(hipGetLastError());
+        if (const int rc = launch_refspec_exact(e, d_refs, e->cfg.nref, e->d_refx)) return rc;      // (one launch: the scratch holds nref images)
         // copies of a reference inside the stack: their CCFs are equal to the bit and the CPU scan alone decides among them
         hipLaunchKernelGGL(ref_hash_kernel, dim3(e->cfg.nref), dim3(256), 0, e->stream, (const float *)e->d_refx, g.lcirc, e->d_refhash);
         hipLaunchKernelGGL(ref_groups_kernel, dim3(1), dim3(256), 0, e->stream, (const float *)e->d_refx, g.lcirc, e->cfg.nref,
@@ -1582,6 +1604,93 @@ static std::pair<hipEvent_t, hipEvent_t> *next_events(std::vector<std::pair<hipE
         pool.push_back({a, b});
     }
     return &pool[used++];
+}
+
+// The particle-resident search of n particles with the engine's stored kernel (solo, duo, pair, fused or tiled, over a crop or not,
+// class-resident): launches of up to resident_batch particles -- a launch stays a bounded unit of work (timing, candidate
+// workspace) -- with one persistent workgroup per CU (its LDS plan fills the CU) that walks over its share, each followed by its
+// finalize and refine.  f: the plan's geometry as this launch wants it (FusedGeom::pack); pack: search_fused_kernel's dense-offset
+// variant (pack_ok); B / nref_b: the reference stream and the references in one stream; refx: their exact spectra; d_cls: the class
+// of every particle, one stream per class (ra_align_classes), or null
+static int resident_search(ra_engine *e, const FusedGeom &f, bool pack, const float *B, int nref_b, const float *refx, const float *d_particles,
+                           int n, float *d_state, ra_result *d_result, const int *d_cls)
+{
+    const SearchPlan &sp = e->search;
+    const int npix = e->geo.nx * e->geo.nx, rch = resident_batch(e, n);
+    if (const int rc = ensure_resident_ws(e, rch)) return rc;
+    for (int start = 0; start < n; start += rch) {
+        const int cn = std::min(rch, n - start);
+        const float *part = d_particles + (size_t)start * npix;
+        float *st = d_state + (size_t)start * 2;
+        const int *cls = d_cls ? d_cls + start : nullptr;
+        const dim3 grid(std::min(cn, e->n_cu)), block(RF_THREADS);
+        std::pair<hipEvent_t, hipEvent_t> *evc = e->timing ? next_events(e->ev_ccf, e->ev_used_ccf) : nullptr;
+        if (evc) RA_HIP(hipEventRecord(evc->first, e->stream));
+        if (sp.solo)
+            hipLaunchKernelGGL(sp.solo, grid, block, sp.lds, e->stream, e->dg, f, part, (const float *)st, cn, B, nref_b, e->d_fcand, (float *)nullptr);
+        else
+            hipLaunchKernelGGL(pack ? sp.pack : sp.fused, grid, block, sp.lds, e->stream, e->dg, f, part, (const float *)st, cn, B, nref_b, e->d_fcand, cls);
+        RA_HIP(hipGetLastError());
+        if (evc) RA_HIP(hipEventRecord(evc->second, e->stream));
+        if (const int rc = finalize_and_refine(e, e->d_fcand, 1, cn, st, d_result + start, part, refx, cls)) return rc;
+    }
+    return RA_OK;
+}
+
+// Polar2Dm + Normalize_ring statistics + Frngs of `cn` particles into the A blocks / d_gstats of the size-generic path
+static int launch_generic_polar(ra_engine *e, const float *part, const float *st, int cn, float *Abuf)
+{
+    const Geometry &g = e->geo;
+    if (e->dg.ent_base) {
+        hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, e->stream, e->dg, st, cn, e->d_ent_base, e->d_ent_total);
+        RA_HIP(hipGetLastError());
+    }
+    if (e->zones) {
+        hipLaunchKernelGGL(polar_zone_kernel<RA_ZONE_NW>, dim3((unsigned)cn * e->zdev.nzone * e->zdev.nchunk), dim3(64 * RA_ZONE_NW), e->zplan.lds_bytes, e->stream,
+                           e->dg, e->zdev, part, st, cn, Abuf, e->d_stats_part);
+        RA_HIP(hipGetLastError());
+        const int nent = cn * e->dg.ent_stride;
+        hipLaunchKernelGGL(polar_stats_kernel, dim3((nent + 255) / 256), dim3(256), 0, e->stream, e->dg, (const float2 *)e->d_stats_part, nent,
+                           e->zdev.nquad_total, e->d_gstats);
+    } else
+        hipLaunchKernelGGL(gpolar_kernel(e, false), dim3((unsigned)(((long long)cn * e->dg.ent_stride + 3) / 4)), dim3(RA_GEN_THREADS), e->lds_gpolar, e->stream, e->dg,
+                           part, st, cn, Abuf, e->d_gstats);
+    RA_HIP(hipGetLastError());
+    return RA_OK;
+}
+
+// Crosrng_ms of n_mtile tiles of 8 particle-offsets against every reference tile, best reference per tile to Cbuf (the size-generic
+// path).  split / tm: RALIGN_GCCF_SPLIT at maxrin 1024 and RALIGN_GCCF_TM, as the caller reads them at the launch (gccf_shape)
+static int launch_contraction(ra_engine *e, const float *Abuf, CandT *Cbuf, int n_mtile, bool split, int tm)
+{
+    const GccfShape gs = gccf_shape(e->nrtile, e->geo.maxrin, split, tm);
+    hipStream_t sp = e->stream;
+    if (!split) {
+        const auto k = gs.TR == 2 ? ccf_generic_kernel<2, 2> : gs.TM == 2 ? ccf_generic_kernel<2, 7> : ccf_generic_kernel<1, 7>;
+        hipLaunchKernelGGL(k, dim3(std::min((n_mtile + gs.TM - 1) / gs.TM, gs.nwg)), dim3(RA_GCCF_THREADS), e->lds_gccf, sp, e->dg, Abuf, (const float *)e->d_B,
+                           n_mtile, e->nrtile, e->cfg.nref, Cbuf, e->d_zscr, e->g_P, (const float2 *)e->d_gstats, (const float *)e->d_gcdc, 0, 0);
+        RA_HIP(hipGetLastError());
+        return RA_OK;
+    }
+    // contraction and inverse transforms as two kernels per slice of nblk blocks (the scratch holds one slice)
+    const int ntask = (int)gs.blocks(n_mtile, e->nrtile);
+    auto launch = [&](auto ccfk, auto ifftk, int task0, int nt, int grid2) {
+        hipLaunchKernelGGL(ccfk, dim3(std::min(nt, gs.nwg)), dim3(RA_EXP_ENV("RALIGN_GCCF_WAVES") ? 64 * std::max(1, std::min(8, ra_atoi(RA_EXP_ENV("RALIGN_GCCF_WAVES")))) : RA_GCCF_THREADS), 0, sp, e->dg, Abuf, e->d_B, n_mtile, e->nrtile, e->cfg.nref, Cbuf,
+                           e->d_zscr, e->g_P, (const float2 *)e->d_gstats, (const float *)e->d_gcdc, task0, nt);
+        if (!(e->dg.dbg & 1))          // (profiling builds, RALIGN_DEBUG=1: the contraction alone)
+        hipLaunchKernelGGL(ifftk, dim3(grid2), dim3(RA_GCCF_THREADS), gs.lds_ifft, sp, e->dg, n_mtile, e->nrtile, e->cfg.nref, Cbuf,
+                           (const float2 *)e->d_zscr, (const float2 *)e->d_gstats, task0, nt);
+    };
+    for (int task0 = 0; task0 < ntask; task0 += gs.nblk) {
+        const int nt = std::min(gs.nblk, ntask - task0);
+        const int grid2 = std::min(nt * gs.TM * gs.TR * 8, (RA_EXP_ENV("RALIGN_IFFT_WGS") ? ra_atoi(RA_EXP_ENV("RALIGN_IFFT_WGS")) : 2) * e->n_cu);
+        if (gs.TM == 4) launch(ccf_generic_kernel<4, 7, true>, gccf_ifft_kernel<4, 7>, task0, nt, grid2);
+        else if (gs.TR == 7 && gs.TM == 2) launch(ccf_generic_kernel<2, 7, true>, gccf_ifft_kernel<2, 7>, task0, nt, grid2);
+        else if (gs.TR == 7) launch(ccf_generic_kernel<1, 7, true>, gccf_ifft_kernel<1, 7>, task0, nt, grid2);
+        else launch(ccf_generic_kernel<2, 2, true>, gccf_ifft_kernel<2, 2>, task0, nt, grid2);
+        RA_HIP(hipGetLastError());
+    }
+    return RA_OK;
 }
 
 // average-centre correction of ali2d_single_iter: d += R(-alpha) M cs using the previous
@@ -1686,7 +1795,6 @@ extern "C" int ra_set_class_references(ra_engine *e, const float *d_refs, int nc
     if (!e || !d_refs || ncls <= 0) { g_last_error = "null argument"; return RA_ERR_ARG; }
     if (!e->fused || e->tiled || e->generic || e->cfg.nref != 1 || e->cfg.mode != RA_MODE_REFFREE) { g_last_error = "class-resident launch needs the fused kernel with one reference (and a box its reference preparation holds in LDS)"; return RA_ERR_STATE; }
     const FusedGeom f = e->fplan.f;
-    int rc;
     if (ncls > e->cls_cap) {
         if (e->d_cls_refspec) (void)hipFree(e->d_cls_refspec);
         if (e->d_cls_Bf) (void)hipFree(e->d_cls_Bf);
@@ -1701,25 +1809,13 @@ extern "C" int ra_set_class_references(ra_engine *e, const float *d_refs, int nc
         }
         e->cls_cap = ncls;
     }
-    (void)rc;
     hipLaunchKernelGGL(ref_polar_fft_kernel, dim3(ncls), dim3(256), e->lds_ref, e->stream, e->dg, d_refs, ncls, e->d_cls_refspec);
     RA_HIP(hipGetLastError());
     hipLaunchKernelGGL(pack_refs_fused_kernel, dim3(std::min(64, (f.b_floats + 255) / 256), ncls), dim3(256), 0, e->stream, e->dg, f,
                        (const float *)e->d_cls_refspec, 1, e->d_cls_Bf);
     RA_HIP(hipGetLastError());
     if (e->refine_ok && e->refine_thr != 0.f && e->d_cls_refx) {
-        if (e->refine_gm) {          // ring buffers in global scratch: as many classes per launch as the scratch has blocks (setup_refine)
-            const int cap = std::max(e->refine_grid, e->cfg.nref);
-            for (int c0 = 0; c0 < ncls; c0 += cap) {
-                const int cnt = std::min(cap, ncls - c0);
-                hipLaunchKernelGGL(refspec_exact_kernel<true>, dim3(cnt), dim3(RA_EXACT_THREADS), 0, e->stream, e->dg, (const int *)e->d_numr,
-                                   (const float *)e->d_wr, (const float *)e->d_twx, (const int *)e->d_twxoff, d_refs + (size_t)c0 * e->geo.nx * e->geo.nx, cnt,
-                                   e->d_cls_refx + (size_t)c0 * e->geo.lcirc, e->d_rscratch);
-            }
-        } else
-            hipLaunchKernelGGL(refspec_exact_kernel<false>, dim3(ncls), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr,
-                               (const float *)e->d_wr, (const float *)e->d_twx, (const int *)e->d_twxoff, d_refs, ncls, e->d_cls_refx, (float *)nullptr);
-        RA_HIP(hipGetLastError());
+        if (const int rc = launch_refspec_exact(e, d_refs, ncls, e->d_cls_refx)) return rc;
     }
     e->cls_ready = ncls;
     return RA_OK;
@@ -1732,25 +1828,7 @@ extern "C" int ra_align_classes(ra_engine *e, const float *d_particles, int n, f
     if (n == 0) return RA_OK;
     if (!d_particles || !d_state || !d_result || !d_cls) { g_last_error = "null argument"; return RA_ERR_ARG; }
     if (!e->fused || e->tiled || e->generic || e->cfg.nref != 1 || e->cls_ready <= 0) { g_last_error = "ra_set_class_references has not been called"; return RA_ERR_STATE; }
-    const Geometry &g = e->geo;
-    const int npix = g.nx * g.nx;
-    const FusedGeom f = e->fplan.f;
-    fused_fn fk = select_fused(g.maxrin, 1, f.nzr, e->dg.sbuf);
-    const int rch = resident_batch(e, n);
-    {
-        int rcw = ensure_resident_ws(e, rch);
-        if (rcw) return rcw;
-    }
-    for (int start = 0; start < n; start += rch) {
-        const int cn = std::min(rch, n - start);
-        float *st = d_state + (size_t)start * 2;
-        hipLaunchKernelGGL(fk, dim3(std::min(cn, e->n_cu)), dim3(RF_THREADS), e->fplan.lds_bytes, e->stream, e->dg, f,
-                           d_particles + (size_t)start * npix, (const float *)st, cn, (const float *)e->d_cls_Bf, 1, e->d_fcand, d_cls + start);
-        RA_HIP(hipGetLastError());
-        int rcf = finalize_and_refine(e, e->d_fcand, 1, cn, st, d_result + start, d_particles + (size_t)start * npix, e->d_cls_refx, d_cls + start);
-        if (rcf) return rcf;
-    }
-    return RA_OK;
+    return resident_search(e, e->fplan.f, false, e->d_cls_Bf, 1, e->d_cls_refx, d_particles, n, d_state, d_result, d_cls);
 }
 
 extern "C" int ra_align(ra_engine *e, const float *d_particles, int n, float *d_state, ra_result *d_result,
@@ -1762,63 +1840,17 @@ extern "C" int ra_align(ra_engine *e, const float *d_particles, int n, float *d_
     if (!e->refs_ready) { g_last_error = "ra_set_references has not been called"; return RA_ERR_STATE; }
     const Geometry &g = e->geo;
     const int npix = g.nx * g.nx;
-    const int ngroup = g.nshift_pad / 4;
-    ccf_fn ccf = e->generic ? nullptr : select_ccf(g.maxrin);
     if (cs && (cs[0] != 0.f || cs[1] != 0.f)) {
         RA_HIP(hipMemcpyAsync(e->d_cs, cs, 2 * sizeof(float), hipMemcpyHostToDevice, e->stream));
         hipLaunchKernelGGL(apply_cs_kernel, dim3((n + 255) / 256), dim3(256), 0, e->stream, n, e->d_cs, d_result, d_state);
         RA_HIP(hipGetLastError());
     }
     hipStream_t sp = e->stream;
-    if (e->solo) {
-        // particle-resident search, one offset resident per pass (ralign_solo.h): one persistent workgroup per CU
-        const FusedGeom f = e->fplan.f;
-        const solo_fn fk = e->pair ? select_pair(g.maxrin, f.nrpw) : e->duo ? select_duo(g.maxrin, f.nh, plan_nqmax(f)) : select_solo(g.maxrin, f.nh, f.ntile);
-        const int rch = resident_batch(e, n);
-        {
-            int rcw = ensure_resident_ws(e, rch);
-            if (rcw) return rcw;
-        }
-        for (int start = 0; start < n; start += rch) {
-            const int cn = std::min(rch, n - start);
-            float *st = d_state + (size_t)start * 2;
-            std::pair<hipEvent_t, hipEvent_t> *evc = e->timing ? next_events(e->ev_ccf, e->ev_used_ccf) : nullptr;
-            if (evc) RA_HIP(hipEventRecord(evc->first, sp));
-            hipLaunchKernelGGL(fk, dim3(std::min(cn, e->n_cu)), dim3(RF_THREADS), e->fplan.lds_bytes, sp, e->dg, f, d_particles + (size_t)start * npix,
-                               (const float *)st, cn, (const float *)e->d_Bf, e->cfg.nref, e->d_fcand, (float *)nullptr);
-            RA_HIP(hipGetLastError());
-            if (evc) RA_HIP(hipEventRecord(evc->second, sp));
-            int rcf = finalize_and_refine(e, e->d_fcand, 1, cn, st, d_result + start, d_particles + (size_t)start * npix, e->d_refx, nullptr);
-            if (rcf) return rcf;
-        }
-        return RA_OK;
-    }
-    if (e->fused) {
-        // particle-resident search: one workgroup per particle, spectra stay on the CU; launched per chunk so that a
-        // launch stays a bounded unit of work (timing, candidate workspace)
+    if (e->solo || e->fused) {
         FusedGeom f = e->fplan.f;
         // dense offset stream: a template parameter of search_fused_kernel, a run-time flag of search_tiled_kernel (RALIGN_PACK=0: off)
         f.pack = e->tiled && g.nshift % 4 != 0 && g.nshift >= 4 && pack_allowed();
-        fused_fn fk = e->tiled ? select_tiled(f.nh, e->dg.sbuf) : select_fused(g.maxrin, e->cfg.nref, e->fplan.f.nzr, e->dg.sbuf, pack_ok(e), e->tcrop);
-        const int rch = resident_batch(e, n);
-        {
-            int rcw = ensure_resident_ws(e, rch);
-            if (rcw) return rcw;
-        }
-        for (int start = 0; start < n; start += rch) {
-            const int cn = std::min(rch, n - start);
-            float *st = d_state + (size_t)start * 2;
-            std::pair<hipEvent_t, hipEvent_t> *evc = e->timing ? next_events(e->ev_ccf, e->ev_used_ccf) : nullptr;
-            if (evc) RA_HIP(hipEventRecord(evc->first, sp));
-            // one workgroup per CU (its LDS plan fills the CU); each walks over its share of the chunk
-            hipLaunchKernelGGL(fk, dim3(std::min(cn, e->n_cu)), dim3(RF_THREADS), e->fplan.lds_bytes, sp, e->dg, f, d_particles + (size_t)start * npix,
-                               (const float *)st, cn, (const float *)e->d_Bf, e->cfg.nref, e->d_fcand, (const int *)nullptr);
-            RA_HIP(hipGetLastError());
-            if (evc) RA_HIP(hipEventRecord(evc->second, sp));
-            int rcf = finalize_and_refine(e, e->d_fcand, 1, cn, st, d_result + start, d_particles + (size_t)start * npix, e->d_refx, nullptr);
-            if (rcf) return rcf;
-        }
-        return RA_OK;
+        return resident_search(e, f, pack_ok(e), e->d_Bf, e->cfg.nref, e->d_refx, d_particles, n, d_state, d_result, nullptr);
     }
     {
         int rcw = ensure_unfused_ws(e);
@@ -1855,49 +1887,11 @@ extern "C" int ra_align(ra_engine *e, const float *d_particles, int n, float *d_
         if (evp) RA_HIP(hipEventRecord(evp->second, sp));
         const int n_mtile = (cn * e->dg.ent_stride + 7) / 8;
         if (evc) RA_HIP(hipEventRecord(evc->first, sp));
-        // blocks of TM x 7 tiles when the reference tiles come in sevens (gccf_tm): the B stream is read once per 8 TM particle-offsets
-        const bool split = e->generic && g.maxrin == 1024 && env_int("RALIGN_GCCF_SPLIT", 1) != 0;
-        const int tmv = e->generic ? gccf_tm(e->nrtile, g.maxrin, env_int("RALIGN_GCCF_TM", 0)) : 1;
-        const bool tm2 = tmv >= 2 && gccf_wide_blocks(e->nrtile);
-        if (tm2 && !split)
-            hipLaunchKernelGGL((ccf_generic_kernel<2, 7>), dim3(std::min((n_mtile + 1) / 2, e->g_nblk)), dim3(RA_GCCF_THREADS), e->lds_gccf, sp, e->dg,
-                               Abuf, e->d_B, n_mtile, e->nrtile, e->cfg.nref, Cbuf, e->d_zscr, e->g_P, (const float2 *)e->d_gstats,
-                               (const float *)e->d_gcdc);
-        else if (split) {
-            // maxrin 1024: contraction and inverse transforms as two kernels per slice of g_nblk blocks (the scratch holds one slice)
-            const bool wide = gccf_wide_blocks(e->nrtile);
-            const int TMv = wide ? tmv : 2, TRv = wide ? 7 : 2;
-            const int n_mt2 = (n_mtile + TMv - 1) / TMv, n_rt2 = (e->nrtile + TRv - 1) / TRv, ntask = n_mt2 * n_rt2;
-            const size_t lds2 = ((size_t)8 * RA_IFFT3_PSTRIDE + 16 * 16 + 16 * 64) * sizeof(float2);
-            const int nwg = TMv >= 4 ? e->g_nblk / 2 : e->g_nblk;           // 4 x 7 blocks: one workgroup per CU (256 registers)
-            const int nblk = nwg * gccf_blocks_per_wg();                    // blocks per slice (the scratch holds them)
-            auto launch = [&](auto ccfk, auto ifftk, int task0, int nt, int grid2) {
-                hipLaunchKernelGGL(ccfk, dim3(std::min(nt, nwg)), dim3(RA_EXP_ENV("RALIGN_GCCF_WAVES") ? 64 * std::max(1, std::min(8, ra_atoi(RA_EXP_ENV("RALIGN_GCCF_WAVES")))) : RA_GCCF_THREADS), 0, sp, e->dg, Abuf, e->d_B, n_mtile, e->nrtile, e->cfg.nref, Cbuf,
-                                   e->d_zscr, e->g_P, (const float2 *)e->d_gstats, (const float *)e->d_gcdc, task0, nt);
-                if (!(e->dg.dbg & 1))          // (profiling builds, RALIGN_DEBUG=1: the contraction alone)
-                hipLaunchKernelGGL(ifftk, dim3(grid2), dim3(RA_GCCF_THREADS), lds2, sp, e->dg, n_mtile, e->nrtile, e->cfg.nref, Cbuf,
-                                   (const float2 *)e->d_zscr, (const float2 *)e->d_gstats, task0, nt);
-            };
-            for (int task0 = 0; task0 < ntask; task0 += nblk) {
-                const int nt = std::min(nblk, ntask - task0);
-                const int grid2 = std::min(nt * TMv * TRv * 8, (RA_EXP_ENV("RALIGN_IFFT_WGS") ? ra_atoi(RA_EXP_ENV("RALIGN_IFFT_WGS")) : 2) * e->n_cu);
-                if (wide && TMv == 4) launch(ccf_generic_kernel<4, 7, true>, gccf_ifft_kernel<4, 7>, task0, nt, grid2);
-                else if (wide && TMv == 2) launch(ccf_generic_kernel<2, 7, true>, gccf_ifft_kernel<2, 7>, task0, nt, grid2);
-                else if (wide) launch(ccf_generic_kernel<1, 7, true>, gccf_ifft_kernel<1, 7>, task0, nt, grid2);
-                else launch(ccf_generic_kernel<2, 2, true>, gccf_ifft_kernel<2, 2>, task0, nt, grid2);
-                RA_HIP(hipGetLastError());
-            }
-        }
-        else if (e->generic && gccf_wide_blocks(e->nrtile))
-            hipLaunchKernelGGL((ccf_generic_kernel<1, 7>), dim3(std::min(n_mtile, e->g_nblk)), dim3(RA_GCCF_THREADS), e->lds_gccf, sp, e->dg,
-                               Abuf, e->d_B, n_mtile, e->nrtile, e->cfg.nref, Cbuf, e->d_zscr, e->g_P, (const float2 *)e->d_gstats,
-                               (const float *)e->d_gcdc);
-        else if (e->generic)
-            hipLaunchKernelGGL((ccf_generic_kernel<2, 2>), dim3(std::min((n_mtile + 1) / 2, e->g_nblk)), dim3(RA_GCCF_THREADS), e->lds_gccf, sp, e->dg,
-                               Abuf, e->d_B, n_mtile, e->nrtile, e->cfg.nref, Cbuf, e->d_zscr, e->g_P, (const float2 *)e->d_gstats,
-                               (const float *)e->d_gcdc);
-        else
-            hipLaunchKernelGGL(ccf, dim3(n_mtile), dim3(RA_CCF_THREADS), e->lds_ccf, sp, e->dg, Abuf, e->d_B, n_mtile,
+        if (e->generic) {          // (the block shape's switches are read at the launch)
+            int rcc = launch_contraction(e, Abuf, Cbuf, n_mtile, g.maxrin == 1024 && env_int("RALIGN_GCCF_SPLIT", 1) != 0, env_int("RALIGN_GCCF_TM", 0));
+            if (rcc) return rcc;
+        } else
+            hipLaunchKernelGGL(e->ccf, dim3(n_mtile), dim3(RA_CCF_THREADS), e->lds_ccf, sp, e->dg, Abuf, e->d_B, n_mtile,
                                e->nrtile, e->cfg.nref, Cbuf);
         RA_HIP(hipGetLastError());
         if (evc) RA_HIP(hipEventRecord(evc->second, sp));
@@ -1908,7 +1902,6 @@ extern "C" int ra_align(ra_engine *e, const float *d_particles, int n, float *d_
         int rcf = finalize_and_refine(e, nullptr, e->nrtile, n, d_state, d_result, d_particles, e->d_refx, nullptr, 2, 0);
         if (rcf) return rcf;
     }
-    (void)ngroup;
     return RA_OK;
 }
 
@@ -1916,7 +1909,7 @@ extern "C" int ra_debug_spectra(ra_engine *e, const float *d_particles, int n, c
 {
     if (!e || !d_particles || !d_state || !h_out || n < 1 || n > e->chunk) { g_last_error = "bad argument"; return RA_ERR_ARG; }
     const Geometry &g = e->geo;
-    if (e->solo) {
+    if (e->search.debug) {
         // the polar stage of search_solo_kernel: ring buffer and statistics of every in-window (particle, offset)
         const size_t rawcnt = (size_t)n * g.nshift * (g.lring + 2), cnt = (size_t)n * g.nshift * g.lcirc;
         float *d_raw = nullptr, *d_out = nullptr;
@@ -1925,8 +1918,7 @@ extern "C" int ra_debug_spectra(ra_engine *e, const float *d_particles, int n, c
         if (he == hipSuccess) he = hipMemsetAsync(d_raw, 0, rawcnt * sizeof(float), e->stream);
         if (he == hipSuccess) {
             const FusedGeom f = e->fplan.f;
-            const solo_fn dk = e->pair ? (solo_fn)search_pair_kernel<256, 1> : (solo_fn)search_solo_kernel<512, 1, true>;
-            hipLaunchKernelGGL(dk, dim3(std::min(n, e->n_cu)), dim3(RF_THREADS), e->fplan.lds_bytes, e->stream, e->dg, f, d_particles,
+            hipLaunchKernelGGL(e->search.debug, dim3(std::min(n, e->n_cu)), dim3(RF_THREADS), e->search.lds, e->stream, e->dg, f, d_particles,
                                d_state, n, (const float *)e->d_Bf, e->cfg.nref, e->d_fcand, d_raw);
             hipLaunchKernelGGL(unpack_solo_spectra_kernel, dim3(n * g.nshift), dim3(256), 0, e->stream, e->dg, (const float *)d_raw, n,
                                (const int *)e->d_numr, (const int *)e->d_ring_off, d_out);
@@ -2162,9 +2154,7 @@ static int ensure_refine_ws(ra_engine *e, int nimg)
     if (!e->d_rftw) {
         std::vector<double2> tw(nx);
         for (int t = 0; t < nx; t++) { const double a = 2.0 * M_PI * t / nx; tw[t] = make_double2(cos(a), sin(a)); }
-        const double2 *p = nullptr;
-        if ((rc = upload(e, tw, &p))) return rc;
-        e->d_rftw = (double2 *)p;
+        if ((rc = upload(e, tw, &e->d_rftw))) return rc;
     }
     e->rf_cap = cap;
     return RA_OK;
@@ -2197,9 +2187,7 @@ static int class_fsc_kernels(ra_engine *e, const float *d_sums, int masked)
     if (!e->d_fsc_off) {          // the coefficients of every shell, in scan order
         std::vector<int> off, idx;
         fsc_shell_table(nx, off, idx);
-        const int *p0 = nullptr, *p1 = nullptr;
-        if ((rc = upload(e, off, &p0)) || (rc = upload(e, idx, &p1))) return rc;
-        e->d_fsc_off = p0; e->d_fsc_idx = p1;
+        if ((rc = upload(e, off, &e->d_fsc_off)) || (rc = upload(e, idx, &e->d_fsc_idx))) return rc;
     }
     const int threads = std::min(1024, (RA_FSC_PARTS * len + 63) / 64 * 64);
     const size_t lds = (size_t)RA_FSC_PARTS * len * 4 * sizeof(double);

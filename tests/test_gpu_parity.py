@@ -304,15 +304,73 @@ def test_anisotropic_and_fractional_windows(xr, yr, step):
     eng.close()
 
 
-def test_chunking_is_invisible():
-    nx, ou, nref, xr, n = 32, 12, 4, 2, 150
-    refs = synth.make_references(nref, nx, ou)
-    parts, _ = synth.make_particles(refs, n, xr, xr, 1.0, ou=ou)
-    rg, mask, refs_n, cref = oracle_setup(refs, ou, nx)
-    e1, _, s1, r1 = run_engine(parts, refs_n, ou, xr, xr, 1.0, chunk=0)
-    e2, _, s2, r2 = run_engine(parts, refs_n, ou, xr, xr, 1.0, chunk=32)
-    assert torch.equal(r1, r2) and torch.equal(s1, s2)
-    e1.close(); e2.close()
+# One geometry per launch path of the resident batch loop (ra_align, ra_align_classes) and of the chunked path.  Geometries by name are
+# those of tests/test_gpu_dispatch.py::CASES and tests/test_gpu_plan_table.py::EXTRA; n and chunk give at least three launches and a
+# ragged last one (the size-generic cases: n > chunk, one refine launch behind the last chunk).  family = (search_path, search_tiled,
+# search_offsets_per_pass); ledger = a row only that path's engine has in its LDS ledger.
+#   id,                   geometry,           environment,           n,  chunk, family,    maxrin, ledger
+CHUNK_CASES = [
+    # the case this test began with: prepared references, noise of sigma 1, and no family asserted (it runs under every path switch)
+    ("box32-R4", ("box32", 32, 12, 1, 1, 2, 2, 1.0, 4, 0, api.RA_MODE_MREF, None), {}, 150, 32, None, None, None),
+    ("fused-pack",         "R14",              {},                    16, 6, (1, 0, 0), 256,  "search_fused_kernel"),
+    ("fused-pack-box93",   "box93-ou36",       {},                    16, 6, (1, 0, 0), 256,  "search_fused_kernel<pack>"),       # (R14 plans no pack kernel)
+    ("fused-no-pack",      "R14",              {"RALIGN_PACK": "0"},  16, 6, (1, 0, 0), 256,  "search_fused_kernel"),
+    ("fused-crop",         "box94-ou36",       {},                    16, 6, (1, 0, 0), 256,  "search_fused_kernel<pack> (crop)"),
+    ("tiled",              "R15",              {},                    16, 6, (1, 1, 0), 256,  "search_tiled_kernel"),
+    ("tiled-crop",         "R16-crop",         {},                    16, 6, (1, 1, 0), 256,  "search_tiled_kernel (crop)"),
+    ("pair",               "box128-ou40-R8",   {},                    16, 6, (3, 0, 2), 256,  "search_pair_kernel"),
+    ("duo",                "box100-ou41",      {},                    16, 6, (3, 0, 2), 512,  "search_duo_kernel"),
+    ("solo",               "box100-ou41",      {"RALIGN_DUO": "0"},   16, 6, (3, 0, 1), 512,  "search_solo_kernel"),
+    ("kernel-pair",        "R17-maxrin128",    {},                    16, 6, (0, 0, 0), 128,  "ccf_kernel"),
+    ("generic",            "box140-ou61",      {},                    7,  2, (2, 0, 0), 512,  "ccf_generic_kernel<2, 2>"),
+    ("generic-split",      "box200-ou88-R50",  {},                    7,  2, (2, 0, 0), 1024, "gccf_ifft_kernel<4, 7>"),
+    ("class-resident",     ("classes", 64, 25, 1, 1, 2, 2, 1.0, 1, 0, api.RA_MODE_REFFREE, None), {}, 16, 6, (1, 0, 0), 256, "search_fused_kernel"),
+]
+
+
+@pytest.mark.parametrize("refine", [None, -1.0], ids=["refine-default", "refine-all"])
+@pytest.mark.parametrize("case", CHUNK_CASES, ids=[c[0] for c in CHUNK_CASES])
+def test_chunking_is_invisible(case, refine, monkeypatch):
+    """every kernel family: results and states of an engine that takes the call in one launch
+    (chunk = 0) and of one that cuts it into batches are equal bit for bit, with the default refine threshold and with every
+    particle on the refine list (which then grows past its create-time size)"""
+    from test_gpu_plan_table import BY_NAME, SWITCHES
+    cid, geom, env, n, chunk, family, maxrin, ledger = case
+    if family:
+        default_path_only(*SWITCHES)
+    _, nx, ou, ir, rs, xr, yr, ts, nref, _, mode, _ = BY_NAME[geom] if isinstance(geom, str) else geom
+    ncls = 3 if cid == "class-resident" else 0
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    dev = torch.device("cuda:0")
+    refs = synth.make_references(ncls or nref, nx, ou)
+    parts, _ = synth.make_particles(refs, n, xr, yr, 0.5 if family else 1.0, ou=ou)
+    if not family:
+        refs = np.ascontiguousarray(oracle_setup(refs, ou, nx)[2])
+    tp, tr = torch.from_numpy(parts).to(dev), torch.from_numpy(refs).to(dev)
+    tc = (torch.arange(n, device=dev) % 3).to(torch.int32)
+    out = []
+    for ch in (0, chunk):
+        eng = api.Engine(nx, ou, xr, yr, ts, nref, mode, first_ring=ir, ring_skip=rs, chunk=ch)
+        if family:
+            assert (eng.search_path, int(eng.search_tiled), eng.search_offsets_per_pass) == family and eng.maxrin == maxrin
+            assert ledger in [r["kernel"] for r in eng.lds_report()]
+        if refine is not None:
+            eng.set_refine(refine)
+        st, res = eng.new_state(n), eng.new_result(n)
+        if ncls:
+            eng.set_class_references(tr)
+            eng.align_classes(tp, st, res, tc)
+        else:
+            eng.set_references(tr)
+            eng.align(tp, st, res)
+        eng.sync()
+        if refine is not None:
+            # (a resident launch starts the list anew; the chunked path collects the whole call in one list)
+            assert eng.last_refine_count() == (n if ch == 0 or eng.search_path in (0, 2) else n - (n - 1) // ch * ch)
+        out.append((res, st))
+        eng.close()
+    assert torch.equal(out[0][0], out[1][0]) and torch.equal(out[0][1], out[1][1])
 
 
 def test_reset_shifts_shrinks_window():
