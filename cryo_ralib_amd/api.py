@@ -79,7 +79,7 @@ EXPORTED_SYMBOLS = [
     "ra_fsc_len", "ra_class_fsc", "ra_last_class_fsc", "ra_fit_tanh", "ra_class_averages", "ra_filter_references",
     "ra_state_from_params_dev", "ra_class_fsc_fit", "ra_filter_references_dev", "ra_last_refine_count", "ra_lds_report",
     "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
-    "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d",
+    "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d", "ra_sdr_reconstruct",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
@@ -199,6 +199,7 @@ def load_library(path=None):
     L.ra_sdr_project.argtypes = [vp, ci, ci, ci, vp, vp, ci, vp, ci, vp, vp]
     L.ra_sdr_factors.argtypes = [vp, ci, ci, vp, ci, vp, vp]
     L.ra_rot_shift2d.argtypes = [vp, ci, ci, vp, vp, vp]
+    L.ra_sdr_reconstruct.argtypes = [vp, ci, ci, vp, ci, ci, vp, ci, vp, ci, vp, vp, vp, vp, vp]
     cf = ctypes.c_float
     L.ra_tsne_knn.argtypes = [vp, ci, ci, ci, vp, vp, vp]
     L.ra_tsne_affinity.argtypes = [vp, ci, ci, cf, vp, vp]
@@ -352,6 +353,24 @@ def mpca(images, p0, q0, **kw):
     """MPCA of images [n][p][q] (sdr.mpca)."""
     from . import sdr
     return sdr.mpca(images, p0, q0, **kw)
+
+
+def sdr_transform(images, model, **kw):
+    """Factors [n][r] of images [n][p][q] under a fitted sdr.SdrModel (sdr.transform)."""
+    from . import sdr
+    return sdr.transform(images, model, **kw)
+
+
+def sdr_reconstruct(factors, model, **kw):
+    """Images [n][p][q] rebuilt from factors [n][r] under a fitted sdr.SdrModel (sdr.reconstruct)."""
+    from . import sdr
+    return sdr.reconstruct(factors, model, **kw)
+
+
+def sdr_denoise(images, model, **kw):
+    """reconstruct(transform(images)), with residuals=True also |x - x^|^2 per image (sdr.denoise)."""
+    from . import sdr
+    return sdr.denoise(images, model, **kw)
 
 
 def tsne(X, **kw):

@@ -10,6 +10,7 @@
 //   sdr_gram_combine_kernel                             adds the run partials in a fixed order in double; writes both halves.
 //   sdr_project_kernel                                  U_i = A^T X_i B, [n][p0 q0] row-major (a, b) -> a q0 + b.
 //   sdr_factors_kernel                                  F = U G, [n][r].
+//   sdr_reconstruct_kernel                              x^_i = mean + A reshape(G f_i) B^T, [n][p][q], and |x_i - x^_i|^2.
 //
 // Every product is v_mfma_f32_16x16x4_f32 (exact f32 products, a k-ordered f32 fma chain). Operand maps (16x16x4): A[i][k] at
 // lane (i = l & 15, k = l >> 4), B[k][j] at lane (k = l >> 4, j = l & 15), C/D row = (l >> 4) * 4 + reg, column = l & 15.
@@ -301,5 +302,193 @@ __global__ __launch_bounds__(SDR_THREADS) void sdr_factors_kernel(const float *_
         }
     }
 }
+
+// Reconstruction. A workgroup owns a run of SDR_REC_RUN images (fixed, so an image's bits do not depend on n or on the grid).
+//   stage 0, once per run:  c = F G^T as one [run][r] x [r][m] product: F's rows and 64 rows of G at a time are staged in LDS with
+//                           coalesced loads, wave w owns 16 of the 64 columns; c lands in LDS as C_s[a][b], row stride qs.
+//                           Without G the rows of F are C already.
+//   A and B:                the operands of the tiles a wave owns (row tiles w, w + 4, .. of x^ for A, column tiles w, w + 4, ..
+//                           of T for B) are loaded once into registers and serve every image of the run: NU tiles x KS steps
+//                           of 4 columns, NU = ceil(max(p, q) / 64), KS = 4 ceil(max(p0, q0) / 16) (templates: the product loops
+//                           carry no branch, a tile or step past its matrix multiplies selected zeros and is never stored).
+//                           The steps run in the same order in every plan, so the plan does not show in the bits.
+//   stage 1, per image:     T[a][y] = sum_b C[a][b] B[y][b]  ([p0][q], LDS, row stride ts).
+//   stage 2, per image:     x^[x][y] = sum_a A[x][a] T[a][y], + mean, stored once; with resid the image is read at the same
+//                           pixel and (x - x^)^2 summed in double: per lane in tile order, the lanes of a wave by halving
+//                           shuffles, the four waves in order -- one writer, an order fixed by (p, q).
+// c, C and T never leave LDS.  Strides: qs, rs = 4 mod 8 and ts = 16 mod 32, so the 16 rows (C, F, G) or the 4 rows (T) of one
+// MFMA operand read fall in distinct banks.  Every operand outside its matrix is a selected 0, never a product with what LDS held.
+#define SDR_REC_RUN 8
+
+struct SdrRecPlan {
+    int qs, rs, ts;                 // row strides of C, of the staged F and G rows, of T (floats)
+    size_t floats;                  // dynamic LDS: C of the run, then the larger of T and the stage-0 staging
+};
+
+__host__ __device__ inline int sdr_rec_pad(int k) { k = (k + 3) & ~3; return (k & 4) ? k : k + 4; }
+
+__host__ __device__ inline SdrRecPlan sdr_rec_plan(int r, bool has_g, int p0, int q0, int q)
+{
+    SdrRecPlan pl;
+    pl.qs = sdr_rec_pad(q0);
+    pl.rs = sdr_rec_pad(r);
+    pl.ts = 16 * (((q + 15) / 16) | 1);
+    const size_t t = (size_t)p0 * pl.ts, stage = has_g ? (size_t)(SDR_REC_RUN + 64) * pl.rs : 0;
+    pl.floats = (size_t)SDR_REC_RUN * p0 * pl.qs + (t > stage ? t : stage);
+    return pl;
+}
+
+struct SdrRecArgs {
+    const float *F, *G, *A, *B, *mean, *x;     // G null: F is U; mean null: none added; x: the images, with resid only
+    float *out;
+    double *resid;
+    int n, r, p0, q0, p, q;                     // r: columns of F (p0 q0 without G)
+};
+
+template <int KS, int NU>
+__global__ __launch_bounds__(SDR_THREADS) void sdr_reconstruct_kernel(SdrRecArgs g)
+{
+    extern __shared__ __align__(16) float W[];
+    __shared__ double red[SDR_THREADS / 64];
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, lr = lane & 15, lk = lane >> 4;
+    const int m = g.p0 * g.q0, nxt = (g.p + 15) / 16, nyt = (g.q + 15) / 16, nat = (g.p0 + 15) / 16;
+    const SdrRecPlan pl = sdr_rec_plan(g.r, g.G != nullptr, g.p0, g.q0, g.q);
+    const int qs = pl.qs, rs = pl.rs, ts = pl.ts;
+    float *Cs = W, *T = W + (size_t)SDR_REC_RUN * g.p0 * qs, *Fs = T, *Gs = T + SDR_REC_RUN * rs;
+    const int i0 = blockIdx.x * SDR_REC_RUN, cnt = min(SDR_REC_RUN, g.n - i0);
+
+    if (g.G) {
+        // consecutive rows of r floats into LDS rows of stride rs: no division per element, four loads in flight per thread
+        auto stage = [&](float *dst, const float *src, int count) {
+            const int drow = SDR_THREADS / g.r, dcol = SDR_THREADS - drow * g.r;
+            int row = threadIdx.x / g.r, col = threadIdx.x - row * g.r;
+#pragma unroll 4
+            for (int e = threadIdx.x; e < count; e += SDR_THREADS) {
+                dst[row * rs + col] = src[e];
+                row += drow;
+                col += dcol;
+                if (col >= g.r) { col -= g.r; row++; }
+            }
+        };
+        stage(Fs, g.F + (size_t)i0 * g.r, cnt * g.r);
+        for (int t0 = 0; t0 < m; t0 += 64) {
+            const int rows = min(64, m - t0);
+            __syncthreads();                    // F is staged; the previous rows of G are consumed
+            stage(Gs, g.G + (size_t)t0 * g.r, rows * g.r);
+            __syncthreads();
+            if (t0 + wave * 16 >= m) continue;
+            const int t = t0 + wave * 16 + lr;
+            f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int k0 = 0; k0 < g.r; k0 += 4) {
+                const int kk = k0 + lk;
+                const float a = (lr < cnt && kk < g.r) ? Fs[lr * rs + kk] : 0.f;
+                const float b = (t < m && kk < g.r) ? Gs[(wave * 16 + lr) * rs + kk] : 0.f;
+                acc = sdr_mfma(a, b, acc);
+            }
+            if (t < m) {
+                const int ta = t / g.q0, tb = t - ta * g.q0;
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++)
+                    if (lk * 4 + reg < cnt) Cs[((lk * 4 + reg) * g.p0 + ta) * qs + tb] = acc[reg];
+            }
+        }
+    } else {
+        for (int e = threadIdx.x; e < cnt * m; e += SDR_THREADS) {
+            const int s = e / m, t = e - s * m, ta = t / g.q0;
+            Cs[(s * g.p0 + ta) * qs + t - ta * g.q0] = g.F[(size_t)i0 * m + e];
+        }
+    }
+    __syncthreads();                            // C is complete; the staging area becomes T
+
+    float Areg[NU][KS], Breg[NU][KS];
+#pragma unroll
+    for (int u = 0; u < NU; u++)
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) {
+            const int xy = (wave + 4 * u) * 16 + lr, k = 4 * ks + lk;
+            Areg[u][ks] = (xy < g.p && k < g.p0) ? g.A[xy * g.p0 + k] : 0.f;
+            Breg[u][ks] = (xy < g.q && k < g.q0) ? g.B[xy * g.q0 + k] : 0.f;
+        }
+
+#pragma unroll 1
+    for (int s = 0; s < cnt; s++) {
+        const float *C = Cs + s * g.p0 * qs;
+        for (int at = 0; at < nat; at++) {
+            f32x4 acc[NU];
+#pragma unroll
+            for (int u = 0; u < NU; u++) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int a = at * 16 + lr;
+#pragma unroll
+            for (int ks = 0; ks < KS; ks++) {
+                const int k = 4 * ks + lk;
+                const float cv = (a < g.p0 && k < g.q0) ? C[a * qs + k] : 0.f;
+#pragma unroll
+                for (int u = 0; u < NU; u++) acc[u] = sdr_mfma(cv, Breg[u][ks], acc[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < NU; u++) {
+                if (wave + 4 * u >= nyt) continue;
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    const int row = at * 16 + lk * 4 + reg;
+                    if (row < g.p0) T[row * ts + (wave + 4 * u) * 16 + lr] = acc[u][reg];
+                }
+            }
+        }
+        __syncthreads();
+
+        // The mean and the image values of a tile are fetched in front of the tile's products, which hide the loads: out may alias
+        // both for the compiler, so a load written next to its use would wait behind the store before it, 16 round trips a tile.
+        // Every address is a uniform row pointer plus one 32-bit lane offset, so the 48 of a tile cost no vector registers.
+        const size_t base = (size_t)(i0 + s) * g.p * g.q;
+        double rsum = 0.0;
+#pragma unroll 1
+        for (int yt = 0; yt < nyt; yt++) {
+            const int y = yt * 16 + lr;
+            const unsigned voff = (unsigned)((wave * 16 + lk * 4) * g.q + y);
+            float mv[NU][4], xv[NU][4];
+#pragma unroll
+            for (int u = 0; u < NU; u++)
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    const bool in = (wave + 4 * u) * 16 + lk * 4 + reg < g.p && y < g.q;
+                    const size_t row = (size_t)(64 * u + reg) * g.q;
+                    mv[u][reg] = (in && g.mean) ? (g.mean + row)[voff] : 0.f;
+                    xv[u][reg] = (in && g.resid) ? (g.x + base + row)[voff] : 0.f;
+                }
+            f32x4 acc[NU];
+#pragma unroll
+            for (int u = 0; u < NU; u++) acc[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ks = 0; ks < KS; ks++) {
+                const int k = 4 * ks + lk;
+                const float tv = k < g.p0 ? T[k * ts + y] : 0.f;
+#pragma unroll
+                for (int u = 0; u < NU; u++) acc[u] = sdr_mfma(Areg[u][ks], tv, acc[u]);
+            }
+#pragma unroll
+            for (int u = 0; u < NU; u++) {
+                if (wave + 4 * u >= nxt) continue;
+#pragma unroll
+                for (int reg = 0; reg < 4; reg++) {
+                    if ((wave + 4 * u) * 16 + lk * 4 + reg >= g.p || y >= g.q) continue;
+                    const float v = g.mean ? acc[u][reg] + mv[u][reg] : acc[u][reg];
+                    if (g.resid) {
+                        const double d = (double)xv[u][reg] - (double)v;
+                        rsum += d * d;
+                    }
+                    (g.out + base + (size_t)(64 * u + reg) * g.q)[voff] = v;
+                }
+            }
+        }
+        if (g.resid) {
+            for (int off = 32; off > 0; off >>= 1) rsum += __shfl_down(rsum, off);
+            if (lane == 0) red[wave] = rsum;
+        }
+        __syncthreads();                        // T is consumed; the waves' sums are in red
+        if (g.resid && threadIdx.x == 0) g.resid[i0 + s] = ((red[0] + red[1]) + red[2]) + red[3];
+    }
+}
+
 
 }  // namespace ralign

@@ -81,3 +81,40 @@ extern "C" int ra_sdr_factors(const float *d_U, int n, int m, const float *d_G, 
     hipError_t he = hipGetLastError();
     return he == hipSuccess ? RA_OK : hip_error("ra_sdr_factors", he);
 }
+
+// sdr_reconstruct_kernel<4 ks4, nu>: the register plan of a shape (ralign_sdr.h)
+template <int KS> static const void *sdr_reconstruct_nu(int nu)
+{
+    return nu == 1 ? (const void *)sdr_reconstruct_kernel<KS, 1> : nu == 2 ? (const void *)sdr_reconstruct_kernel<KS, 2>
+         : nu == 3 ? (const void *)sdr_reconstruct_kernel<KS, 3> : (const void *)sdr_reconstruct_kernel<KS, 4>;
+}
+
+static const void *sdr_reconstruct_plan(int ks4, int nu)
+{
+    return ks4 == 1 ? sdr_reconstruct_nu<4>(nu) : ks4 == 2 ? sdr_reconstruct_nu<8>(nu) : ks4 == 3 ? sdr_reconstruct_nu<12>(nu)
+                                                                                                  : sdr_reconstruct_nu<16>(nu);
+}
+
+extern "C" int ra_sdr_reconstruct(const float *d_F, int n, int r_or_m, const float *d_G, int p0, int q0, const float *d_A, int p,
+                                  const float *d_B, int q, const float *d_mean, const float *d_images, float *d_out, double *d_resid,
+                                  void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (n < 0 || p < 1 || p > 256 || q < 1 || q > 256 || p0 < 1 || p0 > std::min(p, 64) || q0 < 1 || q0 > std::min(q, 64) || p0 * q0 > 2048)
+        return arg_error("ra_sdr_reconstruct: need n >= 0, 1 <= p, q <= 256, 1 <= p0 <= min(p, 64), 1 <= q0 <= min(q, 64) and p0 q0 <= 2048");
+    if (d_G ? (r_or_m < 1 || r_or_m > std::min(256, p0 * q0)) : r_or_m != p0 * q0)
+        return arg_error("ra_sdr_reconstruct: need 1 <= r <= min(256, p0 q0) with d_G, and rows of p0 q0 factors without");
+    if (n == 0) return RA_OK;
+    if (!d_F || !d_A || !d_B || !d_out) return arg_error("ra_sdr_reconstruct: null argument");
+    if ((d_images != nullptr) != (d_resid != nullptr)) return arg_error("ra_sdr_reconstruct: d_images and d_resid go together");
+    SdrRecArgs g;
+    g.F = d_F; g.G = d_G; g.A = d_A; g.B = d_B; g.mean = d_mean; g.x = d_images; g.out = d_out; g.resid = d_resid;
+    g.n = n; g.r = r_or_m; g.p0 = p0; g.q0 = q0; g.p = p; g.q = q;
+    const size_t lds = sdr_rec_plan(r_or_m, d_G != nullptr, p0, q0, q).floats * sizeof(float);
+    const void *fk = sdr_reconstruct_plan((std::max(p0, q0) + 15) / 16, (std::max(p, q) + 63) / 64);
+    if (const int rc = raise_dynamic_lds(nullptr, fk, "sdr_reconstruct_kernel", lds)) return rc;
+    void *args[] = {&g};
+    hipError_t he = hipLaunchKernel(fk, dim3((n + SDR_REC_RUN - 1) / SDR_REC_RUN), dim3(SDR_THREADS), args, lds, stream);
+    if (he == hipSuccess) he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_sdr_reconstruct", he);
+}

@@ -422,7 +422,13 @@ int  ra_wiener_score(const float *d_images, int n, int nx, const ra_result *d_pa
  *                   1 <= p0 <= min(p, 64), 1 <= q0 <= min(q, 64), p0 q0 <= 2048.
  *   ra_sdr_factors  d_F [n][r] = U G; d_U [n][m], d_G [m][r]; 1 <= m <= 2048, 1 <= r <= min(256, m).
  *   ra_rot_shift2d  d_out [n][nx][nx] = rot_shift2D of d_in by d_params[i] (alpha, sx, sy, mirror; the other fields unused): the
- *                   kernel and grid of ra_transform_accumulate without sums, so bitwise equal to its aligned images; 2 <= nx <= 1024. */
+ *                   kernel and grid of ra_transform_accumulate without sums, so bitwise equal to its aligned images; 2 <= nx <= 1024.
+ *   ra_sdr_reconstruct  d_out [n][p][q] = d_mean + A reshape(c_i) B^T with c_i = G f_i (d_F [n][r], d_G [m][r], m = p0 q0) or,
+ *                   d_G NULL, c_i = row i of d_F [n][m] (r_or_m == m then); reshape is (a, b) -> a q0 + b; d_mean NULL adds none.
+ *                   With d_resid (and d_images, which go together) d_resid[i] = sum over pixels of (x_i - x^_i)^2 in double, x^_i as
+ *                   written, summed in an order fixed by (p, q).  One writer per pixel and per residual, no atomics, no scratch:
+ *                   an image's bits depend neither on n nor on its place in the batch.  Domain as ra_sdr_project and
+ *                   ra_sdr_factors, but n >= 0: n == 0 is a no-op.  A non-finite factor spoils its own image only. */
 int  ra_sdr_mean(const float *d_images, int n, int p, int q, float *d_mean, void *hip_stream);
 int  ra_sdr_gram(const float *d_images, int n, int p, int q, const float *d_mean, int form, const float *d_proj, int k,
                  double *d_gram, void *hip_stream);
@@ -430,6 +436,10 @@ int  ra_sdr_project(const float *d_images, int n, int p, int q, const float *d_m
                     int q0, float *d_U, void *hip_stream);
 int  ra_sdr_factors(const float *d_U, int n, int m, const float *d_G, int r, float *d_F, void *hip_stream);
 int  ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result *d_params, float *d_out, void *hip_stream);
+int  ra_sdr_reconstruct(const float *d_F, int n, int r_or_m, const float *d_G /* NULL: d_F is U */, int p0, int q0,
+                        const float *d_A, int p, const float *d_B, int q, const float *d_mean /* NULL: no mean */,
+                        const float *d_images /* NULL unless d_resid */, float *d_out, double *d_resid /* or NULL */,
+                        void *hip_stream);
 
 /* t-SNE (scikit-learn 1.7 TSNE with method="barnes_hut", angle=0, two output dimensions) of X [n][d] in device memory, without an
  * engine.  Pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL =
