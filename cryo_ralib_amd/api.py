@@ -81,6 +81,7 @@ EXPORTED_SYMBOLS = [
     "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
     "ra_sdr_mean", "ra_sdr_gram", "ra_sdr_project", "ra_sdr_factors", "ra_rot_shift2d", "ra_sdr_reconstruct",
     "ra_tsne_knn", "ra_tsne_affinity", "ra_tsne_step", "ra_tsne_error",
+    "ra_tsne_knn_query", "ra_tsne_affinity_rows", "ra_tsne_place_gradient", "ra_tsne_place",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
     "ra_hdbscan_core", "ra_hdbscan_round",
@@ -205,6 +206,10 @@ def load_library(path=None):
     L.ra_tsne_affinity.argtypes = [vp, ci, ci, cf, vp, vp]
     L.ra_tsne_step.argtypes = [vp, vp, vp, vp, ci, vp, vp, vp, ci, cf, cf, cf, vp, vp]
     L.ra_tsne_error.argtypes = [vp, ci, vp, vp, vp, ci, cf, vp, vp, vp]
+    L.ra_tsne_knn_query.argtypes = [vp, ci, vp, ci, ci, ci, vp, vp, vp]
+    L.ra_tsne_affinity_rows.argtypes = [vp, ci, ci, cf, vp, vp]
+    L.ra_tsne_place_gradient.argtypes = [vp, ci, vp, ci, vp, vp, ci, cf, vp, vp, vp, vp]
+    L.ra_tsne_place.argtypes = [vp, ci, vp, ci, vp, vp, ci, cf, cf, cf, ci, vp, vp]
     L.ra_kmeans_sqnorm.argtypes = [vp, ci, ci, vp, vp]
     L.ra_kmeans_labels.argtypes = [vp, ci, ci, vp, vp, ci, vp, ci, vp, vp]
     L.ra_kmeans_lloyd.argtypes = [vp, ci, ci, vp, vp, ci, vp, vp, vp, vp]
@@ -377,6 +382,30 @@ def tsne(X, **kw):
     """t-SNE embedding [n][2] of X [n][d] (tsne.tsne)."""
     from . import tsne as _tsne
     return _tsne.tsne(X, **kw)
+
+
+def tsne_transform(X_new, X_fit, Y_fit, **kw):
+    """New rows placed into a fitted embedding: [n][2] float32 (tsne.transform)."""
+    from . import tsne as _tsne
+    return _tsne.transform(X_new, X_fit, Y_fit, **kw)
+
+
+def tsne_knn_query(Q, X, k, **kw):
+    """(idx [nq][k], dist2 [nq][k]) of the k rows of X nearest every row of Q (tsne.knn_query)."""
+    from . import tsne as _tsne
+    return _tsne.knn_query(Q, X, k, **kw)
+
+
+def tsne_vote_labels(idx, p, labels_fit):
+    """(labels, confidence) of placed rows by the neighbour vote over the fitted rows' labels (tsne.vote_labels)."""
+    from . import tsne as _tsne
+    return _tsne.vote_labels(idx, p, labels_fit)
+
+
+def tsne_large(X, fit_size, **kw):
+    """t-SNE of up to 4194304 rows: a fit on fit_size drawn rows, the rest placed into it (tsne.tsne_large)."""
+    from . import tsne as _tsne
+    return _tsne.tsne_large(X, fit_size, **kw)
 
 
 def kmeans(X, n_clusters, **kw):

@@ -108,6 +108,90 @@ extern "C" int ra_tsne_error(const float *d_y, int n, const int *d_indptr, const
                     d_stats, (hipStream_t)hip_stream);
 }
 
+// ---- t-SNE, out-of-sample placement (ralign_tsne.h)
+
+extern "C" int ra_tsne_knn_query(const float *d_q, int nq, const float *d_x, int m, int d, int k, int *d_idx, double *d_dist2,
+                                 void *hip_stream)
+{
+    hipStream_t stream = (hipStream_t)hip_stream;
+    if (nq < 1 || nq > TSNE_MAX_NQ || m < 1 || m > TSNE_MAX_N || d < 1 || d > TSNE_MAX_D || k < 1 || k > std::min(m, TSNE_MAX_K))
+        return arg_error("ra_tsne_knn_query: need 1 <= nq <= 4194304, 1 <= m <= 262144, 1 <= d <= 2048 and 1 <= k <= min(m, 301)");
+    if (!d_q || !d_x || !d_idx || !d_dist2) return arg_error("ra_tsne_knn_query: null argument");
+    TsneKnnQueryArgs a;
+    a.q = d_q; a.x = d_x; a.nq = nq; a.m = m; a.d = d; a.k = k;
+    a.C = std::min(m, k + TSNE_KNN_MARGIN);
+    a.cap = a.C + TSNE_KNN_SLACK;
+    a.idx = d_idx; a.dist2 = d_dist2;
+    const size_t lds = (size_t)16 * a.C * sizeof(double) + (size_t)16 * TSNE_KNN_TILE * sizeof(float) + (size_t)16 * a.cap * 8;
+    if (const int rc = RA_LDS(nullptr, tsne_knn_query_kernel, lds)) return rc;
+    StreamScratch scratch(stream);
+    float *d_nrm = scratch.get<float>((size_t)nq + m);
+    if (!d_nrm) return hip_error("ra_tsne_knn_query", scratch.status());
+    a.qnrm = d_nrm; a.xnrm = d_nrm + nq;
+    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, d_q, nq, d, d_nrm);
+    hipError_t he = hipGetLastError();
+    RA_LAUNCH(he, tsne_sqnorm_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, d_x, m, d, d_nrm + nq);
+    RA_LAUNCH(he, tsne_knn_query_kernel, dim3((nq + 15) / 16), dim3(TSNE_KNN_THREADS), lds, stream, a);
+    return he == hipSuccess ? RA_OK : hip_error("ra_tsne_knn_query", he);
+}
+
+extern "C" int ra_tsne_affinity_rows(const double *d_dist2, int rows, int k, float perplexity, double *d_pcond, void *hip_stream)
+{
+    if (rows < 1 || rows > TSNE_MAX_NQ || k < 1 || k > TSNE_MAX_K || !(perplexity > 0.f && perplexity <= 100.f))
+        return arg_error("ra_tsne_affinity_rows: need 1 <= rows <= 4194304, 1 <= k <= 301 and 0 < perplexity <= 100");
+    if (!d_dist2 || !d_pcond) return arg_error("ra_tsne_affinity_rows: null argument");
+    hipLaunchKernelGGL(tsne_affinity_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)hip_stream, d_dist2, rows, k,
+                       log((double)perplexity), d_pcond);
+    hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_tsne_affinity_rows", he);
+}
+
+static bool tsne_place_ok(const char *what, const float *d_y, int n, const float *d_yfit, int m, const int *d_idx, const float *d_p,
+                          int k, float exaggeration)
+{
+    if (n < 1 || n > TSNE_MAX_NQ || m < 1 || m > TSNE_MAX_N || k < 1 || k > std::min(m, TSNE_MAX_K) || !std::isfinite(exaggeration) ||
+        !(exaggeration >= 1.f)) {
+        set_error(std::string(what) + ": need 1 <= n <= 4194304, 1 <= m <= 262144, 1 <= k <= min(m, 301) and a finite exaggeration >= 1");
+        return false;
+    }
+    if (!d_y || !d_yfit || !d_idx || !d_p) { set_error(std::string(what) + ": null argument"); return false; }
+    return true;
+}
+
+static int tsne_place_run(const char *what, float *d_y, int n, const float *d_yfit, int m, const int *d_idx, const float *d_p, int k,
+                          float exaggeration, float momentum, float learning_rate, int n_iter, float *d_grad, double *d_kl,
+                          double *d_z, hipStream_t stream)
+{
+    TsnePlaceArgs a;
+    a.y = (float2 *)d_y; a.yfit = (const float2 *)d_yfit; a.idx = d_idx; a.p = d_p; a.n = n; a.m = m; a.k = k; a.n_iter = n_iter;
+    a.exaggeration = exaggeration; a.momentum = momentum; a.learning_rate = learning_rate;
+    a.grad = (float2 *)d_grad; a.kl = d_kl; a.z = d_z;
+    hipLaunchKernelGGL(tsne_place_kernel, dim3((n + TSNE_PLACE_ROWS - 1) / TSNE_PLACE_ROWS), dim3(TSNE_PLACE_THREADS), 0, stream, a);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error(what, he);
+}
+
+extern "C" int ra_tsne_place_gradient(const float *d_y, int n, const float *d_yfit, int m, const int *d_idx, const float *d_p, int k,
+                                      float exaggeration, float *d_grad, double *d_kl, double *d_z, void *hip_stream)
+{
+    if (!tsne_place_ok("ra_tsne_place_gradient", d_y, n, d_yfit, m, d_idx, d_p, k, exaggeration)) return RA_ERR_ARG;
+    if (!d_grad && !d_kl && !d_z) return arg_error("ra_tsne_place_gradient: none of gradient, KL and Z asked for");
+    // n_iter = 0: the kernel reads d_y and writes the outputs only
+    return tsne_place_run("ra_tsne_place_gradient", const_cast<float *>(d_y), n, d_yfit, m, d_idx, d_p, k, exaggeration, 0.f, 0.f, 0,
+                          d_grad, d_kl, d_z, (hipStream_t)hip_stream);
+}
+
+extern "C" int ra_tsne_place(float *d_y, int n, const float *d_yfit, int m, const int *d_idx, const float *d_p, int k,
+                             float exaggeration, float momentum, float learning_rate, int n_iter, double *d_kl, void *hip_stream)
+{
+    if (!tsne_place_ok("ra_tsne_place", d_y, n, d_yfit, m, d_idx, d_p, k, exaggeration)) return RA_ERR_ARG;
+    if (n_iter < 0 || !(momentum >= 0.f && momentum < 1.f) || !std::isfinite(learning_rate) || !(learning_rate > 0.f))
+        return arg_error("ra_tsne_place: need n_iter >= 0, 0 <= momentum < 1 and a finite learning rate > 0");
+    if (n_iter == 0 && !d_kl) return RA_OK;
+    return tsne_place_run("ra_tsne_place", d_y, n, d_yfit, m, d_idx, d_p, k, exaggeration, momentum, learning_rate, n_iter, nullptr,
+                          d_kl, nullptr, (hipStream_t)hip_stream);
+}
+
 // ---- k-means (ralign_kmeans.h)
 
 static bool km_shape_ok(const char *what, int n, int d, int k)

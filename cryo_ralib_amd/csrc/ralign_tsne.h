@@ -11,6 +11,7 @@
 //   tsne_update_kernel      Z from the block partials, the row's repulsion from its segment partials, the sparse attraction over
 //                           its CSR row, the gradient, then sklearn's gains / momentum update (or the gradient alone).
 //   tsne_stats_kernel       KL error and squared gradient norm from the update's per-workgroup partials.
+//   tsne_knn_query_kernel, tsne_place_kernel   out-of-sample placement of new points into a fixed embedding (at the end).
 //
 // Determinism: no atomics on floating-point data. Every sum has an order fixed by n alone: the segment length, the row blocks
 // and the reduction trees depend on n only, never on the device or on how the grid is scheduled. The kNN list's append order
@@ -413,6 +414,275 @@ __global__ __launch_bounds__(256) void tsne_stats_kernel(const double *__restric
     e = tsne_block_sum<256>(e, red);
     g = tsne_block_sum<256>(g, red);
     if (threadIdx.x == 0) { stats[0] = e; stats[1] = g; }
+}
+
+// ---- out-of-sample placement: new points against a fixed embedding
+//
+//   tsne_knn_query_kernel   tsne_knn_kernel with separate query rows q [nq][d] and base rows x [m][d] and no self exclusion:
+//                           C = min(m, k + TSNE_KNN_MARGIN) survivors of the float32 Gram screen, re-ranked in double.
+//   tsne_place_kernel       a wave owns TSNE_PLACE_R new points and keeps their y, update and gains in registers over all
+//                           iterations; its 64 lanes share the fitted points (lane l takes columns l, l + 64, ... of each staged
+//                           chunk) and the neighbour list (entries l, l + 64, ...).  Per chunk a lane sums at most
+//                           TSNE_PLACE_CHUNK / 64 columns in float32, then adds the partial to a double; the lanes' doubles are
+//                           added by one xor butterfly, so all 64 hold the same bits and each applies the same update.
+//
+// Order: a point's sums depend on m and k only (the chunk, the lane stride and the butterfly are constants); the four points of a
+// wave run the same instructions on separate registers, so neither n, the point's slot nor the grid enters any value.
+
+#define TSNE_MAX_NQ 4194304
+#define TSNE_PLACE_THREADS 256
+#define TSNE_PLACE_R 4                                                 // points per wave
+#define TSNE_PLACE_ROWS (TSNE_PLACE_R * TSNE_PLACE_THREADS / 64)       // points per workgroup
+#define TSNE_PLACE_CHUNK 2048                                          // fitted points staged in LDS at a time
+
+struct TsneKnnQueryArgs {
+    const float *q, *qnrm, *x, *xnrm;
+    int nq, m, d, k, C, cap;        // C survivors per row, cap list capacity (C + TSNE_KNN_SLACK)
+    int *idx;                       // [nq][k]
+    double *dist2;                  // [nq][k]
+};
+
+// LDS as tsne_knn_kernel: tile [16][64] float, list distances [16][cap] float, list indices [16][cap] int, exact [16][C] double
+__global__ __launch_bounds__(TSNE_KNN_THREADS) void tsne_knn_query_kernel(TsneKnnQueryArgs a)
+{
+    extern __shared__ __align__(16) unsigned char tsne_smem[];
+    double *ex = (double *)tsne_smem;
+    float *tile = (float *)(ex + 16 * a.C);
+    float *ld = tile + 16 * TSNE_KNN_TILE;
+    int *li = (int *)(ld + 16 * a.cap);
+    __shared__ int cnt[16], full[16], thr_i[16];
+    __shared__ float thr_d[16];
+
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
+    const int i0 = blockIdx.x * 16;
+    const int row = tid >> 4, sub = tid & 15, gi = i0 + row;   // selection: 16 lanes per query row
+    if (tid < 16) { cnt[tid] = 0; full[tid] = 0; thr_d[tid] = __builtin_inff(); thr_i[tid] = 0; }
+    __syncthreads();
+
+    // keep the C smallest (distance, index) of the rows whose list holds more than `limit`; workgroup-uniform
+    auto compact = [&](int limit) {
+        const int c = cnt[row];
+        const bool act = gi < a.nq && c > limit;
+        float *rd = ld + row * a.cap;
+        int *ri = li + row * a.cap;
+        if (act) {
+            for (int e = sub; e < c; e += 16) {
+                const float de = rd[e];
+                const int ie = ri[e];
+                int rank = 0;
+                for (int f = 0; f < c; f++) rank += tsne_key_less(rd[f], ri[f], de, ie) ? 1 : 0;
+                if (rank == a.C - 1) { thr_d[row] = de; thr_i[row] = ie; }
+            }
+        }
+        __syncthreads();
+        if (act) {
+            const float td = thr_d[row];
+            const int ti = thr_i[row];
+            int base = 0;
+            for (int c0 = 0; c0 < c; c0 += 16) {
+                const int e = c0 + sub;
+                float dv = 0.f;
+                int iv = 0;
+                bool keep = false;
+                if (e < c) { dv = rd[e]; iv = ri[e]; keep = !tsne_key_less(td, ti, dv, iv); }
+                const unsigned long long b = __ballot(keep);
+                const unsigned grp = (unsigned)(b >> (lane & 48)) & 0xffffu;
+                const int pre = __popc(grp & ((1u << sub) - 1u));
+                if (keep) { rd[base + pre] = dv; ri[base + pre] = iv; }
+                base += __popc(grp);
+            }
+            if (sub == 0) { cnt[row] = base; full[row] = 1; }
+        }
+        __syncthreads();
+    };
+
+    const int qi = i0 + lr;
+    const float *xq = x_row_or_null(a.q, qi, a.nq, a.d);
+    for (int j0 = 0; j0 < a.m; j0 += TSNE_KNN_TILE) {
+        const int cj = j0 + wave * 16 + lr;
+        const float *xc = x_row_or_null(a.x, cj, a.m, a.d);
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+        for (int k0 = 0; k0 < a.d; k0 += 4) {
+            const int kk = k0 + lk;
+            const float av = (xq && kk < a.d) ? xq[kk] : 0.f;
+            const float bv = (xc && kk < a.d) ? xc[kk] : 0.f;
+            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
+        }
+        const float nc = cj < a.m ? a.xnrm[cj] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int orow = lk * 4 + r;
+            const float nq = i0 + orow < a.nq ? a.qnrm[i0 + orow] : 0.f;
+            tile[orow * TSNE_KNN_TILE + wave * 16 + lr] = tsne_not_nan(nq + nc - 2.f * acc[r]);
+        }
+        __syncthreads();
+        if (gi < a.nq) {
+            const bool fl = full[row] != 0;
+            const float td = thr_d[row];
+#pragma unroll
+            for (int t = 0; t < TSNE_KNN_TILE / 16; t++) {
+                const int col = sub + 16 * t, j = j0 + col;
+                if (j >= a.m) continue;
+                const float dv = tile[row * TSNE_KNN_TILE + col];
+                // columns arrive in increasing index order, so a distance equal to the cut loses to the kept entry
+                if (!fl || dv < td) {
+                    const int pos = atomicAdd(&cnt[row], 1);
+                    ld[row * a.cap + pos] = dv;
+                    li[row * a.cap + pos] = j;
+                }
+            }
+        }
+        __syncthreads();
+        bool over = false;
+#pragma unroll
+        for (int r = 0; r < 16; r++) over |= cnt[r] > a.cap - TSNE_KNN_TILE;
+        if (over) compact(a.cap - TSNE_KNN_TILE);
+    }
+    compact(a.C);
+
+    // re-rank the survivors by the exact squared distance (double, from q_i - x_j, the features in order)
+    const int c = gi < a.nq ? cnt[row] : 0;
+    const float *xi = a.q + (size_t)min(gi, a.nq - 1) * a.d;
+    double *rx = ex + row * a.C;
+    const int *ri = li + row * a.cap;
+    for (int e = sub; e < c; e += 16) {
+        const float *xj = a.x + (size_t)ri[e] * a.d;
+        double s = 0.0;
+        for (int t = 0; t < a.d; t++) {
+            const double df = (double)xi[t] - (double)xj[t];
+            s += df * df;
+        }
+        rx[e] = s != s ? __builtin_inf() : s;
+    }
+    __syncthreads();
+    for (int e = sub; e < c; e += 16) {
+        const double de = rx[e];
+        const int ie = ri[e];
+        int rank = 0;
+        for (int f = 0; f < c; f++) rank += tsne_key_less(rx[f], ri[f], de, ie) ? 1 : 0;
+        if (rank < a.k) {
+            a.idx[(size_t)gi * a.k + rank] = ie;
+            a.dist2[(size_t)gi * a.k + rank] = de;
+        }
+    }
+}
+
+struct TsnePlaceArgs {
+    float2 *y;                      // [n]: read; written after the iterations if n_iter > 0
+    const float2 *yfit;             // [m]
+    const int *idx;                 // [n][k] neighbour lists; entries outside 0 .. m - 1 are skipped
+    const float *p;                 // [n][k]
+    int n, m, k, n_iter;
+    float exaggeration, momentum, learning_rate;
+    float2 *grad;                   // [n] gradient at the final y with the exaggeration (may be null)
+    double *kl, *z;                 // [n] KL_i and Z_i at the final y (may be null)
+};
+
+// Z_i, the repulsion sum_j w^2 (y_i - Y_j) over all m fitted points, the attraction sum_nbr p w (y_i - Y_j) and (want_kl) KL_i of
+// the wave's TSNE_PLACE_R points; on return every lane holds the same values.  Workgroup-uniform: it stages yfit through ys
+template <bool KL>
+__device__ __forceinline__ void tsne_place_eval(const TsnePlaceArgs &a, float2 *ys, int row0, const float (&yx)[TSNE_PLACE_R],
+                                                const float (&yy)[TSNE_PLACE_R], double (&Z)[TSNE_PLACE_R],
+                                                double (&rx)[TSNE_PLACE_R], double (&ry)[TSNE_PLACE_R],
+                                                double (&ax)[TSNE_PLACE_R], double (&ay)[TSNE_PLACE_R], double (&kl)[TSNE_PLACE_R])
+{
+#pragma clang fp contract(off)
+    const int tid = threadIdx.x, lane = tid & 63;
+#pragma unroll
+    for (int r = 0; r < TSNE_PLACE_R; r++) { Z[r] = 0.0; rx[r] = 0.0; ry[r] = 0.0; ax[r] = 0.0; ay[r] = 0.0; kl[r] = 0.0; }
+    for (int jt = 0; jt < a.m; jt += TSNE_PLACE_CHUNK) {
+        const int c = min(TSNE_PLACE_CHUNK, a.m - jt);
+        __syncthreads();
+        for (int t = tid; t < c; t += TSNE_PLACE_THREADS) ys[t] = a.yfit[jt + t];
+        __syncthreads();
+        float fx[TSNE_PLACE_R], fy[TSNE_PLACE_R], z[TSNE_PLACE_R];
+#pragma unroll
+        for (int r = 0; r < TSNE_PLACE_R; r++) { fx[r] = 0.f; fy[r] = 0.f; z[r] = 0.f; }
+#pragma unroll 4
+        for (int j = lane; j < c; j += 64) {
+            const float2 v = ys[j];
+#pragma unroll
+            for (int r = 0; r < TSNE_PLACE_R; r++) {
+                const float dx = yx[r] - v.x, dy = yy[r] - v.y;
+                const float w = __builtin_amdgcn_rcpf(__builtin_fmaf(dx, dx, __builtin_fmaf(dy, dy, 1.f)));
+                const float w2 = w * w;
+                z[r] += w;
+                fx[r] = __builtin_fmaf(w2, dx, fx[r]);
+                fy[r] = __builtin_fmaf(w2, dy, fy[r]);
+            }
+        }
+#pragma unroll
+        for (int r = 0; r < TSNE_PLACE_R; r++) { Z[r] += (double)z[r]; rx[r] += (double)fx[r]; ry[r] += (double)fy[r]; }
+    }
+#pragma unroll
+    for (int r = 0; r < TSNE_PLACE_R; r++) { Z[r] = tsne_wave_sum(Z[r]); rx[r] = tsne_wave_sum(rx[r]); ry[r] = tsne_wave_sum(ry[r]); }
+    const float tiny = 1.17549435e-38f;
+#pragma unroll
+    for (int r = 0; r < TSNE_PLACE_R; r++) {
+        const int i = row0 + r;
+        if (i < a.n) {
+            for (int e = lane; e < a.k; e += 64) {
+                const int j = a.idx[(size_t)i * a.k + e];
+                if ((unsigned)j >= (unsigned)a.m) continue;
+                const float2 v = a.yfit[j];
+                const float pij = a.p[(size_t)i * a.k + e];
+                const float dx = yx[r] - v.x, dy = yy[r] - v.y;
+                const float w = 1.f / (1.f + (dx * dx + dy * dy));
+                const float f = pij * w;
+                ax[r] += (double)(f * dx);
+                ay[r] += (double)(f * dy);
+                if (KL) kl[r] += (double)pij * log(fmax((double)pij, (double)tiny) / fmax((double)w / Z[r], (double)tiny));
+            }
+        }
+        ax[r] = tsne_wave_sum(ax[r]);
+        ay[r] = tsne_wave_sum(ay[r]);
+        if (KL) kl[r] = tsne_wave_sum(kl[r]);
+    }
+}
+
+__global__ __launch_bounds__(TSNE_PLACE_THREADS) void tsne_place_kernel(TsnePlaceArgs a)
+{
+#pragma clang fp contract(off)
+    __shared__ float2 ys[TSNE_PLACE_CHUNK];
+    const int lane = threadIdx.x & 63;
+    const int row0 = blockIdx.x * TSNE_PLACE_ROWS + (threadIdx.x >> 6) * TSNE_PLACE_R;
+    float yx[TSNE_PLACE_R], yy[TSNE_PLACE_R], ux[TSNE_PLACE_R], uy[TSNE_PLACE_R], gx[TSNE_PLACE_R], gy[TSNE_PLACE_R];
+    double Z[TSNE_PLACE_R], rx[TSNE_PLACE_R], ry[TSNE_PLACE_R], ax[TSNE_PLACE_R], ay[TSNE_PLACE_R], kl[TSNE_PLACE_R];
+#pragma unroll
+    for (int r = 0; r < TSNE_PLACE_R; r++) {
+        const float2 v = row0 + r < a.n ? a.y[row0 + r] : float2{0.f, 0.f};
+        yx[r] = v.x; yy[r] = v.y; ux[r] = 0.f; uy[r] = 0.f; gx[r] = 1.f; gy[r] = 1.f;
+    }
+    const double e = (double)a.exaggeration;
+    for (int it = 0; it < a.n_iter; it++) {
+        tsne_place_eval<false>(a, ys, row0, yx, yy, Z, rx, ry, ax, ay, kl);
+#pragma unroll
+        for (int r = 0; r < TSNE_PLACE_R; r++) {
+            float dx = (float)(4.0 * (e * ax[r] - rx[r] / Z[r])), dy = (float)(4.0 * (e * ay[r] - ry[r] / Z[r]));
+            gx[r] = fmaxf(ux[r] * dx < 0.f ? gx[r] + 0.2f : gx[r] * 0.8f, 0.01f);
+            gy[r] = fmaxf(uy[r] * dy < 0.f ? gy[r] + 0.2f : gy[r] * 0.8f, 0.01f);
+            dx *= gx[r];
+            dy *= gy[r];
+            ux[r] = a.momentum * ux[r] - a.learning_rate * dx;
+            uy[r] = a.momentum * uy[r] - a.learning_rate * dy;
+            yx[r] += ux[r];
+            yy[r] += uy[r];
+        }
+    }
+    if (a.grad || a.kl || a.z) {
+        if (a.kl) tsne_place_eval<true>(a, ys, row0, yx, yy, Z, rx, ry, ax, ay, kl);
+        else tsne_place_eval<false>(a, ys, row0, yx, yy, Z, rx, ry, ax, ay, kl);
+    }
+#pragma unroll
+    for (int r = 0; r < TSNE_PLACE_R; r++) {
+        const int i = row0 + r;
+        if (i >= a.n || lane != r) continue;
+        if (a.n_iter > 0) a.y[i] = float2{yx[r], yy[r]};
+        if (a.grad) a.grad[i] = float2{(float)(4.0 * (e * ax[r] - rx[r] / Z[r])), (float)(4.0 * (e * ay[r] - ry[r] / Z[r]))};
+        if (a.kl) a.kl[i] = kl[r];
+        if (a.z) a.z[i] = Z[r];
+    }
 }
 
 }  // namespace ralign

@@ -20,8 +20,42 @@ numpy, chunking the all-pairs step: it is the CPU checker.
 
 Domain: 2 <= n <= 262144, 1 <= d <= 2048, 0 < perplexity <= 100 and perplexity < n, max_iter >= 250, n_components = 2; init "pca"
 needs d >= 2.  Anything else raises TsneError before anything is launched; so does non-finite input.
+
+Out-of-sample placement (transform, tsne_large; the tool's --fit_size and --place_into): new rows X_new [n][d] are placed into a
+fixed embedding Y_fit [m][2] of fitted rows X_fit [m][d] (any embedding of X_fit, normally tsne()'s).  Each new point interacts
+with the fitted points only, so the work is n m pairs per iteration and batches without limit.  The rules:
+  1. Neighbours.  k = min(m, int(3 perplexity + 1)).  For new row i the k fitted rows of least D2(i, j) = sum_t (xnew_it -
+     xfit_jt)^2, formed in double from the differences of the float32 values with the features in order, ordered by (D2, j).  No
+     row is excluded: a new row equal to a fitted row lists it first at distance 0.
+  2. Affinities.  p_i. = binary_search_perplexity(D2 row, perplexity), each row searched on its own (the fit's rule and kernel).
+     No symmetrisation and no global normalisation.  The device rounds p to float32 once.
+  3. Objective, per point.  w_ij = 1 / (1 + |y_i - Y_j|^2), Z_i = sum_{j < m} w_ij over every fitted point, KL_i = sum_{j in N(i)}
+     p_ij log(max(p_ij, tiny) / max(w_ij / Z_i, tiny)), tiny = float32's smallest normal.  The normalisation is per point, so a
+     point's result does not depend on which other points were placed with it.
+  4. Gradient.  g_i = 4 (e sum_{j in N(i)} p_ij w_ij (y_i - Y_j) - sum_{j < m} w_ij^2 (y_i - Y_j) / Z_i).  |w d| <= 1/2, sum p <= 1
+     and the repulsion is a weighted mean of w d, so |g_i|_inf <= 2 (e + 1): nothing is clipped.
+  5. Start.  init="weighted": y_i = sum_j p_ij Y_N(i,j) in double in list order, rounded to float32; init="nearest": Y of the
+     first neighbour; or an [n][2] array.
+  6. Optimiser.  Exactly n_iter iterations of the fit's rule from update = 0 and gains = 1: inc = update g < 0; gains = inc ?
+     gains + 0.2 : gains 0.8, floored at 0.01; update = momentum update - learning_rate gains g; y += update.  No checks, no early
+     stop, no host sync inside the loop.  Defaults: perplexity 30, learning_rate 0.1, momentum 0.8, exaggeration e = 1, n_iter 250.
+  7. Independence and determinism.  Everything returned for point i is a function of (x_i, X_fit, Y_fit, parameters) alone,
+     bitwise the same whatever n, the batch size, the point's position in the batch or the stream.  No floating-point atomics;
+     every sum over j runs in an order fixed by m (and k) only.
+  8. Label vote (vote_labels).  score_i(c) = sum_{j: label = c} p_ij in double in list order over the fitted points' integer
+     labels (-1, noise, counts as a label); the label is the largest score, the lowest label on ties; the confidence is the
+     winning score.
+Rules 1, 2 and 3-6 run in ra_tsne_knn_query, ra_tsne_affinity_rows and ra_tsne_place (one launch for all iterations); rules 5 and
+8 are torch and numpy plumbing.  backend="numpy" is the float64 checker, chunked, without a GPU.  Domain: X_fit and Y_fit agree in
+m, X_new and X_fit in d; 2 <= m <= 262144, 1 <= d <= 2048, 0 < perplexity <= 100 and perplexity < m, n >= 0 (n = 0 returns empty
+arrays without a launch), batch <= 262144, finite input; tsne_large: 2 <= fit_size <= min(n, 262144), n <= 4194304.
+
+    python -m cryo_ralib_amd.tsne IN OUT.npz --fit_size M [--seed S] ...            fit M drawn rows, place the rest (tsne_large)
+    python -m cryo_ralib_amd.tsne IN OUT.npz --place_into FIT_OUT.npz --fit_input FILE [--fit_key factors] ...
+    both: [--place_iter 250] [--place_lr 0.1] [--place_exaggeration 1] [--place_perplexity P] [--batch 65536] [--fit_labels FILE]
 """
 import argparse
+import collections
 import math
 import sys
 
@@ -272,6 +306,37 @@ class _Device:
         self.call("ra_tsne_error", ptr(y), n, ptr(indptr), ptr(indices), ptr(p32), int(p32.numel()), float(exaggeration), ptr(g), ptr(st))
         return float(st[0].item()), g
 
+    def knn_query(self, Q, X, k):
+        nq, d = (int(s) for s in Q.shape)
+        idx = self.torch.empty((nq, k), dtype=self.torch.int32, device=self.dev)
+        d2 = self.torch.empty((nq, k), dtype=self.torch.float64, device=self.dev)
+        self.call("ra_tsne_knn_query", ptr(Q), nq, ptr(X), int(X.shape[0]), d, k, ptr(idx), ptr(d2))
+        return idx, d2
+
+    def affinity_rows(self, d2, perplexity):
+        rows, k = (int(s) for s in d2.shape)
+        pc = self.torch.empty((rows, k), dtype=self.torch.float64, device=self.dev)
+        self.call("ra_tsne_affinity_rows", ptr(d2), rows, k, float(perplexity), ptr(pc))
+        return pc
+
+    def place_gradient(self, y, yfit, idx, p32, exaggeration=1.0):
+        """(grad [n][2] float32, KL_i [n] float64, Z_i [n] float64) at y, as device tensors"""
+        n, k = (int(s) for s in idx.shape)
+        g = self.torch.empty((n, 2), dtype=self.torch.float32, device=self.dev)
+        kl = self.torch.empty(n, dtype=self.torch.float64, device=self.dev)
+        z = self.torch.empty(n, dtype=self.torch.float64, device=self.dev)
+        self.call("ra_tsne_place_gradient", ptr(y), n, ptr(yfit), int(yfit.shape[0]), ptr(idx), ptr(p32), k, float(exaggeration),
+                  ptr(g), ptr(kl), ptr(z))
+        return g, kl, z
+
+    def place(self, y, yfit, idx, p32, exaggeration, momentum, learning_rate, n_iter):
+        """n_iter iterations in place on y; returns KL_i [n] at the final y"""
+        n, k = (int(s) for s in idx.shape)
+        kl = self.torch.empty(n, dtype=self.torch.float64, device=self.dev)
+        self.call("ra_tsne_place", ptr(y), n, ptr(yfit), int(yfit.shape[0]), ptr(idx), ptr(p32), k, float(exaggeration),
+                  float(momentum), float(learning_rate), int(n_iter), ptr(kl))
+        return kl
+
 
 class _DeviceState:
     """float32 state of the optimiser on the device: two embedding buffers (a step reads every y_j while it writes)"""
@@ -497,11 +562,422 @@ def trustworthiness(X, Y, n_neighbors=10):
     return float(1.0 - t * (2.0 / (n * n_neighbors * (2.0 * n - 3.0 * n_neighbors - 1.0))))
 
 
+# ---- out-of-sample placement (rules 1 - 8 of the module's text)
+
+MAX_NEW, MAX_BATCH = 4194304, 262144
+TransformDetails = collections.namedtuple("TransformDetails", "embedding kl kl_init idx p")
+LargeResult = collections.namedtuple("LargeResult", "embedding fit_indices kl_point fit")
+
+
+def n_neighbors_query(m, perplexity):
+    """rule 1's neighbour count for m fitted points"""
+    return min(m, int(3.0 * perplexity + 1))
+
+
+def check_transform_domain(n, m, d, perplexity=30.0, learning_rate=0.1, momentum=0.8, exaggeration=1.0, n_iter=250, batch=65536):
+    """raise TsneError unless the shapes and parameters of a placement are inside the supported domain"""
+    def need(ok, msg):
+        if not ok:
+            raise TsneError(msg)
+    for name, v in (("n", n), ("m", m), ("d", d), ("n_iter", n_iter), ("batch", batch)):
+        need(_common.is_int(v), "%s must be an integer, got %r" % (name, v))
+    need(n >= 0, "need n >= 0 new points, got %d" % n)
+    need(2 <= m <= MAX_N, "need 2 <= m <= %d fitted points, got %d" % (MAX_N, m))
+    need(1 <= d <= MAX_D, "need 1 <= d <= %d features, got %d" % (MAX_D, d))
+    need(_common.is_real(perplexity) and 0 < perplexity <= 100, "need 0 < perplexity <= 100, got %r" % (perplexity,))
+    need(perplexity < m, "perplexity (%g) must be less than the number of fitted points (%d)" % (perplexity, m))
+    need(_common.is_real(learning_rate) and learning_rate > 0, "need a finite learning_rate > 0, got %r" % (learning_rate,))
+    need(_common.is_real(momentum) and 0 <= momentum < 1, "need 0 <= momentum < 1, got %r" % (momentum,))
+    need(_common.is_real(exaggeration) and exaggeration >= 1, "need a finite exaggeration >= 1, got %r" % (exaggeration,))
+    need(n_iter >= 0, "need n_iter >= 0, got %d" % n_iter)
+    need(1 <= batch <= MAX_BATCH, "need 1 <= batch <= %d, got %d" % (MAX_BATCH, batch))
+
+
+def knn_query_numpy(Q, X, k):
+    """rule 1 in float64: (idx [nq][k] int64, dist2 [nq][k]) of the k rows of X nearest each row of Q, by (distance, index)"""
+    Q, X = np.asarray(Q, np.float64), np.asarray(X, np.float64)
+    nq, m = Q.shape[0], X.shape[0]
+    idx = np.empty((nq, k), np.int64)
+    d2 = np.empty((nq, k), np.float64)
+    ch = max(1, (1 << 22) // m)
+    for s in range(0, nq, ch):
+        e = min(nq, s + ch)
+        D = np.zeros((e - s, m))
+        for t in range(X.shape[1]):
+            df = Q[s:e, t, None] - X[None, :, t]
+            D += df * df
+        o = np.argsort(D, axis=1, kind="stable")[:, :k]
+        idx[s:e], d2[s:e] = o, np.take_along_axis(D, o, axis=1)
+    return idx, d2
+
+
+def place_gradient_numpy(y, Y_fit, idx, p, exaggeration=1.0, dtype=np.float64, want_kl=True):
+    """rules 3 and 4 at y: (gradient [n][2], KL_i [n] or None, Z_i [n]) in `dtype`, the all-pairs part in chunks of rows; list
+    entries outside 0 .. m - 1 are skipped"""
+    y, Y_fit, p = np.asarray(y, dtype), np.asarray(Y_fit, dtype), np.asarray(p, dtype)
+    idx = np.asarray(idx, np.int64)
+    n, m = y.shape[0], Y_fit.shape[0]
+    Z = np.empty(n, dtype)
+    rep = np.empty((n, 2), dtype)
+    ch = max(1, (1 << 21) // m)
+    for s in range(0, n, ch):
+        e = min(n, s + ch)
+        dx, dy = y[s:e, 0, None] - Y_fit[None, :, 0], y[s:e, 1, None] - Y_fit[None, :, 1]
+        w = 1 / (1 + (dx * dx + dy * dy))
+        Z[s:e] = w.sum(axis=1)
+        w *= w
+        rep[s:e, 0], rep[s:e, 1] = (w * dx).sum(axis=1), (w * dy).sum(axis=1)
+    ok = (idx >= 0) & (idx < m)
+    j = np.where(ok, idx, 0)
+    pv = np.where(ok, p, 0).astype(dtype)
+    dx, dy = y[:, 0, None] - Y_fit[j, 0], y[:, 1, None] - Y_fit[j, 1]
+    w = 1 / (1 + (dx * dx + dy * dy))
+    f = pv * w
+    attr = np.stack([(f * dx).sum(axis=1), (f * dy).sum(axis=1)], axis=1)
+    kl = None
+    if want_kl:
+        tiny = dtype(FLOAT32_TINY)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            kl = (pv * np.log(np.maximum(pv, tiny) / np.maximum(w / Z[:, None], tiny))).sum(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        grad = 4 * (dtype(exaggeration) * attr - rep / Z[:, None])
+    return grad, kl, Z
+
+
+def place_numpy(y0, Y_fit, idx, p, exaggeration=1.0, momentum=0.8, learning_rate=0.1, n_iter=250, dtype=np.float64):
+    """rule 6 in `dtype` numpy: (y [n][2], KL_i [n] at the final y)"""
+    y = np.array(y0, dtype)
+    update, gains = np.zeros_like(y), np.ones_like(y)
+    for _ in range(n_iter):
+        g = place_gradient_numpy(y, Y_fit, idx, p, exaggeration, dtype, want_kl=False)[0]
+        gains = np.maximum(np.where(update * g < 0, gains + dtype(0.2), gains * dtype(0.8)), dtype(0.01))
+        update = dtype(momentum) * update - dtype(learning_rate) * (gains * g)
+        y = y + update
+    return y, place_gradient_numpy(y, Y_fit, idx, p, 1.0, dtype)[1]
+
+
+def _check_init(init, n):
+    if isinstance(init, str):
+        if init not in ("weighted", "nearest"):
+            raise TsneError("init is 'weighted', 'nearest' or an [n][2] array, got %r" % (init,))
+        return init
+    Y = np.asarray(init.detach().cpu().numpy() if hasattr(init, "detach") else init, np.float32)
+    if Y.shape != (n, 2):
+        raise TsneError("an init array is [n][2] = [%d][2], got %s" % (n, Y.shape))
+    if not np.all(np.isfinite(Y)):
+        raise TsneError("the init array holds NaN or infinite values")
+    return Y
+
+
+def initial_placement_numpy(init, Y_fit, idx, p):
+    """rule 5: the [n][2] float32 start; init is "weighted", "nearest" or the rows of an init array"""
+    if not isinstance(init, str):
+        return np.asarray(init, np.float32)
+    Y = np.asarray(Y_fit, np.float64)
+    if init == "nearest":
+        return Y[idx[:, 0]].astype(np.float32)
+    acc = np.zeros((idx.shape[0], 2))
+    for j in range(idx.shape[1]):
+        acc = acc + np.asarray(p[:, j, None], np.float64) * Y[idx[:, j]]
+    return acc.astype(np.float32)
+
+
+def _initial_placement_device(torch, init, Y_fit, idx, p32):
+    """rule 5 on the device: the same sum, one list column at a time in float64 (a product and an addition, nothing fused)"""
+    if not isinstance(init, str):
+        return torch.from_numpy(np.ascontiguousarray(init, np.float32)).to(Y_fit.device)
+    if init == "nearest":
+        return Y_fit[idx[:, 0].long()].contiguous()
+    Y = Y_fit.double()
+    acc = torch.zeros((idx.shape[0], 2), dtype=torch.float64, device=Y_fit.device)
+    for j in range(int(idx.shape[1])):
+        acc = acc + p32[:, j, None].double() * Y[idx[:, j].long()]
+    return acc.float().contiguous()
+
+
+def _host_finite(A, step=1 << 16):
+    return all(bool(np.all(np.isfinite(A[s:s + step]))) for s in range(0, A.shape[0], step))
+
+
+def knn_query(Q, X, k, backend="device"):
+    """rule 1: (idx [nq][k], dist2 [nq][k] float64) of the k rows of X [m][d] nearest every row of Q [nq][d], as numpy arrays"""
+    Q = _common.as_input(Q, backend, TsneError)
+    X = _common.as_input(X, backend, TsneError)
+    (nq, d), (m, dx) = (int(s) for s in Q.shape), (int(s) for s in X.shape)
+    if not (_common.is_int(k) and 1 <= nq <= MAX_NEW and 1 <= m <= MAX_N and 1 <= d <= MAX_D and d == dx and 1 <= k <= min(m, 301)):
+        raise TsneError("need 1 <= nq <= %d, 1 <= m <= %d, Q and X of the same 1 <= d <= %d and 1 <= k <= min(m, 301)"
+                        % (MAX_NEW, MAX_N, MAX_D))
+    if backend == "numpy":
+        return knn_query_numpy(np.asarray(Q, np.float32), np.asarray(X, np.float32), k)
+    import torch
+    with torch.cuda.device(X.device):
+        idx, d2 = _Device(X.device).knn_query(Q, X, k)
+        return idx.cpu().numpy().astype(np.int64), d2.cpu().numpy()
+
+
+def transform(X_new, X_fit, Y_fit, perplexity=30.0, learning_rate=0.1, momentum=0.8, exaggeration=1.0, n_iter=250, init="weighted",
+              batch=65536, backend="device", details=False):
+    """Place X_new [n][d] into the embedding Y_fit [m][2] of X_fit [m][d] (rules 1 - 7): the embedding [n][2] float32, or with
+    details TransformDetails(embedding, kl [n] (KL_i at the end), kl_init [n] (at the start), idx [n][k], p [n][k]), as numpy
+    arrays.  backend="device": X_fit and Y_fit are contiguous float32 CUDA tensors (numpy arrays are copied to the current
+    device) and the work runs on the current stream; X_new is such a tensor too, or a numpy array of any size, which is copied one
+    batch at a time so that only a batch's lists live on the device."""
+    if backend not in ("device", "numpy"):
+        raise TsneError("backend is 'device' or 'numpy', got %r" % (backend,))
+    host_new = backend == "numpy" or isinstance(X_new, np.ndarray)
+    Xn = _common.as_input(X_new, "numpy" if host_new else "device", TsneError, numpy_on_device=False)
+    Xf, Yf = _common.as_input(X_fit, backend, TsneError), _common.as_input(Y_fit, backend, TsneError)
+    if backend == "numpy":
+        Xf, Yf = np.ascontiguousarray(Xf, np.float32), np.ascontiguousarray(Yf, np.float32)
+    elif Yf.device != Xf.device or not (host_new or Xn.device == Xf.device):
+        raise TsneError("X_new, X_fit and Y_fit are on different devices")
+    (n, d), m = (int(s) for s in Xn.shape), int(Xf.shape[0])
+    if tuple(Yf.shape) != (m, 2):
+        raise TsneError("Y_fit is [m][2] = [%d][2], got %s" % (m, tuple(Yf.shape)))
+    if int(Xf.shape[1]) != d:
+        raise TsneError("X_new has %d features, X_fit %d" % (d, int(Xf.shape[1])))
+    check_transform_domain(n, m, d, perplexity, learning_rate, momentum, exaggeration, n_iter, batch)
+    init = _check_init(init, n)
+    _common.check_finite(Xf, backend, TsneError)
+    _common.check_finite(Yf, backend, TsneError)
+    if not (_host_finite(Xn) if host_new else bool(Xn.isfinite().all().item())):
+        raise TsneError("X holds NaN or infinite values")
+    k = n_neighbors_query(m, perplexity)
+    emb, kl = np.empty((n, 2), np.float32), np.empty(n, np.float64)
+    if details:
+        kl0, idx_all, p_all = np.empty(n, np.float64), np.empty((n, k), np.int64), np.empty((n, k), np.float64)
+
+    def run(torch=None, D=None):
+        for s in range(0, n, batch):
+            e = min(n, s + batch)
+            y0 = init if isinstance(init, str) else init[s:e]
+            if D is None:
+                idx, d2 = knn_query_numpy(np.asarray(Xn[s:e], np.float32), Xf, k)
+                p = binary_search_perplexity(d2, perplexity)
+                y0 = initial_placement_numpy(y0, Yf, idx, p)
+                if details:
+                    kl0[s:e] = place_gradient_numpy(y0, Yf, idx, p)[1]
+                y, kl[s:e] = place_numpy(y0, Yf, idx, p, exaggeration, momentum, learning_rate, n_iter)
+                emb[s:e] = y.astype(np.float32)
+            else:
+                xb = torch.from_numpy(np.ascontiguousarray(Xn[s:e], np.float32)).to(D.dev) if host_new else Xn[s:e]
+                idx, d2 = D.knn_query(xb, Xf, k)
+                p = D.affinity_rows(d2, perplexity).to(torch.float32)
+                y = _initial_placement_device(torch, y0, Yf, idx, p)
+                if details:
+                    kl0[s:e] = D.place_gradient(y, Yf, idx, p)[1].cpu().numpy()
+                kl[s:e] = D.place(y, Yf, idx, p, exaggeration, momentum, learning_rate, n_iter).cpu().numpy()
+                emb[s:e] = y.cpu().numpy()
+            if details:
+                idx_all[s:e] = idx if D is None else idx.cpu().numpy()
+                p_all[s:e] = p if D is None else p.cpu().numpy()
+
+    if backend == "numpy":
+        run()
+    elif n:
+        import torch
+        with torch.cuda.device(Xf.device):
+            run(torch, _Device(Xf.device))
+    return TransformDetails(emb, kl, kl0, idx_all, p_all) if details else emb
+
+
+def affinities_query(X_new, X_fit, perplexity=30.0, batch=65536, backend="device"):
+    """rules 1 and 2 alone: (idx [n][k] int64, p [n][k] float64; on the device p holds float32 values) of the rows of X_new (a
+    numpy array, copied a batch at a time) against X_fit, as numpy arrays: what vote_labels needs for rows that were not placed"""
+    X_new = np.asarray(X_new)
+    Xf = _common.as_input(X_fit, backend, TsneError)
+    (n, d), m = X_new.shape, int(Xf.shape[0])
+    check_transform_domain(n, m, d, perplexity, batch=batch)
+    k = n_neighbors_query(m, perplexity)
+    idx_all, p_all = np.empty((n, k), np.int64), np.empty((n, k), np.float64)
+    if backend == "device" and n:
+        import torch
+        D = _Device(Xf.device)
+    for s in range(0, n, batch):
+        xb = np.ascontiguousarray(X_new[s:s + batch], np.float32)
+        if backend == "numpy":
+            idx_all[s:s + batch], d2 = knn_query_numpy(xb, Xf, k)
+            p_all[s:s + batch] = binary_search_perplexity(d2, perplexity)
+        else:
+            with torch.cuda.device(Xf.device):
+                idx, d2 = D.knn_query(torch.from_numpy(xb).to(D.dev), Xf, k)
+                idx_all[s:s + batch] = idx.cpu().numpy()
+                p_all[s:s + batch] = D.affinity_rows(d2, perplexity).to(torch.float32).cpu().numpy()
+    return idx_all, p_all
+
+
+def vote_labels(idx, p, labels_fit):
+    """rule 8: (labels [n] int32, confidence [n] float64) of the new points from their neighbour lists idx [n][k], p [n][k] and the
+    fitted points' integer labels [m]; list entries outside 0 .. m - 1 are skipped"""
+    idx, p, labels_fit = np.asarray(idx), np.asarray(p, np.float64), np.asarray(labels_fit)
+    if labels_fit.ndim != 1 or labels_fit.size < 1 or not np.issubdtype(labels_fit.dtype, np.integer):
+        raise TsneError("labels_fit is [m] integers, got %s %s" % (labels_fit.dtype, labels_fit.shape))
+    if idx.ndim != 2 or idx.shape != p.shape or not np.issubdtype(idx.dtype, np.integer):
+        raise TsneError("idx [n][k] (integers) and p [n][k] must agree, got %s %s and %s" % (idx.dtype, idx.shape, p.shape))
+    classes, inv = np.unique(labels_fit, return_inverse=True)
+    n, m = idx.shape[0], labels_fit.shape[0]
+    score = np.zeros((n, classes.size))
+    rows = np.arange(n)
+    for j in range(idx.shape[1]):
+        ok = (idx[:, j] >= 0) & (idx[:, j] < m)
+        score[rows[ok], inv[idx[ok, j]]] += p[ok, j]
+    best = np.argmax(score, axis=1)                         # the first maximum: the lowest label on ties
+    return classes[best].astype(np.int32), score[rows, best]
+
+
+def draw_fit_rows(n, fit_size, random_state=None):
+    """the sorted fit rows of tsne_large: check_random_state(random_state).permutation(n)[:fit_size]"""
+    return np.sort(check_random_state(random_state).permutation(n)[:fit_size])
+
+
+def check_large_domain(n, fit_size):
+    if not (_common.is_int(n) and _common.is_int(fit_size) and 2 <= fit_size <= min(n, MAX_N) and n <= MAX_NEW):
+        raise TsneError("need 2 <= fit_size <= min(n, %d) and n <= %d, got fit_size = %r, n = %r" % (MAX_N, MAX_NEW, fit_size, n))
+
+
+def tsne_large(X, fit_size, random_state=None, transform_kwargs=None, **tsne_kwargs):
+    """t-SNE of any n <= 4194304 rows: tsne() on fit_size drawn rows (draw_fit_rows; random_state also seeds the fit), transform()
+    for the rest; fitted rows keep their fitted positions.  LargeResult(embedding [n][2] float32, fit_indices, kl_point [n] (KL_i
+    of the placed rows, nan on fitted rows), fit (the TsneResult)).  The backend is tsne_kwargs' (default "device": X is a CUDA
+    tensor, or a numpy array whose rows are copied as they are used)."""
+    backend = tsne_kwargs.get("backend", "device")
+    host = backend == "numpy" or isinstance(X, np.ndarray)
+    X = _common.as_input(X, "numpy" if host else "device", TsneError, numpy_on_device=False)
+    n = int(X.shape[0])
+    check_large_domain(n, fit_size)
+    fit_idx = draw_fit_rows(n, fit_size, random_state)
+    rest = np.setdiff1d(np.arange(n), fit_idx)
+    if host:
+        Xf, Xr = np.ascontiguousarray(X[fit_idx], np.float32), X[rest]
+        if backend == "device":
+            import torch
+            Xf = torch.from_numpy(Xf).to(torch.device("cuda", torch.cuda.current_device()))
+    else:
+        import torch
+        Xf, Xr = X[torch.from_numpy(fit_idx).to(X.device)].contiguous(), X[torch.from_numpy(rest).to(X.device)].contiguous()
+    fit = tsne(Xf, random_state=random_state, **tsne_kwargs)
+    if backend == "device":
+        with torch.cuda.device(Xf.device):                 # the fitted embedding is copied to the device of the rows
+            placed = transform(Xr, Xf, fit.embedding, details=True, **(transform_kwargs or {}))
+    else:
+        placed = transform(Xr, Xf, fit.embedding, backend=backend, details=True, **(transform_kwargs or {}))
+    emb, kl = np.empty((n, 2), np.float32), np.full(n, np.nan)
+    emb[fit_idx], emb[rest], kl[rest] = fit.embedding, placed.embedding, placed.kl
+    return LargeResult(emb, fit_idx, kl, fit)
+
+
 # ---- command line
 
 def read_input(path, key="factors"):
     """[n][d] float32 from an .npz (key) or an .npy"""
     return _common.read_input(path, key, TsneError)
+
+
+def read_fit_labels(path):
+    """[m] integer labels from an int .npy, or the `labels` of an .npz of the dbscan, hdbscan, kmeans or gmm tool"""
+    try:
+        if path.endswith(".npz"):
+            with np.load(path) as z:
+                if "labels" not in z.files:
+                    raise TsneError("%s has no array 'labels' (it holds %s)" % (path, ", ".join(z.files)))
+                y = z["labels"]
+        else:
+            y = np.load(path)
+    except (OSError, ValueError) as e:
+        raise TsneError("%s: %s" % (path, e))
+    if y.ndim != 1 or not np.issubdtype(y.dtype, np.integer):
+        raise TsneError("%s: need [m] integers, got %s %s" % (path, y.dtype, y.shape))
+    return y
+
+
+def _main_place(ap, args):
+    """the tool's --fit_size and --place_into modes.  Usage errors leave through ap.error (status 2) before the device is touched"""
+    if args.fit_size is not None and args.place_into is not None:
+        ap.error("--fit_size and --place_into are two modes: give one of them")
+    if args.place_into is not None and args.fit_input is None:
+        ap.error("--place_into needs --fit_input (the rows its embedding was fitted on)")
+    if args.fit_size is not None and args.fit_input is not None:
+        ap.error("--fit_input goes with --place_into")
+    try:
+        X = read_input(args.input, args.key)
+        labels_fit = read_fit_labels(args.fit_labels) if args.fit_labels else None
+        lr = args.learning_rate if args.learning_rate == "auto" else float(args.learning_rate)
+        init = args.init if args.init in ("pca", "random") else np.load(args.init)
+        perplexity = args.perplexity
+        if args.place_into is not None:
+            Xf = read_input(args.fit_input, args.fit_key)
+            with np.load(args.place_into) as z:
+                if "embedding" not in z.files:
+                    raise TsneError("%s has no array 'embedding' (it holds %s)" % (args.place_into, ", ".join(z.files)))
+                Yf = np.ascontiguousarray(z["embedding"], np.float32)
+                perplexity = float(z["perplexity"]) if "perplexity" in z.files else perplexity
+    except (TsneError, OSError, ValueError) as e:
+        raise SystemExit("error: %s" % e)
+    n, d = X.shape
+    if args.place_into is not None:
+        m = Xf.shape[0]
+        if Yf.shape != (m, 2):
+            ap.error("%s holds an embedding %s, %s has %d rows" % (args.place_into, Yf.shape, args.fit_input, m))
+        if Xf.shape[1] != d:
+            ap.error("%s has %d features, %s %d" % (args.input, d, args.fit_input, Xf.shape[1]))
+    else:
+        m = args.fit_size
+        try:
+            check_large_domain(n, m)
+        except TsneError as e:
+            ap.error("--fit_size: %s" % e)
+    if labels_fit is not None and labels_fit.shape[0] != m:
+        ap.error("%s holds %d labels for %d fitted rows" % (args.fit_labels, labels_fit.shape[0], m))
+    kw = dict(perplexity=perplexity if args.place_perplexity is None else args.place_perplexity,
+              learning_rate=0.1 if args.place_lr is None else args.place_lr,
+              exaggeration=1.0 if args.place_exaggeration is None else args.place_exaggeration,
+              n_iter=250 if args.place_iter is None else args.place_iter, batch=65536 if args.batch is None else args.batch)
+    try:
+        check_transform_domain(n, m, d, kw["perplexity"], kw["learning_rate"], 0.8, kw["exaggeration"], kw["n_iter"], kw["batch"])
+        if args.fit_size is not None:
+            check_domain(m, d, args.perplexity, args.max_iter, 2, args.early_exaggeration, lr)
+    except TsneError as e:
+        raise SystemExit("error: %s" % e)
+    if args.backend == "device":
+        _common.require_gpu("no GPU visible: use --backend numpy for the CPU checker")
+
+    def run():
+        out = {}
+        if args.fit_size is not None:
+            res = tsne_large(X, m, random_state=args.seed, transform_kwargs=kw, perplexity=args.perplexity,
+                             early_exaggeration=args.early_exaggeration, learning_rate=lr, max_iter=args.max_iter, init=init,
+                             backend=args.backend)
+            fit, fit_rows = res.fit, X[res.fit_indices]
+            out.update(embedding=res.embedding, kl_divergence=np.float64(fit.kl_divergence), n_iter=np.int64(fit.n_iter),
+                       errors=fit.errors, perplexity=np.float64(args.perplexity),
+                       early_exaggeration=np.float64(args.early_exaggeration),
+                       learning_rate=np.float64(resolve_learning_rate(lr, m, args.early_exaggeration)),
+                       max_iter=np.int64(args.max_iter), init=np.str_(args.init),
+                       seed=np.int64(-1 if args.seed is None else args.seed), backend=np.str_(args.backend),
+                       fit_indices=res.fit_indices, kl_point=res.kl_point)
+        else:
+            placed = transform(X, Xf, Yf, backend=args.backend, details=True, **kw)
+            out.update(embedding=placed.embedding, kl_point=placed.kl)
+        if labels_fit is not None:
+            # every row votes, the fitted ones too (each lists itself first at distance 0)
+            idx, p = ((placed.idx, placed.p) if args.fit_size is None else
+                      affinities_query(X, fit_rows, kw["perplexity"], kw["batch"], args.backend))
+            out["labels"], out["label_confidence"] = vote_labels(idx, p, labels_fit)
+        return out
+    try:
+        if args.backend == "device":
+            import torch
+            with torch.cuda.device(args.device):
+                out = run()
+        else:
+            out = run()
+    except TsneError as e:
+        raise SystemExit("error: %s" % e)
+    np.savez(args.output, **out)
+    kl = out["kl_point"][np.isfinite(out["kl_point"])]
+    print("%s: %d points x %d placed against %d fitted, mean KL_i %.6f" % (args.output, kl.size, d, m,
+                                                                        float(kl.mean()) if kl.size else float("nan")))
+    return 0
 
 
 def main(argv=None):
@@ -517,7 +993,25 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=None, help="random_state of init random")
     ap.add_argument("--backend", default="device", choices=("device", "numpy"))
     ap.add_argument("--device", type=int, default=0)
+    ap.add_argument("--fit_size", type=int, default=None, help="fit this many drawn rows (--seed) and place the rest into their "
+                    "embedding; the only mode that takes more than %d rows" % MAX_N)
+    ap.add_argument("--place_into", default=None, help="OUT.npz of an earlier run: place the input's rows into its embedding")
+    ap.add_argument("--fit_input", default=None, help="the rows the embedding of --place_into was fitted on (.npz or .npy)")
+    ap.add_argument("--fit_key", default="factors", help="array of an .npz --fit_input (default factors)")
+    ap.add_argument("--place_iter", type=int, default=None, help="iterations of the placement (default 250)")
+    ap.add_argument("--place_lr", type=float, default=None, help="learning rate of the placement (default 0.1)")
+    ap.add_argument("--place_exaggeration", type=float, default=None, help="exaggeration of the placement (default 1)")
+    ap.add_argument("--place_perplexity", type=float, default=None, help="perplexity of the placement (default: the fit's)")
+    ap.add_argument("--batch", type=int, default=None, help="new rows on the device at a time (default 65536)")
+    ap.add_argument("--fit_labels", default=None, help="int .npy, or OUT.npz of the dbscan, hdbscan, kmeans or gmm tool (its labels), "
+                    "one label per fitted row: adds labels and label_confidence of every row by the neighbour vote")
     args = ap.parse_args(argv)
+    if args.fit_size is not None or args.place_into is not None:
+        return _main_place(ap, args)
+    given = [o for o in ("fit_input", "place_iter", "place_lr", "place_exaggeration", "place_perplexity", "batch", "fit_labels")
+             if getattr(args, o) is not None]
+    if given:
+        ap.error("--%s needs --fit_size or --place_into" % given[0])
     try:
         X = read_input(args.input, args.key)
         lr = args.learning_rate if args.learning_rate == "auto" else float(args.learning_rate)

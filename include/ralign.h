@@ -466,6 +466,32 @@ int  ra_tsne_step(const float *d_y, float *d_y_out, float *d_update, float *d_ga
 int  ra_tsne_error(const float *d_y, int n, const int *d_indptr, const int *d_indices, const float *d_p, int nnz, float exaggeration,
                    float *d_grad, double *d_stats, void *hip_stream);
 
+/* Out-of-sample t-SNE: n new points placed into a fixed embedding d_yfit [m][2] of fitted rows d_x [m][d] (DESIGN.md section 4.18;
+ * the rules are stated at the top of cryo_ralib_amd/tsne.py).  The conventions are those of ra_tsne_* above.  Every value of a new
+ * point is a function of that point, the fitted rows and the parameters alone: bitwise the same whatever n, the point's position,
+ * the batch or the stream (no floating-point atomics; every sum in an order fixed by m and k).  A non-finite y or p spoils its own
+ * point only.  Shape domain: 1 <= n, nq, rows <= 4194304, 1 <= m <= 262144, 1 <= d <= 2048, 1 <= k <= min(m, 301).
+ *   ra_tsne_knn_query       d_idx [nq][k], d_dist2 [nq][k]: for every row of d_q [nq][d] the k rows of d_x [m][d] of least squared
+ *                           distance, ordered by (distance, index), distances in double from q_i - x_j with the features in order.
+ *                           No row is excluded: a query equal to a base row lists it first at distance 0.  The candidates are
+ *                           screened by float32 Gram distances with a margin of 32, as in ra_tsne_knn: on data far from the origin
+ *                           relative to its spread (uncentred data) the screen can drop a true neighbour; centre such data first.
+ *   ra_tsne_affinity_rows   ra_tsne_affinity's search on any `rows` lists of k distances (1 <= k <= 301): it does not tie k to
+ *                           the number of rows, which ra_tsne_affinity does.
+ *   ra_tsne_place_gradient  at d_y [n][2]: d_grad [n][2] = 4 (e sum_nbr p w (y_i - Y_j) - sum_{j < m} w^2 (y_i - Y_j) / Z_i),
+ *                           d_kl [n] = sum_nbr p log(max(p, tiny) / max(w / Z_i, tiny)), d_z [n] = Z_i = sum_{j < m} w_ij,
+ *                           w = 1 / (1 + |y_i - Y_j|^2); d_idx [n][k] and d_p [n][k] (float32) are the neighbour lists, entries
+ *                           outside 0 .. m - 1 are skipped.  Each output may be NULL, not all three.  exaggeration e >= 1.
+ *   ra_tsne_place           n_iter >= 0 iterations of ra_tsne_step's gains / momentum rule on that gradient from update = 0 and
+ *                           gains = 1, in place on d_y, in one launch; d_kl (may be NULL) receives KL_i at the final y.
+ *                           0 <= momentum < 1, finite learning_rate > 0. */
+int  ra_tsne_knn_query(const float *d_q, int nq, const float *d_x, int m, int d, int k, int *d_idx, double *d_dist2, void *hip_stream);
+int  ra_tsne_affinity_rows(const double *d_dist2, int rows, int k, float perplexity, double *d_pcond, void *hip_stream);
+int  ra_tsne_place_gradient(const float *d_y, int n, const float *d_yfit, int m, const int *d_idx, const float *d_p, int k,
+                            float exaggeration, float *d_grad, double *d_kl, double *d_z, void *hip_stream);
+int  ra_tsne_place(float *d_y, int n, const float *d_yfit, int m, const int *d_idx, const float *d_p, int k, float exaggeration,
+                   float momentum, float learning_rate, int n_iter, double *d_kl, void *hip_stream);
+
 /* k-means (scikit-learn 1.7 KMeans(algorithm="lloyd") with uniform weights) of X [n][d] in device memory, without an engine
  * (DESIGN.md section 4.8).  Pointers are device pointers; every call is asynchronous on hip_stream (a hipStream_t; NULL = default
  * stream) and allocates and frees its scratch on that stream, as ra_phase_flip does.  Results are bitwise reproducible call to
