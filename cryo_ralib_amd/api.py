@@ -84,7 +84,7 @@ EXPORTED_SYMBOLS = [
     "ra_tsne_knn_query", "ra_tsne_affinity_rows", "ra_tsne_place_gradient", "ra_tsne_place",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
-    "ra_hdbscan_core", "ra_hdbscan_round",
+    "ra_hdbscan_core", "ra_hdbscan_round", "ra_embed_ranks",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
     "ra_prep_normalize", "ra_prep_filter",
 ]
@@ -223,6 +223,7 @@ def load_library(path=None):
     L.ra_dbscan_step.argtypes = [vp, ci, ci, ctypes.c_double, vp, ci, vp, vp, vp, vp]
     L.ra_hdbscan_core.argtypes = [vp, ci, ci, ci, vp, vp]
     L.ra_hdbscan_round.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.ra_embed_ranks.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -484,6 +485,30 @@ def dbscan_kdistances(X, min_samples, **kw):
     """For every point the least eps at which it is a core point, float64 [n] (dbscan.kdistances)."""
     from . import dbscan as _dbscan
     return _dbscan.kdistances(X, min_samples, **kw)
+
+
+def trustworthiness(X, Y, **kw):
+    """Trustworthiness of the embedding Y of X (quality.trustworthiness): do the neighbours in Y lie near in X?"""
+    from . import quality as _quality
+    return _quality.trustworthiness(X, Y, **kw)
+
+
+def continuity(X, Y, **kw):
+    """Continuity of the embedding Y of X (quality.continuity): do the neighbours in X stay near in Y?"""
+    from . import quality as _quality
+    return _quality.continuity(X, Y, **kw)
+
+
+def embedding_quality(X, Y, **kw):
+    """Trustworthiness, continuity, their per-point scores and the co-ranking curve in one call (quality.embedding_quality)."""
+    from . import quality as _quality
+    return _quality.embedding_quality(X, Y, **kw)
+
+
+def neighbor_ranks(A, idx, **kw):
+    """int32 [n][k]: the rank in A's row i of every entry of the lists idx [n][k] (quality.neighbor_ranks)."""
+    from . import quality as _quality
+    return _quality.neighbor_ranks(A, idx, **kw)
 
 
 def _check(rc, what):

@@ -1,12 +1,13 @@
-// t-SNE, k-means, cluster validity, DBSCAN and HDBSCAN of 2SDR factors (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h,
-// ralign_dbscan.h, ralign_hdbscan.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_* and ra_hdbscan_* entry points of
-// libralign_hip.so, each on the caller's stream.
+// t-SNE, k-means, cluster validity, DBSCAN, HDBSCAN and embedding quality of 2SDR factors (ralign_tsne.h, ralign_kmeans.h,
+// ralign_validity.h, ralign_dbscan.h, ralign_hdbscan.h, ralign_quality.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_*,
+// ra_hdbscan_* and ra_embed_* entry points of libralign_hip.so, each on the caller's stream.
 #include "ralign_host.h"
 #include "ralign_scratch.h"
 #include "ralign_kmeans.h"
 #include "ralign_validity.h"
 #include "ralign_dbscan.h"
 #include "ralign_hdbscan.h"
+#include "ralign_quality.h"
 
 using namespace ralign;
 
@@ -526,4 +527,27 @@ extern "C" int ra_hdbscan_round(const float *d_x, int n, int d, const double *d_
     RA_LAUNCH(he, hdb_out_kernel, dim3(nt), dim3(256), 0, stream, d_comp, n, (const unsigned long long *)cw, (const unsigned long long *)ce,
               d_w2, d_lo, d_hi);
     return he == hipSuccess ? RA_OK : hip_error("ra_hdbscan_round", he);
+}
+
+// ---- embedding quality (ralign_quality.h)
+
+extern "C" int ra_embed_ranks(const float *d_x, int n, int d, const int *d_idx, int k, int *d_rank, long long *d_pen, void *hip_stream)
+{
+    if (n < 2 || n > EMB_MAX_N || d < 1 || d > EMB_MAX_D || k < 1 || k > EMB_MAX_K)
+        return arg_error("ra_embed_ranks: need 2 <= n <= 262144, 1 <= d <= 2048 and 1 <= k <= 301");
+    if (!d_x || !d_idx || (!d_rank && !d_pen)) return arg_error("ra_embed_ranks: null argument, or neither ranks nor penalties asked for");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    EmbRankArgs a;
+    a.x = d_x; a.idx = d_idx; a.n = n; a.d = d; a.k = k; a.kc = std::min(k, EMB_KC);
+    a.rank = d_rank; a.pen = d_pen;
+    const size_t lds = emb_rank_lds(a.kc);
+    if (const int rc = RA_LDS(nullptr, emb_rank_kernel, lds)) return rc;
+    StreamScratch scratch(stream);
+    double *thr = scratch.get<double>((size_t)n * k);
+    if (!thr) return hip_error("ra_embed_ranks", scratch.status());
+    a.thr = thr;
+    hipLaunchKernelGGL(emb_thr_kernel, dim3((unsigned)(((size_t)n * k + 255) / 256)), dim3(256), 0, stream, d_x, n, d, d_idx, k, thr);
+    hipError_t he = hipGetLastError();
+    RA_LAUNCH(he, emb_rank_kernel, dim3((n + DBS_TR - 1) / DBS_TR), dim3(256), lds, stream, a);
+    return he == hipSuccess ? RA_OK : hip_error("ra_embed_ranks", he);
 }

@@ -53,6 +53,10 @@ arrays without a launch), batch <= 262144, finite input; tsne_large: 2 <= fit_si
     python -m cryo_ralib_amd.tsne IN OUT.npz --fit_size M [--seed S] ...            fit M drawn rows, place the rest (tsne_large)
     python -m cryo_ralib_amd.tsne IN OUT.npz --place_into FIT_OUT.npz --fit_input FILE [--fit_key factors] ...
     both: [--place_iter 250] [--place_lr 0.1] [--place_exaggeration 1] [--place_perplexity P] [--batch 65536] [--fit_labels FILE]
+
+Every mode takes --quality [K] (default 10) [--quality_sample N]: trustworthiness, continuity, trust_point and cont_point of the
+written embedding against the input rows (quality.embedding_quality) join OUT.npz; more than 262144 rows need --quality_sample (the
+drawn rows, by --seed, are stored as quality_sample_indices).
 """
 import argparse
 import collections
@@ -890,6 +894,29 @@ def read_fit_labels(path):
     return y
 
 
+def _check_quality(ap, args, n):
+    """--quality's usage errors (status 2, before the device is touched)"""
+    if args.quality is not None:
+        from . import quality
+        quality.check_tool_arguments(ap, n, n, args.quality, args.quality_sample)
+
+
+def _add_quality(out, args, X, backend):
+    """--quality: the four scores of out["embedding"] against the rows X into out; returns their part of the summary line"""
+    if args.quality is None:
+        return ""
+    from . import quality
+    try:
+        q = quality.embedding_quality(X, out["embedding"], args.quality, args.quality_sample, args.seed, backend)
+    except quality.QualityError as e:
+        raise TsneError("--quality: %s" % e)
+    out.update(trustworthiness=np.float64(q.trustworthiness), continuity=np.float64(q.continuity), trust_point=q.trust_point,
+               cont_point=q.cont_point)
+    if q.sample_indices is not None:
+        out["quality_sample_indices"] = q.sample_indices
+    return ", trustworthiness %.6f, continuity %.6f (k = %d)" % (q.trustworthiness, q.continuity, args.quality)
+
+
 def _main_place(ap, args):
     """the tool's --fit_size and --place_into modes.  Usage errors leave through ap.error (status 2) before the device is touched"""
     if args.fit_size is not None and args.place_into is not None:
@@ -914,6 +941,7 @@ def _main_place(ap, args):
     except (TsneError, OSError, ValueError) as e:
         raise SystemExit("error: %s" % e)
     n, d = X.shape
+    _check_quality(ap, args, n)
     if args.place_into is not None:
         m = Xf.shape[0]
         if Yf.shape != (m, 2):
@@ -963,6 +991,7 @@ def _main_place(ap, args):
             idx, p = ((placed.idx, placed.p) if args.fit_size is None else
                       affinities_query(X, fit_rows, kw["perplexity"], kw["batch"], args.backend))
             out["labels"], out["label_confidence"] = vote_labels(idx, p, labels_fit)
+        out["_quality"] = _add_quality(out, args, X, args.backend)
         return out
     try:
         if args.backend == "device":
@@ -973,10 +1002,11 @@ def _main_place(ap, args):
             out = run()
     except TsneError as e:
         raise SystemExit("error: %s" % e)
+    tail = out.pop("_quality")
     np.savez(args.output, **out)
     kl = out["kl_point"][np.isfinite(out["kl_point"])]
-    print("%s: %d points x %d placed against %d fitted, mean KL_i %.6f" % (args.output, kl.size, d, m,
-                                                                        float(kl.mean()) if kl.size else float("nan")))
+    print("%s: %d points x %d placed against %d fitted, mean KL_i %.6f%s" % (args.output, kl.size, d, m,
+                                                                          float(kl.mean()) if kl.size else float("nan"), tail))
     return 0
 
 
@@ -1005,7 +1035,13 @@ def main(argv=None):
     ap.add_argument("--batch", type=int, default=None, help="new rows on the device at a time (default 65536)")
     ap.add_argument("--fit_labels", default=None, help="int .npy, or OUT.npz of the dbscan, hdbscan, kmeans or gmm tool (its labels), "
                     "one label per fitted row: adds labels and label_confidence of every row by the neighbour vote")
+    ap.add_argument("--quality", type=int, nargs="?", const=10, default=None, metavar="K",
+                    help="add trustworthiness, continuity, trust_point and cont_point at K neighbours (default 10) to OUT.npz")
+    ap.add_argument("--quality_sample", type=int, default=None, metavar="N",
+                    help="evaluate --quality on N drawn rows (--seed); needed above %d rows" % MAX_N)
     args = ap.parse_args(argv)
+    if args.quality_sample is not None and args.quality is None:
+        ap.error("--quality_sample needs --quality")
     if args.fit_size is not None or args.place_into is not None:
         return _main_place(ap, args)
     given = [o for o in ("fit_input", "place_iter", "place_lr", "place_exaggeration", "place_perplexity", "batch", "fit_labels")
@@ -1019,25 +1055,31 @@ def main(argv=None):
         check_domain(X.shape[0], X.shape[1], args.perplexity, args.max_iter, 2, args.early_exaggeration, lr)
     except (TsneError, OSError, ValueError) as e:
         raise SystemExit("error: %s" % e)
+    _check_quality(ap, args, X.shape[0])
     if args.backend == "device":
         _common.require_gpu("no GPU visible: use --backend numpy for the CPU checker")
     x = _common.to_device(X, args.device) if args.backend == "device" else X
+
+    def run():
+        res = tsne(x, args.perplexity, args.early_exaggeration, lr, args.max_iter, init=init, random_state=args.seed,
+                   backend=args.backend)
+        out = dict(embedding=res.embedding, kl_divergence=np.float64(res.kl_divergence), n_iter=np.int64(res.n_iter),
+                   errors=res.errors, perplexity=np.float64(args.perplexity), early_exaggeration=np.float64(args.early_exaggeration),
+                   learning_rate=np.float64(resolve_learning_rate(lr, X.shape[0], args.early_exaggeration)),
+                   max_iter=np.int64(args.max_iter), init=np.str_(args.init), seed=np.int64(-1 if args.seed is None else args.seed),
+                   backend=np.str_(args.backend))
+        return res, out, _add_quality(out, args, x, args.backend)
     try:
         if args.backend == "device":
             import torch
             with torch.cuda.device(x.device):
-                res = tsne(x, args.perplexity, args.early_exaggeration, lr, args.max_iter, init=init, random_state=args.seed)
+                res, out, tail = run()
         else:
-            res = tsne(x, args.perplexity, args.early_exaggeration, lr, args.max_iter, init=init, random_state=args.seed,
-                       backend="numpy")
+            res, out, tail = run()
     except TsneError as e:
         raise SystemExit("error: %s" % e)
-    np.savez(args.output, embedding=res.embedding, kl_divergence=np.float64(res.kl_divergence), n_iter=np.int64(res.n_iter),
-             errors=res.errors, perplexity=np.float64(args.perplexity), early_exaggeration=np.float64(args.early_exaggeration),
-             learning_rate=np.float64(resolve_learning_rate(lr, X.shape[0], args.early_exaggeration)),
-             max_iter=np.int64(args.max_iter), init=np.str_(args.init), seed=np.int64(-1 if args.seed is None else args.seed),
-             backend=np.str_(args.backend))
-    print("%s: %d points x %d, %d iterations, KL %.6f" % (args.output, X.shape[0], X.shape[1], res.n_iter, res.kl_divergence))
+    np.savez(args.output, **out)
+    print("%s: %d points x %d, %d iterations, KL %.6f%s" % (args.output, X.shape[0], X.shape[1], res.n_iter, res.kl_divergence, tail))
     return 0
 
 

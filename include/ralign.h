@@ -601,6 +601,20 @@ int  ra_hdbscan_core(const float *d_x, int n, int d, int min_samples, double *d_
 int  ra_hdbscan_round(const float *d_x, int n, int d, const double *d_core2, const int *d_comp, double *d_w2, int *d_lo, int *d_hi,
                       void *hip_stream);
 
+/* Neighbour ranks for trustworthiness and continuity of an embedding (cryo_ralib_amd/quality.py, whose docstring holds the contract
+ * rule by rule).  D2 is ra_dbscan_count's: double, from differences, the features in order, exactly
+ * symmetric.  In the row of i, column l precedes column j iff (D2(i, l), l) < (D2(i, j), j); rank(i, j) = 1 + the number of columns
+ * l != i that precede j, so 1 <= rank <= n - 1 and ties go to the lower index.  One pass over the n^2 distances per 24 list
+ * entries: nothing of size n^2 is stored.  Same conventions as the DBSCAN entries: asynchronous on hip_stream, scratch allocated
+ * and freed on that stream, integer atomics only (bitwise reproducible call to call and across streams), no workgroup waits for
+ * another, RA_ERR_ARG with nothing launched outside the domain: 2 <= n <= 262144, 1 <= d <= 2048, 1 <= k <= 301 (k is not tied to
+ * n: a list may come from anywhere and may repeat an entry).
+ *   ra_embed_ranks  d_idx [n][k]: a list per row, e.g. ra_tsne_knn's on another space.  d_rank [n][k] = rank(i, d_idx[i][t]); an
+ *                   entry outside 0 .. n - 1, or equal to i, is invalid, addresses nothing and gets rank 0.  d_pen [n] =
+ *                   sum_t max(0, d_rank[i][t] - k), the penalty of trustworthiness; an invalid entry adds nothing.  Either output
+ *                   may be NULL, not both; the other's bits do not depend on it. */
+int  ra_embed_ranks(const float *d_x, int n, int d, const int *d_idx, int k, int *d_rank, long long *d_pen, void *hip_stream);
+
 /* block until the engine's stream is idle */
 int  ra_sync(ra_engine *e);
 
