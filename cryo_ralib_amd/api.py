@@ -84,7 +84,7 @@ EXPORTED_SYMBOLS = [
     "ra_tsne_knn_query", "ra_tsne_affinity_rows", "ra_tsne_place_gradient", "ra_tsne_place",
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
-    "ra_hdbscan_core", "ra_hdbscan_round", "ra_embed_ranks",
+    "ra_hdbscan_core", "ra_hdbscan_round", "ra_ward_nearest", "ra_ward_merge", "ra_embed_ranks",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
     "ra_prep_normalize", "ra_prep_filter",
 ]
@@ -223,6 +223,8 @@ def load_library(path=None):
     L.ra_dbscan_step.argtypes = [vp, ci, ci, ctypes.c_double, vp, ci, vp, vp, vp, vp]
     L.ra_hdbscan_core.argtypes = [vp, ci, ci, ci, vp, vp]
     L.ra_hdbscan_round.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp]
+    L.ra_ward_nearest.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp]
+    L.ra_ward_merge.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp]
     L.ra_embed_ranks.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
@@ -479,6 +481,30 @@ def hdbscan(X, **kw):
     """HDBSCAN of X [n][d] (hdbscan.hdbscan): HdbscanResult with labels (-1 for noise), probabilities, tie_mask, n_clusters, ..."""
     from . import hdbscan as _hdbscan
     return _hdbscan.hdbscan(X, **kw)
+
+
+def ward(X, **kw):
+    """Ward clustering of X [n][d] (ward.ward): WardResult with labels, n_clusters, counts, centers and the tree."""
+    from . import ward as _ward
+    return _ward.ward(X, **kw)
+
+
+def ward_linkage(X, **kw):
+    """The Ward dendrogram of X [n][d] (ward.linkage): WardTree with Z (scipy's layout), children, heights, w2, n_rounds, ..."""
+    from . import ward as _ward
+    return _ward.linkage(X, **kw)
+
+
+def ward_cut(tree, **kw):
+    """int32 [n] labels of a WardTree cut at n_clusters or at distance_threshold (ward.cut)."""
+    from . import ward as _ward
+    return _ward.cut(tree, **kw)
+
+
+def ward_sweep(X, ks, **kw):
+    """One Ward tree, then its cut, inertia and the validity scores for every k of ks (ward.sweep)."""
+    from . import ward as _ward
+    return _ward.sweep(X, ks, **kw)
 
 
 def dbscan_kdistances(X, min_samples, **kw):

@@ -1,12 +1,14 @@
-// t-SNE, k-means, cluster validity, DBSCAN, HDBSCAN and embedding quality of 2SDR factors (ralign_tsne.h, ralign_kmeans.h,
-// ralign_validity.h, ralign_dbscan.h, ralign_hdbscan.h, ralign_quality.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_*,
-// ra_hdbscan_* and ra_embed_* entry points of libralign_hip.so, each on the caller's stream.
+// t-SNE, k-means, cluster validity, DBSCAN, HDBSCAN, Ward agglomeration and embedding quality of 2SDR factors (ralign_tsne.h,
+// ralign_kmeans.h, ralign_validity.h, ralign_dbscan.h, ralign_hdbscan.h, ralign_ward.h, ralign_quality.h): the engine-less
+// ra_tsne_*, ra_kmeans_*, ra_dbscan_*, ra_hdbscan_*, ra_ward_* and ra_embed_* entry points of libralign_hip.so, each on the
+// caller's stream.
 #include "ralign_host.h"
 #include "ralign_scratch.h"
 #include "ralign_kmeans.h"
 #include "ralign_validity.h"
 #include "ralign_dbscan.h"
 #include "ralign_hdbscan.h"
+#include "ralign_ward.h"
 #include "ralign_quality.h"
 
 using namespace ralign;
@@ -527,6 +529,59 @@ extern "C" int ra_hdbscan_round(const float *d_x, int n, int d, const double *d_
     RA_LAUNCH(he, hdb_out_kernel, dim3(nt), dim3(256), 0, stream, d_comp, n, (const unsigned long long *)cw, (const unsigned long long *)ce,
               d_w2, d_lo, d_hi);
     return he == hipSuccess ? RA_OK : hip_error("ra_hdbscan_round", he);
+}
+
+// ---- Ward agglomeration (ralign_ward.h)
+
+static bool ward_shape_ok(const char *what, int n, int d)
+{
+    if (n < 2 || n > WARD_MAX_N || d < 1 || d > WARD_MAX_D) {
+        set_error(std::string(what) + ": need 2 <= n <= 262144 and 1 <= d <= 2048");
+        return false;
+    }
+    return true;
+}
+
+extern "C" int ra_ward_nearest(const double *d_c, const int *d_size, int n, int d, const int *d_rows, int n_rows, int *d_nn, double *d_w2,
+                               void *hip_stream)
+{
+    if (!ward_shape_ok("ra_ward_nearest", n, d)) return RA_ERR_ARG;
+    if (n_rows < 1 || n_rows > WARD_MAX_N) return arg_error("ra_ward_nearest: need 1 <= n_rows <= 262144");
+    if (!d_c || !d_size || !d_rows || !d_nn || !d_w2) return arg_error("ra_ward_nearest: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nt = (n + 255) / 256, cap = n + 2 * DBS_TC;
+    KmScratch S;
+    const KmLists M(S, n, 2, KM_BLOCK);
+    const size_t o_flag = S.take((size_t)n * 4), o_pstart = S.take(3 * 4), o_cols = S.take((size_t)cap * 4);
+    StreamScratch scratch(stream);
+    if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_ward_nearest", scratch.status());
+    int *flag = S.at<int>(o_flag), *cnt = M.cnt(), *start = M.start(), *mem = M.mem();
+    int *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols);
+    // the live slots in slot order: the member list of "cluster" 0 of the flags (size >= 1), padded to the column tile with -1
+    hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);
+    RA_LAUNCH(he, dbs_flag_kernel, dim3(nt), dim3(256), 0, stream, d_size, n, 1, flag);
+    if (he == hipSuccess) he = km_member_lists(flag, n, 2, km_run_len(n), M, stream);
+    RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, 2, pstart);
+    RA_LAUNCH(he, val_cols_kernel, dim3(nt), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt, (const int *)pstart,
+              n, 2, cap, cols);
+    RA_LAUNCH(he, ward_row_kernel, dim3((n_rows + WARD_TR - 1) / WARD_TR), dim3(256), 0, stream, d_c, d_size, n, d, d_rows, n_rows,
+              (const int *)cols, (const int *)pstart, d_nn, d_w2);
+    return he == hipSuccess ? RA_OK : hip_error("ra_ward_nearest", he);
+}
+
+extern "C" int ra_ward_merge(double *d_c, int *d_size, int n, int d, const int *d_a, const int *d_b, int n_pairs, void *hip_stream)
+{
+    if (!ward_shape_ok("ra_ward_merge", n, d)) return RA_ERR_ARG;
+    if (n_pairs < 1 || n_pairs > n / 2) return arg_error("ra_ward_merge: need 1 <= n_pairs <= n / 2 disjoint pairs");
+    if (!d_c || !d_size || !d_a || !d_b) return arg_error("ra_ward_merge: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const size_t work = (size_t)n_pairs * d;
+    hipLaunchKernelGGL(ward_merge_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, d_c, (const int *)d_size, n, d, d_a, d_b,
+                       n_pairs);
+    hipError_t he = hipGetLastError();
+    // the sizes change in a launch of their own: every thread of ward_merge_kernel has read them by then
+    RA_LAUNCH(he, ward_size_kernel, dim3((n_pairs + 255) / 256), dim3(256), 0, stream, d_size, n, d_a, d_b, n_pairs);
+    return he == hipSuccess ? RA_OK : hip_error("ra_ward_merge", he);
 }
 
 // ---- embedding quality (ralign_quality.h)

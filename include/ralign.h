@@ -601,6 +601,23 @@ int  ra_hdbscan_core(const float *d_x, int n, int d, int min_samples, double *d_
 int  ra_hdbscan_round(const float *d_x, int n, int d, const double *d_core2, const int *d_comp, double *d_w2, int *d_lo, int *d_hi,
                       void *hip_stream);
 
+/* Ward (minimum-variance) agglomeration: the two device parts of cryo_ralib_amd/ward.py, whose docstring holds the contract rule
+ * by rule.  The state is the cluster table in device memory: d_c [n][d] (double centroids) and d_size [n]
+ * (int; a slot with size <= 0 is dead).  D2 is ra_dbscan_count's chain on the centroids; W2(a, b) = (s_a s_b) / (s_a + s_b) D2, the
+ * sizes in double, symmetric bit for bit.  Nothing of size n^2 is stored.  Same conventions as the DBSCAN entries: asynchronous on
+ * hip_stream, scratch allocated and freed on that stream, no floating-point atomics (bitwise reproducible call to call and across
+ * streams), no workgroup waits for another, RA_ERR_ARG with nothing launched outside the domain: 2 <= n <= 262144, 1 <= d <= 2048.
+ *   ra_ward_nearest  d_rows [n_rows] (1 <= n_rows <= 262144) lists slots, in any order, repeats allowed.  By list position:
+ *                    d_nn = the live slot b != a that minimises (W2(a, b), b) (ties go to the lower slot), d_w2 = that W2.  A
+ *                    listed slot that is dead or outside 0 .. n - 1, or the only live one, gives -1 and +inf.  The list of the live
+ *                    columns is rebuilt from d_size on the device in every call.
+ *   ra_ward_merge    for each of the n_pairs (1 <= n_pairs <= n / 2) disjoint pairs a = d_a[p] < b = d_b[p]:
+ *                    c_a <- (s_a c_a + s_b c_b) / (s_a + s_b) (one fma, one divide per feature), s_a <- s_a + s_b, s_b <- 0.  A
+ *                    pair outside 0 <= a < b < n or with a dead member changes nothing.  The rounds are cryo_ralib_amd/ward.py. */
+int  ra_ward_nearest(const double *d_c, const int *d_size, int n, int d, const int *d_rows, int n_rows, int *d_nn, double *d_w2,
+                     void *hip_stream);
+int  ra_ward_merge(double *d_c, int *d_size, int n, int d, const int *d_a, const int *d_b, int n_pairs, void *hip_stream);
+
 /* Neighbour ranks for trustworthiness and continuity of an embedding (cryo_ralib_amd/quality.py, whose docstring holds the contract
  * rule by rule).  D2 is ra_dbscan_count's: double, from differences, the features in order, exactly
  * symmetric.  In the row of i, column l precedes column j iff (D2(i, l), l) < (D2(i, j), j); rank(i, j) = 1 + the number of columns
