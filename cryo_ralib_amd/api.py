@@ -85,6 +85,7 @@ EXPORTED_SYMBOLS = [
     "ra_kmeans_sqnorm", "ra_kmeans_labels", "ra_kmeans_lloyd", "ra_kmeans_search", "ra_kmeans_seed",
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
     "ra_hdbscan_core", "ra_hdbscan_round", "ra_ward_nearest", "ra_ward_merge", "ra_embed_ranks",
+    "ra_spectral_spmv", "ra_spectral_lanczos", "ra_spectral_ritz", "ra_spectral_components", "ra_spectral_work_bytes",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
     "ra_prep_normalize", "ra_prep_filter",
 ]
@@ -226,6 +227,12 @@ def load_library(path=None):
     L.ra_ward_nearest.argtypes = [vp, vp, ci, ci, vp, ci, vp, vp, vp]
     L.ra_ward_merge.argtypes = [vp, vp, ci, ci, vp, vp, ci, vp]
     L.ra_embed_ranks.argtypes = [vp, ci, ci, vp, ci, vp, vp, vp]
+    L.ra_spectral_spmv.argtypes = [vp, vp, vp, ci, vp, vp, vp]
+    L.ra_spectral_lanczos.argtypes = [vp, vp, vp, ci, vp, vp, ci, ci, ci, vp, vp, vp, vp]
+    L.ra_spectral_ritz.argtypes = [vp, ci, ci, ci, vp, ci, vp, vp]
+    L.ra_spectral_components.argtypes = [vp, vp, ci, vp, vp, vp]
+    L.ra_spectral_work_bytes.restype = ctypes.c_size_t
+    L.ra_spectral_work_bytes.argtypes = [ci, ci]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -505,6 +512,24 @@ def ward_sweep(X, ks, **kw):
     """One Ward tree, then its cut, inertia and the validity scores for every k of ks (ward.sweep)."""
     from . import ward as _ward
     return _ward.sweep(X, ks, **kw)
+
+
+def spectral_embedding(X, **kw):
+    """Spectral embedding (diffusion map) of X [n][d] (spectral.embedding): SpectralResult with embedding, eigenvalues, residuals, ..."""
+    from . import spectral as _spectral
+    return _spectral.embedding(X, **kw)
+
+
+def spectral_cluster(X, n_clusters, **kw):
+    """Spectral clustering of X [n][d] (spectral.cluster): labels (-1 outside the embedded component), the embedding and the k-means result."""
+    from . import spectral as _spectral
+    return _spectral.cluster(X, n_clusters, **kw)
+
+
+def spectral_graph(X, **kw):
+    """The symmetric kNN graph of X [n][d] (spectral.graph): (indptr, indices, a, component)."""
+    from . import spectral as _spectral
+    return _spectral.graph(X, **kw)
 
 
 def dbscan_kdistances(X, min_samples, **kw):

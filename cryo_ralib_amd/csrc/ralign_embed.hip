@@ -1,7 +1,7 @@
-// t-SNE, k-means, cluster validity, DBSCAN, HDBSCAN, Ward agglomeration and embedding quality of 2SDR factors (ralign_tsne.h,
-// ralign_kmeans.h, ralign_validity.h, ralign_dbscan.h, ralign_hdbscan.h, ralign_ward.h, ralign_quality.h): the engine-less
-// ra_tsne_*, ra_kmeans_*, ra_dbscan_*, ra_hdbscan_*, ra_ward_* and ra_embed_* entry points of libralign_hip.so, each on the
-// caller's stream.
+// t-SNE, k-means, cluster validity, DBSCAN, HDBSCAN, Ward agglomeration, embedding quality and spectral embedding of 2SDR factors
+// (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h, ralign_dbscan.h, ralign_hdbscan.h, ralign_ward.h, ralign_quality.h,
+// ralign_spectral.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_*, ra_hdbscan_*, ra_ward_*, ra_embed_* and ra_spectral_*
+// entry points of libralign_hip.so, each on the caller's stream.
 #include "ralign_host.h"
 #include "ralign_scratch.h"
 #include "ralign_kmeans.h"
@@ -10,6 +10,7 @@
 #include "ralign_hdbscan.h"
 #include "ralign_ward.h"
 #include "ralign_quality.h"
+#include "ralign_spectral.h"
 
 using namespace ralign;
 
@@ -605,4 +606,107 @@ extern "C" int ra_embed_ranks(const float *d_x, int n, int d, const int *d_idx, 
     hipError_t he = hipGetLastError();
     RA_LAUNCH(he, emb_rank_kernel, dim3((n + DBS_TR - 1) / DBS_TR), dim3(256), lds, stream, a);
     return he == hipSuccess ? RA_OK : hip_error("ra_embed_ranks", he);
+}
+
+// ---- spectral embedding (ralign_spectral.h)
+
+extern "C" int ra_spectral_spmv(const int *d_indptr, const int *d_indices, const double *d_val, int n, const double *d_x, double *d_y,
+                                void *hip_stream)
+{
+    if (n < 1 || n > SPEC_MAX_N) return arg_error("ra_spectral_spmv: need 1 <= n <= 262144");
+    if (!d_indptr || !d_indices || !d_val || !d_x || !d_y || d_x == d_y) return arg_error("ra_spectral_spmv: null argument, or d_y == d_x");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + SPEC_ROWS - 1) / SPEC_ROWS;
+    StreamScratch scratch(stream);
+    int *bad = scratch.get<int>(1);
+    if (!bad) return hip_error("ra_spectral_spmv", scratch.status());
+    // the one entry that reads back: a CSR that the kernel would have to patch is refused before y is touched
+    hipError_t he = hipMemsetAsync(bad, 0, sizeof(int), stream);
+    RA_LAUNCH(he, spec_check_kernel, dim3(nb), dim3(256), 0, stream, d_indptr, d_indices, n, bad);
+    int h_bad = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) return hip_error("ra_spectral_spmv", he);
+    if (h_bad) return arg_error("ra_spectral_spmv: indptr does not ascend from 0, or a column index is outside 0 .. n - 1");
+    hipLaunchKernelGGL(spec_spmv_kernel, dim3(nb), dim3(256), 0, stream, d_indptr, d_indices, d_val, n, d_x, d_y);
+    he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_spectral_spmv", he);
+}
+
+// the pieces of ra_spectral_lanczos' work buffer for a basis of at most `cols` columns of Q
+struct SpecWork {
+    KmScratch S;
+    int runs, nup;
+    size_t o_w, o_part, o_h, o_np;
+    SpecWork(int n, int cols)
+        : runs((n + SPEC_RUN - 1) / SPEC_RUN), nup((n + SPEC_UPD - 1) / SPEC_UPD), o_w(S.take((size_t)n * 8)),
+          o_part(S.take((size_t)runs * cols * 8)), o_h(S.take((size_t)cols * 8)), o_np(S.take((size_t)nup * 8)) {}
+};
+
+extern "C" size_t ra_spectral_work_bytes(int n, int basis)
+{
+    if (n < 2 || n > SPEC_MAX_N || basis < 1 || basis > SPEC_MAX_M) return 0;
+    return SpecWork(n, basis + 1).S.off;
+}
+
+extern "C" int ra_spectral_lanczos(const int *d_indptr, const int *d_indices, const double *d_val, int n, const double *d_q0, double *d_V,
+                                   int ldv, int j0, int steps, double *d_alpha, double *d_beta, void *d_work, void *hip_stream)
+{
+    if (n < 2 || n > SPEC_MAX_N || ldv < n || j0 < 0 || steps < 1 || j0 > SPEC_MAX_M || steps > SPEC_MAX_M || j0 + steps > SPEC_MAX_M)
+        return arg_error("ra_spectral_lanczos: need 2 <= n <= 262144, ldv >= n, j0 >= 0, steps >= 1 and j0 + steps <= 4096");
+    if (!d_indptr || !d_indices || !d_val || !d_q0 || !d_V || !d_alpha || !d_beta || !d_work || ((size_t)d_work & 255))
+        return arg_error("ra_spectral_lanczos: null argument, or a work buffer that is not 256-byte aligned");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    SpecWork W(n, j0 + steps + 1);                  // ra_spectral_work_bytes(n, j0 + steps)
+    W.S.base = (unsigned char *)d_work;
+    double *w = W.S.at<double>(W.o_w), *part = W.S.at<double>(W.o_part), *h = W.S.at<double>(W.o_h), *np = W.S.at<double>(W.o_np);
+    const int nb = (n + SPEC_ROWS - 1) / SPEC_ROWS, nt = (n + 255) / 256;
+    hipError_t he = hipSuccess;
+    for (int j = j0; j < j0 + steps && he == hipSuccess; j++) {
+        const int cols = j + 2;
+        const double *vj = d_V + (size_t)j * ldv;
+        const dim3 gd(W.runs, (cols + SPEC_CT - 1) / SPEC_CT);
+        RA_LAUNCH(he, spec_spmv_kernel, dim3(nb), dim3(256), 0, stream, d_indptr, d_indices, d_val, n, vj, w);
+        for (int pass = 0; pass < 2; pass++) {
+            RA_LAUNCH(he, spec_dots_kernel, gd, dim3(256), 0, stream, d_q0, (const double *)d_V, ldv, cols, (const double *)w, n, part);
+            RA_LAUNCH(he, spec_reduce_kernel, dim3((cols + 255) / 256), dim3(256), 0, stream, (const double *)part, W.runs, cols, h,
+                      pass == 0 ? d_alpha + j : (double *)nullptr);
+            RA_LAUNCH(he, spec_update_kernel, dim3(W.nup), dim3(SPEC_UPD), 0, stream, d_q0, (const double *)d_V, ldv, cols, (const double *)h,
+                      w, n, pass == 1 ? np : (double *)nullptr);
+        }
+        RA_LAUNCH(he, spec_norm_kernel, dim3(1), dim3(256), 0, stream, (const double *)np, W.nup, d_beta + j);
+        RA_LAUNCH(he, spec_scale_kernel, dim3(nt), dim3(256), 0, stream, (const double *)w, n, (const double *)(d_beta + j),
+                  d_V + (size_t)(j + 1) * ldv);
+    }
+    return he == hipSuccess ? RA_OK : hip_error("ra_spectral_lanczos", he);
+}
+
+extern "C" int ra_spectral_ritz(const double *d_V, int ldv, int m, int n, const double *d_S, int c, double *d_Y, void *hip_stream)
+{
+    if (n < 1 || n > SPEC_MAX_N || ldv < n || m < 1 || m > SPEC_MAX_M || c < 1 || c > SPEC_MAX_C)
+        return arg_error("ra_spectral_ritz: need 1 <= n <= 262144, ldv >= n, 1 <= m <= 4096 and 1 <= c <= 64");
+    if (!d_V || !d_S || !d_Y) return arg_error("ra_spectral_ritz: null argument");
+    hipLaunchKernelGGL(spec_ritz_kernel, dim3((n + 255) / 256, (c + SPEC_RT - 1) / SPEC_RT), dim3(256), 0, (hipStream_t)hip_stream, d_V, ldv,
+                       m, n, d_S, c, d_Y);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_spectral_ritz", he);
+}
+
+extern "C" int ra_spectral_components(const int *d_indptr, const int *d_indices, int n, int *d_label, int *d_changed, void *hip_stream)
+{
+    if (n < 1 || n > SPEC_MAX_N) return arg_error("ra_spectral_components: need 1 <= n <= 262144");
+    if (!d_indptr || !d_indices || !d_label || !d_changed) return arg_error("ra_spectral_components: null argument");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nt = (n + 255) / 256;
+    KmScratch S;
+    const size_t o_m = S.take((size_t)n * 4), o_p = S.take((size_t)n * 4);
+    StreamScratch scratch(stream);
+    if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_spectral_components", scratch.status());
+    int *m = S.at<int>(o_m), *P = S.at<int>(o_p);
+    hipError_t he = hipMemsetAsync(d_changed, 0, sizeof(int), stream);
+    RA_LAUNCH(he, spec_min_kernel, dim3((n + SPEC_ROWS - 1) / SPEC_ROWS), dim3(256), 0, stream, d_indptr, d_indices, n, (const int *)d_label, m);
+    if (he == hipSuccess) he = hipMemcpyAsync(P, d_label, (size_t)n * 4, hipMemcpyDeviceToDevice, stream);
+    RA_LAUNCH(he, spec_hook_kernel, dim3(nt), dim3(256), 0, stream, n, (const int *)d_label, (const int *)m, P);
+    RA_LAUNCH(he, spec_compress_kernel, dim3(nt), dim3(256), 0, stream, n, (const int *)P, d_label, d_changed);
+    return he == hipSuccess ? RA_OK : hip_error("ra_spectral_components", he);
 }

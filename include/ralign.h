@@ -618,6 +618,36 @@ int  ra_ward_nearest(const double *d_c, const int *d_size, int n, int d, const i
                      void *hip_stream);
 int  ra_ward_merge(double *d_c, int *d_size, int n, int d, const int *d_a, const int *d_b, int n_pairs, void *hip_stream);
 
+/* Spectral embedding (Laplacian eigenmaps / diffusion maps) of a symmetric kNN graph: the device parts of
+ * cryo_ralib_amd/spectral.py, whose docstring holds the contract rule by rule.  Everything is double.  The
+ * operator is a CSR (d_indptr [n + 1], d_indices, d_val) with the columns of a row ascending; the basis is d_V [m + 1][ldv] (vector j
+ * is row j, ldv >= n) and d_q0 [n] the known top eigenvector.  Same conventions as the DBSCAN entries: asynchronous on hip_stream
+ * (ra_spectral_spmv alone reads one int back), no floating-point atomics, every sum in an order fixed by the sizes alone (bitwise
+ * reproducible call to call and across streams), no workgroup waits for another, every column index range-checked before it
+ * addresses anything, RA_ERR_ARG with nothing launched outside the domain: n <= 262144, at most 4096 basis vectors, c <= 64.
+ *   ra_spectral_spmv        y = A x, 1 <= n.  16 lanes share a row: lane l adds the entries l, l + 16, ... in order by fma, then the
+ *                           lanes combine in a fixed tree, so the order of a row's sum depends on its length only; an empty row
+ *                           gives 0.  The CSR is checked on the device first: an indptr that does not ascend from 0 or a column
+ *                           outside 0 .. n - 1 returns RA_ERR_ARG with d_y untouched.  d_y != d_x.
+ *   ra_spectral_work_bytes  the size of ra_spectral_lanczos' d_work for a call with j0 + steps <= basis; 0 outside the domain.
+ *   ra_spectral_lanczos     enqueues `steps` Lanczos steps from basis vector j0 (2 <= n, j0 + steps <= 4096) with no host
+ *                           synchronisation.  Step j: w = M v_j; twice h = Q^T w (partial dots [runs of 512 rows][j + 2], then
+ *                           the runs in run order), w -= Q h (t order) with Q = [q0, v_0 .. v_j]; d_alpha[j] = v_j . w = h[j + 1]
+ *                           of the first pass; d_beta[j] = |w|; v_{j+1} = w / d_beta[j], read from device memory by the scaling
+ *                           kernel (zeros when d_beta[j] <= 2^-40, so a breakdown leaves finite values behind it).  d_work is
+ *                           256-byte aligned.  The operator is not checked: an entry with a column out of range is skipped.
+ *   ra_spectral_ritz        d_Y [c][n]: Y_t = sum_j d_S[j][t] V_j in j order (d_S [m][c]), one writer per element.
+ *   ra_spectral_components  one round of minimum-label hooking over the CSR plus pointer compression, in place on d_label [n]
+ *                           (start from d_label[i] = i), integer atomicMin only; d_changed[0] = the number of labels that moved.
+ *                           Call until it is 0: d_label[i] is then the lowest member of i's component. */
+int  ra_spectral_spmv(const int *d_indptr, const int *d_indices, const double *d_val, int n, const double *d_x, double *d_y,
+                      void *hip_stream);
+size_t ra_spectral_work_bytes(int n, int basis);
+int  ra_spectral_lanczos(const int *d_indptr, const int *d_indices, const double *d_val, int n, const double *d_q0, double *d_V, int ldv,
+                         int j0, int steps, double *d_alpha, double *d_beta, void *d_work, void *hip_stream);
+int  ra_spectral_ritz(const double *d_V, int ldv, int m, int n, const double *d_S, int c, double *d_Y, void *hip_stream);
+int  ra_spectral_components(const int *d_indptr, const int *d_indices, int n, int *d_label, int *d_changed, void *hip_stream);
+
 /* Neighbour ranks for trustworthiness and continuity of an embedding (cryo_ralib_amd/quality.py, whose docstring holds the contract
  * rule by rule).  D2 is ra_dbscan_count's: double, from differences, the features in order, exactly
  * symmetric.  In the row of i, column l precedes column j iff (D2(i, l), l) < (D2(i, j), j); rank(i, j) = 1 + the number of columns
