@@ -86,6 +86,7 @@ EXPORTED_SYMBOLS = [
     "ra_kmeans_silhouette", "ra_kmeans_dispersion", "ra_gmm_estep", "ra_gmm_mstep", "ra_dbscan_count", "ra_dbscan_step",
     "ra_hdbscan_core", "ra_hdbscan_round", "ra_ward_nearest", "ra_ward_merge", "ra_embed_ranks",
     "ra_spectral_spmv", "ra_spectral_lanczos", "ra_spectral_ritz", "ra_spectral_components", "ra_spectral_work_bytes",
+    "ra_umap_smooth_knn", "ra_umap_epochs", "ra_umap_place",
     "ra_fourier_resize", "ra_wiener_accumulate", "ra_wiener_finalize", "ra_wiener_frc", "ra_wiener_finalize_ssnr", "ra_wiener_score",
     "ra_prep_normalize", "ra_prep_filter",
 ]
@@ -233,6 +234,10 @@ def load_library(path=None):
     L.ra_spectral_components.argtypes = [vp, vp, ci, vp, vp, vp]
     L.ra_spectral_work_bytes.restype = ctypes.c_size_t
     L.ra_spectral_work_bytes.argtypes = [ci, ci]
+    cd, cu64 = ctypes.c_double, ctypes.c_uint64
+    L.ra_umap_smooth_knn.argtypes = [vp, ci, ci, ci, vp, vp, vp, vp]
+    L.ra_umap_epochs.argtypes = [vp, vp, ci, vp, vp, vp, ci, cd, cd, cd, ci, cd, ci, ci, ci, cu64, vp]
+    L.ra_umap_place.argtypes = [vp, ci, ctypes.c_longlong, vp, ci, vp, vp, ci, cd, cd, cd, ci, cd, ci, cu64, vp]
     L.ra_legacy_bytes.restype = ctypes.c_size_t
     L.ra_legacy_bytes.argtypes = [ctypes.c_uint, ctypes.POINTER(AlignConfig)]
     if path is None:
@@ -530,6 +535,24 @@ def spectral_graph(X, **kw):
     """The symmetric kNN graph of X [n][d] (spectral.graph): (indptr, indices, a, component)."""
     from . import spectral as _spectral
     return _spectral.graph(X, **kw)
+
+
+def umap(X, **kw):
+    """UMAP embedding of X [n][d] (umap.umap): UmapResult with embedding [n][2], graph, a, b, n_epochs, init."""
+    from . import umap as _umap
+    return _umap.umap(X, **kw)
+
+
+def umap_transform(X_new, X_fit, Y_fit, **kw):
+    """Place X_new into the UMAP embedding Y_fit of X_fit (umap.transform)."""
+    from . import umap as _umap
+    return _umap.transform(X_new, X_fit, Y_fit, **kw)
+
+
+def umap_fuzzy_graph(X, **kw):
+    """The fuzzy simplicial set of X [n][d] (umap.fuzzy_graph): (indptr, indices, s, rho, sigma)."""
+    from . import umap as _umap
+    return _umap.fuzzy_graph(X, **kw)
 
 
 def dbscan_kdistances(X, min_samples, **kw):

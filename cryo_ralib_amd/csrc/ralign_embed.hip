@@ -1,7 +1,7 @@
-// t-SNE, k-means, cluster validity, DBSCAN, HDBSCAN, Ward agglomeration, embedding quality and spectral embedding of 2SDR factors
-// (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h, ralign_dbscan.h, ralign_hdbscan.h, ralign_ward.h, ralign_quality.h,
-// ralign_spectral.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_*, ra_hdbscan_*, ra_ward_*, ra_embed_* and ra_spectral_*
-// entry points of libralign_hip.so, each on the caller's stream.
+// t-SNE, k-means, cluster validity, DBSCAN, HDBSCAN, Ward agglomeration, embedding quality, spectral embedding and UMAP of 2SDR
+// factors (ralign_tsne.h, ralign_kmeans.h, ralign_validity.h, ralign_dbscan.h, ralign_hdbscan.h, ralign_ward.h, ralign_quality.h,
+// ralign_spectral.h, ralign_umap.h): the engine-less ra_tsne_*, ra_kmeans_*, ra_dbscan_*, ra_hdbscan_*, ra_ward_*, ra_embed_*,
+// ra_spectral_* and ra_umap_* entry points of libralign_hip.so, each on the caller's stream.
 #include "ralign_host.h"
 #include "ralign_scratch.h"
 #include "ralign_kmeans.h"
@@ -11,6 +11,7 @@
 #include "ralign_ward.h"
 #include "ralign_quality.h"
 #include "ralign_spectral.h"
+#include "ralign_umap.h"
 
 using namespace ralign;
 
@@ -709,4 +710,84 @@ extern "C" int ra_spectral_components(const int *d_indptr, const int *d_indices,
     RA_LAUNCH(he, spec_hook_kernel, dim3(nt), dim3(256), 0, stream, n, (const int *)d_label, (const int *)m, P);
     RA_LAUNCH(he, spec_compress_kernel, dim3(nt), dim3(256), 0, stream, n, (const int *)P, d_label, d_changed);
     return he == hipSuccess ? RA_OK : hip_error("ra_spectral_components", he);
+}
+
+// ---- UMAP (ralign_umap.h)
+
+extern "C" int ra_umap_smooth_knn(const double *d_dist2, int rows, int k, int n_neighbors, double *d_rho, double *d_sigma, double *d_w,
+                                  void *hip_stream)
+{
+    if (rows < 1 || rows > UMAP_MAX_ROWS || k < 1 || k > UMAP_MAX_K || n_neighbors < 2 || n_neighbors > UMAP_MAX_K + 1)
+        return arg_error("ra_umap_smooth_knn: need 1 <= rows <= 4194304, 1 <= k <= 301 and 2 <= n_neighbors <= 302");
+    if (!d_dist2 || !d_rho || !d_sigma || !d_w) return arg_error("ra_umap_smooth_knn: null argument");
+    hipLaunchKernelGGL(umap_smooth_kernel, dim3((rows + UMAP_SK_ROWS - 1) / UMAP_SK_ROWS), dim3(256), 0, (hipStream_t)hip_stream, d_dist2,
+                       rows, k, std::log2((double)n_neighbors), d_rho, d_sigma, d_w);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_umap_smooth_knn", he);
+}
+
+static bool umap_curve_ok(const char *what, double a, double b, double gamma, int neg, double lr, int n_epochs, UmapCurve &c)
+{
+    if (!std::isfinite(a) || !(a > 0.0) || !std::isfinite(b) || !(b > 0.0) || !std::isfinite(gamma) || !(gamma >= 0.0) || neg < 0 ||
+        neg > UMAP_MAX_NEG || !std::isfinite(lr) || !(lr > 0.0) || n_epochs < 1 || n_epochs > UMAP_MAX_EPOCHS) {
+        set_error(std::string(what) + ": need finite a > 0, b > 0, gamma >= 0 and lr > 0, 0 <= negatives <= 16 and 1 <= n_epochs <= 10000");
+        return false;
+    }
+    c.a = a; c.b = b; c.m2ab = (-2.0 * a) * b; c.g2b = (2.0 * gamma) * b;
+    return true;
+}
+
+extern "C" int ra_umap_epochs(float *d_y, float *d_y_alt, int n, const int *d_indptr, const int *d_indices, const double *d_rate, int nnz,
+                              double a, double b, double gamma, int neg, double lr, int n_epochs, int epoch0, int count,
+                              unsigned long long seed, void *hip_stream)
+{
+    UmapEpochArgs e;
+    if (n < 4 || n > UMAP_MAX_N || nnz < 0 || (long long)nnz > 2LL * n * UMAP_MAX_K)
+        return arg_error("ra_umap_epochs: need 4 <= n <= 262144 and 0 <= nnz <= 2 n 301");
+    if (!umap_curve_ok("ra_umap_epochs", a, b, gamma, neg, lr, n_epochs, e.c)) return RA_ERR_ARG;
+    if (epoch0 < 1 || count < 1 || epoch0 > n_epochs || count > n_epochs - epoch0 + 1)
+        return arg_error("ra_umap_epochs: need epoch0 >= 1, count >= 1 and epoch0 + count - 1 <= n_epochs");
+    if (!d_y || !d_y_alt || d_y == d_y_alt || !d_indptr || (nnz > 0 && (!d_indices || !d_rate)))
+        return arg_error("ra_umap_epochs: null argument, or d_y_alt == d_y (an epoch reads every y_j while it writes)");
+    hipStream_t stream = (hipStream_t)hip_stream;
+    const int nb = (n + UMAP_ROWS - 1) / UMAP_ROWS;
+    StreamScratch scratch(stream);
+    int *bad = scratch.get<int>(1);
+    if (!bad) return hip_error("ra_umap_epochs", scratch.status());
+    // the one read of the call: a CSR that the kernel would have to patch is refused before a position is written
+    hipError_t he = hipMemsetAsync(bad, 0, sizeof(int), stream);
+    RA_LAUNCH(he, umap_check_kernel, dim3(nb), dim3(256), 0, stream, d_indptr, d_indices, n, nnz, bad);
+    int h_bad = 0;
+    if (he == hipSuccess) he = hipMemcpyAsync(&h_bad, bad, sizeof(int), hipMemcpyDeviceToHost, stream);
+    if (he == hipSuccess) he = hipStreamSynchronize(stream);
+    if (he != hipSuccess) return hip_error("ra_umap_epochs", he);
+    if (h_bad) return arg_error("ra_umap_epochs: indptr does not ascend from 0 to nnz, or a column index is outside 0 .. n - 1");
+    e.indptr = d_indptr; e.indices = d_indices; e.rate = d_rate; e.n = n; e.neg = neg;
+    for (int s = 0; s < count && he == hipSuccess; s++) {
+        const int t = epoch0 + s;
+        e.y = (const float2 *)(s % 2 ? d_y_alt : d_y);
+        e.y_out = (float2 *)(s % 2 ? d_y : d_y_alt);
+        e.t = t;
+        e.alpha = lr * (1.0 - (double)(t - 1) / (double)n_epochs);
+        e.key = seed * UMAP_KEY_SEED + (unsigned long long)t * UMAP_KEY_EPOCH;
+        RA_LAUNCH(he, umap_epoch_kernel, dim3(nb), dim3(256), 0, stream, e);
+    }
+    return he == hipSuccess ? RA_OK : hip_error("ra_umap_epochs", he);
+}
+
+extern "C" int ra_umap_place(float *d_y, int n_new, long long row0, const float *d_yfit, int m, const int *d_idx, const double *d_rate, int k,
+                             double a, double b, double gamma, int neg, double lr, int n_epochs, unsigned long long seed, void *hip_stream)
+{
+    UmapPlaceArgs p;
+    if (n_new < 1 || n_new > UMAP_MAX_ROWS || row0 < 0 || row0 > UMAP_MAX_ROW0 - n_new || m < 2 || m > UMAP_MAX_N || k < 1 ||
+        k > std::min(m, UMAP_MAX_K))
+        return arg_error("ra_umap_place: need 1 <= n_new <= 4194304, row0 >= 0, row0 + n_new <= 2^48, 2 <= m <= 262144 and 1 <= k <= min(m, 301)");
+    if (!umap_curve_ok("ra_umap_place", a, b, gamma, neg, lr, n_epochs, p.c)) return RA_ERR_ARG;
+    if (!d_y || !d_yfit || !d_idx || !d_rate) return arg_error("ra_umap_place: null argument");
+    p.y = (float2 *)d_y; p.yfit = (const float2 *)d_yfit; p.idx = d_idx; p.rate = d_rate;
+    p.n = n_new; p.m = m; p.k = k; p.neg = neg; p.n_epochs = n_epochs;
+    p.row0 = (unsigned long long)row0; p.seed_key = seed * UMAP_KEY_SEED; p.lr = lr;
+    hipLaunchKernelGGL(umap_place_kernel, dim3((n_new + UMAP_ROWS - 1) / UMAP_ROWS), dim3(256), 0, (hipStream_t)hip_stream, p);
+    const hipError_t he = hipGetLastError();
+    return he == hipSuccess ? RA_OK : hip_error("ra_umap_place", he);
 }

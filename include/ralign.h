@@ -648,6 +648,36 @@ int  ra_spectral_lanczos(const int *d_indptr, const int *d_indices, const double
 int  ra_spectral_ritz(const double *d_V, int ldv, int m, int n, const double *d_S, int c, double *d_Y, void *hip_stream);
 int  ra_spectral_components(const int *d_indptr, const int *d_indices, int n, int *d_label, int *d_changed, void *hip_stream);
 
+/* UMAP of a kNN graph: the device parts of cryo_ralib_amd/umap.py, whose docstring holds the contract rule by rule (DESIGN.md section
+ * 4.22).  Positions are float32 [n][2], every sum is double.  Same conventions as the spectral entries: asynchronous on hip_stream
+ * (ra_umap_epochs alone reads one int back, before its first launch), no atomics on positions, every sum in an order fixed by the
+ * row's length alone, samples from a counter-based generator keyed by (seed, epoch, entry, sample): bitwise reproducible call to call
+ * and across streams.  No workgroup waits for another; every index read from memory is range-checked before it addresses anything;
+ * RA_ERR_ARG with nothing launched outside the domain.
+ *   ra_umap_smooth_knn  rule 2 on d_dist2 [rows][k] (squared distances as ra_tsne_knn / ra_tsne_knn_query write them), 1 <= rows <=
+ *                       4194304, 1 <= k <= 301, target log2(n_neighbors), 2 <= n_neighbors <= 302: d_rho [rows], d_sigma [rows],
+ *                       d_w [rows][k].  One wave per row; psum adds lane l's entries l, l + 64, ... in order, then the lanes in the
+ *                       xor butterfly 1 .. 32; the mean behind sigma's floor is added in list order.
+ *   ra_umap_epochs      enqueues the epochs t = epoch0 .. epoch0 + count - 1 (1 <= epoch0, epoch0 + count - 1 <= n_epochs <= 10000)
+ *                       of rules 5 and 6 on the symmetric CSR (d_indptr [n + 1], d_indices, d_rate [nnz] = s / max s), 4 <= n <=
+ *                       262144, one launch per epoch and no host synchronisation between them.  Epoch s of the call reads d_y for
+ *                       even s and d_y_alt for odd s and writes the other: the result is in d_y_alt if count is odd, else in d_y.
+ *                       16 lanes share a row: lane l walks the entries l, l + 16, ... in order, then the lanes combine in the xor
+ *                       tree 8, 4, 2, 1.  The CSR is checked on the device first: an indptr that does not ascend from 0 to nnz or a
+ *                       column outside 0 .. n - 1 returns RA_ERR_ARG with both buffers untouched.  0 <= negatives <= 16.
+ *   ra_umap_place       rule 8's optimisation of d_y [n_new][2] (in: the start; out: the result) against the fixed d_yfit [m][2]
+ *                       with the lists d_idx [n_new][k], d_rate [n_new][k] (w / max of the row), all n_epochs epochs in one launch.
+ *                       row0 is the global index of the call's first row (the samples' key), so a row's result does not depend on
+ *                       its batch.  1 <= n_new <= 4194304 rows a call, row0 >= 0 and row0 + n_new <= 2^48 (the key 16 ((row0 + i) k + slot)
+ *                       + s is formed in 64 bits), 2 <= m <= 262144, 1 <= k <= min(m, 301). */
+int  ra_umap_smooth_knn(const double *d_dist2, int rows, int k, int n_neighbors, double *d_rho, double *d_sigma, double *d_w,
+                        void *hip_stream);
+int  ra_umap_epochs(float *d_y, float *d_y_alt, int n, const int *d_indptr, const int *d_indices, const double *d_rate, int nnz, double a,
+                    double b, double gamma, int neg, double lr, int n_epochs, int epoch0, int count, unsigned long long seed,
+                    void *hip_stream);
+int  ra_umap_place(float *d_y, int n_new, long long row0, const float *d_yfit, int m, const int *d_idx, const double *d_rate, int k,
+                   double a, double b, double gamma, int neg, double lr, int n_epochs, unsigned long long seed, void *hip_stream);
+
 /* Neighbour ranks for trustworthiness and continuity of an embedding (cryo_ralib_amd/quality.py, whose docstring holds the contract
  * rule by rule).  D2 is ra_dbscan_count's: double, from differences, the features in order, exactly
  * symmetric.  In the row of i, column l precedes column j iff (D2(i, l), l) < (D2(i, j), j); rank(i, j) = 1 + the number of columns
