@@ -73,7 +73,7 @@ EXPORTED_SYMBOLS = [
     "pre_align_run", "pre_align_run_m", "mref_align_run", "mref_align_run_m", "get_num_ref", "reset_shifts",
     "ref_free_alignment_2D_init", "ref_free_alignment_2D_size_check", "ref_free_alignment_2D",
     "ref_free_alignment_2D_filter_references", "ra_isac_get_references", "ra_legacy_bytes",
-    "ra_last_error", "ra_create", "ra_destroy", "ra_set_stream", "ra_num_shifts", "ra_maxrin", "ra_lcirc", "ra_search_path", "ra_search_tiled", "ra_search_offsets_per_pass", "ra_set_nomirror", "ra_set_mask",
+    "ra_last_error", "ra_create", "ra_destroy", "ra_set_stream", "ra_num_shifts", "ra_maxrin", "ra_lcirc", "ra_search_path", "ra_search_tiled", "ra_search_l1_tap_rings", "ra_l1_tap_rule", "ra_search_offsets_per_pass", "ra_set_nomirror", "ra_set_mask",
     "ra_reset_shifts", "ra_set_references", "ra_get_prepared_references", "ra_align", "ra_state_from_params", "ra_set_refine", "ra_set_class_references", "ra_align_classes",
     "ra_debug_spectra", "ra_transform_accumulate", "ra_update_references", "ra_normalize_particles", "ra_sync", "ra_kernel_time",
     "ra_fsc_len", "ra_class_fsc", "ra_last_class_fsc", "ra_fit_tanh", "ra_class_averages", "ra_filter_references",
@@ -124,6 +124,9 @@ def load_library(path=None):
     L.ra_lcirc.argtypes = [vp]
     L.ra_search_path.argtypes = [vp]
     L.ra_search_tiled.argtypes = [vp]
+    if hasattr(L, "ra_search_l1_tap_rings"):      # (an older build loaded through RALIGN_LIB for a side-by-side measurement has none)
+        L.ra_search_l1_tap_rings.argtypes = [vp]
+        L.ra_l1_tap_rule.argtypes = [ctypes.c_int] * 4 + [ctypes.c_float] * 2
     L.ra_search_skips_offsets.argtypes = [vp]
     L.ra_search_offsets_per_pass.argtypes = [vp]
     L.ra_set_nomirror.argtypes = [vp, ctypes.c_int]
@@ -717,6 +720,12 @@ class Engine:
     @property
     def search_tiled(self):
         return bool(self.lib.ra_search_tiled(self.handle))
+
+    @property
+    def search_l1_tap_rings(self):
+        """search_fused_kernel: rings of at most this many samples (64 | 128) read their taps through the vector L1; 0: all from
+        LDS (ra_search_l1_tap_rings)"""
+        return self.lib.ra_search_l1_tap_rings(self.handle)
 
     @property
     def search_skips_offsets(self):

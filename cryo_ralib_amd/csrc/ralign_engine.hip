@@ -300,7 +300,7 @@ static gpolar_fn gpolar_kernel(const ra_engine *e, bool refs)
 }
 
 static fused_fn select_tiled(int nh, int sbuf);
-static fused_fn select_fused(int maxrin, int nref, int nzr, int sbuf, bool pack = false, bool crop = false);
+static fused_fn select_fused(int maxrin, int nref, int nzr, int sbuf, bool pack = false, bool crop = false, int tapl1 = 0);
 // search_tiled_kernel for an engine of the size-generic class: rings of 256 samples (ou <= 36) in a box so much larger than the rings
 // that the whole image does not fit next to four ring buffers, but a crop around the particle's sampling centre does (crop_plan,
 // ralign_solo.h).  Four offsets per pass with every wave in a ring job instead of the pair kernel's two: 1.6 x its rate.
@@ -791,11 +791,28 @@ static ccf_fn select_ccf(int maxrin)
     }
 }
 
-static fused_fn select_fused(int maxrin, int nref, int nzr, int sbuf, bool pack, bool crop)
+// the instantiations with the short rings' taps through the vector L1 (TAPL1 = 64 | 128): the family of the 90 x 90 boxes only --
+// rings of 256 samples, compile-time ring-buffer stride, one spectra round per pass, the whole image in LDS, up to 10 references
+static bool fused_tap_family(int maxrin, int nzr, int sbuf, bool crop) { return maxrin == 256 && nzr == 1 && sbuf == RF_SBUF_FIXED && !crop; }
+template <int TAPL1> static fused_fn select_fused_tap(int nrp, bool pack)
+{
+    switch ((nrp + 1) / 2) {
+    case 1: return pack ? search_fused_kernel<256, 1, true, RF_SBUF_FIXED, true, false, TAPL1> : search_fused_kernel<256, 1, true, RF_SBUF_FIXED, false, false, TAPL1>;
+    case 2: return pack ? search_fused_kernel<256, 2, true, RF_SBUF_FIXED, true, false, TAPL1> : search_fused_kernel<256, 2, true, RF_SBUF_FIXED, false, false, TAPL1>;
+    case 3: return pack ? search_fused_kernel<256, 3, true, RF_SBUF_FIXED, true, false, TAPL1> : search_fused_kernel<256, 3, true, RF_SBUF_FIXED, false, false, TAPL1>;
+    default: return nullptr;      // 13 and more references: no gain measured (14), not instantiated (setup_fused does not ask for it)
+    }
+}
+
+static fused_fn select_fused(int maxrin, int nref, int nzr, int sbuf, bool pack, bool crop, int tapl1)
 {
     if (nref > RF_MAXREF) return nullptr;
     const int nrp = (nref + 1) / 2;
     const bool one = nzr == 1;      // one store / inverse-FFT round per pass
+    if (tapl1) {
+        if (!fused_tap_family(maxrin, nzr, sbuf, crop)) return nullptr;
+        return tapl1 == 128 ? select_fused_tap<128>(nrp, pack) : tapl1 == 64 ? select_fused_tap<64>(nrp, pack) : nullptr;
+    }
     if (crop) {                     // the image in LDS is a crop (tcrop_wanted): run-time ring-buffer stride only
         if (maxrin != 256 || (pack && !one)) return nullptr;
         switch ((nrp + 1) / 2) {
@@ -916,10 +933,21 @@ static int setup_fused(ra_engine *e, const PlanRequest &rq)
         crop_plan(g, tcr, rq.sw.crop);
         fp.f.s_crop = tcr.s_crop; fp.f.s_cropm = tcr.s_cropm;
     }
+    // tap source of the short rings (l1_tap_rings): decided with every plan -- ra_create and ra_reset_shifts, whose new search range
+    // moves the sampling centres -- for the kernel family that has the instantiations
+    // (profiling builds: RALIGN_TAPL1 = 0 | 64 caps the setting; the probe of the LDS taps, RALIGN_DEBUG bit 16384, needs them all in LDS)
+    fp.tap_l1 = 0;
+    const int tap_cap = (e->dg.dbg & 16384) ? 0 : RA_EXP_ENV("RALIGN_TAPL1") ? ra_atoi(RA_EXP_ENV("RALIGN_TAPL1")) : kTapL1Cap;
+    // ... and for 2 to 5 reference pairs (3 - 10 references): where it was measured to win.  Against the LDS taps, at the 90 x 90
+    // headline geometry (profiles/tap_source_ab.txt): one pair (reference-free search, the class-resident launch) is 1.9 % SLOWER
+    // -- its short contraction leaves the pass to the ring jobs, which the waves with the L1 taps end --, 4 - 8 references gain
+    // 3 - 4 %, 10 gain 1.3 %, 14 nothing; 11 and 12 were not measured and keep the LDS taps
+    if (!e->tiled && fused_tap_family(g.maxrin, fp.f.nzr, e->dg.sbuf, e->tcrop) && fp.f.nrp >= 2 && fp.f.nrp <= 5)
+        fp.tap_l1 = l1_tap_rings(g.numr, g.nring, g.nx, g.last_ring, e->cfg.xrng, e->cfg.yrng, std::min(tap_cap, kTapL1Cap));
     int rc;
     if ((rc = upload_resident_tables(e))) return rc;
     for (int pk = 0; pk < (e->tiled ? 1 : 2); pk++) {
-        const fused_fn fk = e->tiled ? select_tiled(fp.f.nh, e->dg.sbuf) : select_fused(g.maxrin, e->cfg.nref, fp.f.nzr, e->dg.sbuf, pk != 0, e->tcrop);
+        const fused_fn fk = e->tiled ? select_tiled(fp.f.nh, e->dg.sbuf) : select_fused(g.maxrin, e->cfg.nref, fp.f.nzr, e->dg.sbuf, pk != 0, e->tcrop, fp.tap_l1);
         (pk ? e->search.pack : e->search.fused) = fk;
         if (!fk) continue;
         const std::string kn = std::string(e->tiled ? "search_tiled_kernel" : pk ? "search_fused_kernel<pack>" : "search_fused_kernel") + (e->tcrop ? " (crop)" : "");
@@ -1471,6 +1499,18 @@ extern "C" int ra_lds_report(const ra_engine *e, ra_lds_row *rows, int cap)
     return n;
 }
 extern "C" int ra_search_tiled(const ra_engine *e) { return !e ? RA_ERR_ARG : (e->fused && e->tiled) ? 1 : 0; }
+// the containment rule of ra_search_l1_tap_rings without an engine or a device: l1_tap_rings (ralign_plan.h) on the rings of the
+// geometry, whatever kernel family and reference count an engine would have
+extern "C" int ra_l1_tap_rule(int nx, int first_ring, int last_ring, int ring_skip, float xrng, float yrng)
+{
+    Geometry g;
+    if (nx < 1 || !build_rings(g, nx, first_ring, last_ring, ring_skip > 0 ? ring_skip : 1) || xrng < 0.f || yrng < 0.f) {
+        g_last_error = "bad ring or window arguments";
+        return RA_ERR_ARG;
+    }
+    return l1_tap_rings(g.numr, g.nring, nx, last_ring, xrng, yrng);
+}
+extern "C" int ra_search_l1_tap_rings(const ra_engine *e) { return !e ? RA_ERR_ARG : (e->fused && !e->tiled) ? e->fplan.tap_l1 : 0; }
 extern "C" int ra_search_path(const ra_engine *e) { return !e ? RA_ERR_ARG : e->solo ? 3 : e->fused ? 1 : e->generic ? 2 : 0; }
 extern "C" int ra_search_offsets_per_pass(const ra_engine *e) { return !e ? RA_ERR_ARG : !e->solo ? 0 : (e->duo || e->pair) ? 2 : 1; }
 extern "C" int ra_search_skips_offsets(const ra_engine *e) { return !e ? RA_ERR_ARG : (e->solo || e->dg.ent_base) ? 1 : 0; }

@@ -77,6 +77,8 @@ struct FusedPlanHost {
     std::vector<int> bsrc;
     std::vector<float> cdc_w;
     size_t lds_bytes = 0;
+    int tap_l1 = 0;                // search_fused_kernel's TAPL1 of this plan: rings of at most 64 | 128 samples take their taps through the vector
+                                   // L1, 0: all from LDS (l1_tap_rings, ralign_plan.h; set by the engine with every plan)
 };
 
 // B-stream source of (bin k, ring r, reference ref, Re/Im part): entry code or -1 (zero).  The Nyquist coefficient of
@@ -406,7 +408,11 @@ struct PassSync {
 // PACK: the offsets of consecutive particles of a workgroup fill the passes without padding (see the pass loop)
 // CROP: the LDS image is a crop around the particle's sampling centre (engines of the size-generic class, tcrop_wanted); a template
 // parameter because the run-time branch in load_image cost the 90 x 90 instantiations 0.7 % (two more registers, nine more spilled scalars)
-template <int N, int NRPW, bool ONE, int SB, bool PACK = false, bool CROP = false>
+// TAPL1: the ring jobs of rings of at most TAPL1 samples (64: the 64-sample and the mixed job, 128: the 128-sample job too) read their
+// taps from the particle's image in global memory, through the vector L1, instead of the LDS image (TAP_L1, ralign_kernels.h): the
+// LDS array, which bounds the sampling half of the ring jobs, loses their share of the tap reads.  Each instantiation holds every
+// job once, with one tap source.  The host picks it (l1_tap_rings, ralign_plan.h: no tap may leave the image); 0: every tap from LDS
+template <int N, int NRPW, bool ONE, int SB, bool PACK = false, bool CROP = false, int TAPL1 = 0>
 __global__ __launch_bounds__(RF_THREADS) void search_fused_kernel(DevGeom g_in, FusedGeom f, const float *__restrict__ particles,
                                                                   const float *__restrict__ state, int n,
                                                                   const float *__restrict__ Bf0, int nref,
@@ -414,6 +420,7 @@ __global__ __launch_bounds__(RF_THREADS) void search_fused_kernel(DevGeom g_in, 
 {
     // cls != null (class-resident mode, one reference): particle p is aligned to reference cls[p], whose B stream is
     // Bf0 + cls[p] * b_floats (pack_refs_fused_kernel with blockIdx.y = class)
+    static_assert(TAPL1 == 0 || (!CROP && (TAPL1 == 64 || TAPL1 == 128)), "taps through the L1: whole-image kernels, rings up to 64 or 128 samples");
     DevGeom g = g_in;
     g.maxrin = N; g.lg_maxrin = __builtin_ctz(N);      // the kernel is instantiated per maxrin: constants, not kernel arguments
     if constexpr (SB != 0) g.sbuf = SB;
@@ -528,8 +535,18 @@ __global__ __launch_bounds__(RF_THREADS) void search_fused_kernel(DevGeom g_in, 
         const int pk = particle_of(i);
         const Window wk = particle_window(g, state[2 * pk], state[2 * pk + 1]);
         const int si = min(sk, g.nshift - 1);
-        red[16 + 2 * k] = ((float)g.cnx + wk.sxi) + g.shift_x[si];
-        red[17 + 2 * k] = ((float)g.cnx + wk.syi) + g.shift_y[si];
+        float cx = ((float)g.cnx + wk.sxi) + g.shift_x[si], cy = ((float)g.cnx + wk.syi) + g.shift_y[si];
+        if constexpr (TAPL1 > 0) {
+            // the host's containment rule (l1_tap_rings) holds for centres within |mashi| + ceil(range) of the image centre, which
+            // the window rule and the offset list guarantee: the clamp changes no such value, and keeps a state that is not a number
+            // (which the window rule of RA_MODE_MREF lets through) from sending a global tap out of the image
+            const int mashi = abs(g.cnx - g.win_ring - 2);
+            const float mx = (float)(mashi + (int)ceilf(g.xrng)), my = (float)(mashi + (int)ceilf(g.yrng));
+            cx = fminf(fmaxf(cx, (float)g.cnx - mx), (float)g.cnx + mx);
+            cy = fminf(fmaxf(cy, (float)g.cnx - my), (float)g.cnx + my);
+        }
+        red[16 + 2 * k] = cx;
+        red[17 + 2 * k] = cy;
         red[7] = 0.f;
     };
     // this wave's job of round 0 is the same in every pass
@@ -590,6 +607,12 @@ __global__ __launch_bounds__(RF_THREADS) void search_fused_kernel(DevGeom g_in, 
                 }
                 const int slo = ph ? a : 0, shi = (split && !ph) ? a : nlive;
                 const bool wait = pend && !ph;
+                // tap bases of the jobs: the LDS image, or -- TAPL1 -- the image of this round's particle in global memory with the
+                // one-based origin folded in (wave-uniform: scalar registers)
+                constexpr int T128 = TAPL1 >= 128 ? TAP_L1 : TAP_LDS, T64 = TAPL1 >= 64 ? TAP_L1 : TAP_LDS;
+                const float *gimg = imgb;
+                if constexpr (TAPL1 > 0) gimg = particles + ((long long)particle_of(i0 + ph) * (g.nx * g.nx) - (g.nx + 1));
+                const float *tap128 = T128 == TAP_L1 ? gimg : imgb, *tap64 = T64 == TAP_L1 ? gimg : imgb;
 #pragma unroll 1
                 for (int jr = 0; jr * RF_WAVES < g.n_job; jr++) {
                     // jobs sorted longest first, dealt round robin: the SIMDs issue oldest-wave-first, so the first waves finish
@@ -603,10 +626,10 @@ __global__ __launch_bounds__(RF_THREADS) void search_fused_kernel(DevGeom g_in, 
                     const PassSync ps = {wait && jr == 0, ifft_done, done_target};
 #endif
                     switch (__builtin_amdgcn_readfirstlane(jd.x)) {
-                    case 1: ring_job<8, 8, true, true>(g, imgb, bufs, tw_s, qt_s, red + 16, red + 24, inst_s, instw_s, jd.y, jd.z, jd.w, g.sbuf, shi, ps, slo); break;
+                    case 1: ring_job<8, 8, true, true, T128>(g, tap128, bufs, tw_s, qt_s, red + 16, red + 24, inst_s, instw_s, jd.y, jd.z, jd.w, g.sbuf, shi, ps, slo); break;
                     case 6: ring_job<16, 8, true, true>(g, imgb, bufs, tw_s, qt_s, red + 16, red + 24, inst_s, instw_s, jd.y, jd.z, jd.w, g.sbuf, shi, ps, slo); break;
-                    case 7: ring_job<8, 4, true, true>(g, imgb, bufs, tw_s, qt_s, red + 16, red + 24, inst_s, instw_s, jd.y, jd.z, jd.w, g.sbuf, shi, ps, slo); break;
-                    case 9: ring_job_mix<true>(g, imgb, bufs, tw_s, qt_s, red + 16, red + 24, inst_s, instw_s, jd.y, jd.z, jd.w, g.sbuf, shi, ps, slo); break;
+                    case 7: ring_job<8, 4, true, true, T64>(g, tap64, bufs, tw_s, qt_s, red + 16, red + 24, inst_s, instw_s, jd.y, jd.z, jd.w, g.sbuf, shi, ps, slo); break;
+                    case 9: ring_job_mix<true, T64>(g, tap64, bufs, tw_s, qt_s, red + 16, red + 24, inst_s, instw_s, jd.y, jd.z, jd.w, g.sbuf, shi, ps, slo); break;
                     default: break;      // the fused job table holds codes 1, 6, 7 and 9 only (make_jobs with 4 offset slots)
                     }
                 }

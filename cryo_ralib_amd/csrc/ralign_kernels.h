@@ -235,6 +235,68 @@ __device__ __forceinline__ float bilinear_pad(const float *base, int st, float x
 #endif
 }
 
+// Where the four taps of a sample come from (template parameter of the ring jobs):
+//   TAP_LDS   the padded LDS image, bilinear_pad (the default: every kernel but the instantiations below)
+//   TAP_L1    the particle's image in global memory, through the CU's vector L1, bilinear_l1 (search_fused_kernel<..., TAPL1 > 0>,
+//             its short rings only)
+enum { TAP_LDS = 0, TAP_L1 = 1 };
+typedef float v2f_a4 __attribute__((ext_vector_type(2), aligned(4)));
+
+// bilinear_pad with the four taps from global memory: `base` = image - nx - 1 floats (the 1-based origin folded in) is wave-uniform
+// and stays in scalar registers, the row stride is nx, and a row of taps is ONE 32-bit lane offset on top of the base, as the B
+// stream's requests are (global_load ... v_off, s[base]).  Positions, fractions, the two fused lerps and their order are
+// bilinear_pad's: the samples are the same to the bit.  Global memory has no zero border: the host admits a ring only when no tap
+// of any sample, search offset and window state can leave the image (l1_tap_rings, ralign_plan.h).
+__device__ __forceinline__ float bilinear_l1(const float *base, int nx, float xold, float yold)
+{
+#pragma clang fp contract(off)
+    const int ix = (int)xold, iy = (int)yold;
+    const float ydif = __builtin_amdgcn_fractf(yold), xdif = __builtin_amdgcn_fractf(xold);
+    int idx;
+    asm("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(idx) : "v"(iy), "s"(nx), "v"(ix));
+    const char *b = reinterpret_cast<const char *>(base);
+    const unsigned o0 = 4u * (unsigned)idx, o1 = o0 + 4u * (unsigned)nx;      // the second row: one add on the offset
+    // the two taps (x, x + 1) of a row as ONE 8-byte request, 4-byte aligned.  Four 4-byte requests (what hipcc joins into this
+    // form anyway unless the second tap gets a base of its own) are slower by 2.3 ms per headline step: 31.45 against 29.14 ms
+    const v2f r0 = *reinterpret_cast<const v2f_a4 *>(b + o0), r1 = *reinterpret_cast<const v2f_a4 *>(b + o1);
+    const v2f g = __builtin_elementwise_fma((v2f){ydif, ydif}, r1 - r0, r0);
+    float d = g.y - g.x;
+    asm("" : "+v"(d));
+    return __builtin_fmaf(xdif, d, g.x);
+}
+
+#ifdef RALIGN_PROFILE_SWITCHES
+// profiling builds, RALIGN_DEBUG bit 16384 (the short-ring jobs): bilinear_pad's instructions with the four taps at ONE conflict-free
+// LDS address per lane, base[lane] -- wrong samples; the timing of a job whose taps cost the LDS array no more than their issue
+__device__ __forceinline__ float bilinear_probe(const float *base, int st, float xold, float yold, int lane)
+{
+#pragma clang fp contract(off)
+    const int ix = (int)xold, iy = (int)yold;
+    const float ydif = __builtin_amdgcn_fractf(yold), xdif = __builtin_amdgcn_fractf(xold);
+    int idx;
+    asm volatile("v_mad_i32_i24 %0, %1, %2, %3" : "=v"(idx) : "v"(iy), "s"(st), "v"(ix));      // issued, not used
+    const float *p = base + lane;
+    const v2f r0 = {p[0], p[1]}, r1 = {p[st], p[st + 1]};
+    const v2f g = __builtin_elementwise_fma((v2f){ydif, ydif}, r1 - r0, r0);
+    float d = g.y - g.x;
+    asm("" : "+v"(d));
+    return __builtin_fmaf(xdif, d, g.x);
+}
+#endif
+
+// the sample of a ring job at (x, y) from its tap source
+template <int TAP>
+__device__ __forceinline__ float ring_tap_sample(const DevGeom &g, const float *imgb, float x, float y, bool probe, int lane)
+{
+    if constexpr (TAP == TAP_L1) return bilinear_l1(imgb, g.nx, x, y);
+    else {
+#ifdef RALIGN_PROFILE_SWITCHES
+        if (probe) return bilinear_probe(imgb, g.pst, x, y, lane);
+#endif
+        return bilinear_pad(imgb, g.pst, x, y);
+    }
+}
+
 // search window of one particle: the reset/clamp rule and search_range
 // (test_mref_gpu_align.py:1030-1038; ali2d_single_iter for RA_MODE_REFFREE)
 struct Window { float sxi, syi; int lkx, rkx, lky, rky; };
@@ -449,7 +511,9 @@ struct NoSync { __device__ __forceinline__ void operator()() const {} };
 // is combined, so the job waits for them once.  That holds up to 3 LR / 2 more values in registers at that point: a gain in the
 // kernels that have the registers (fused, tiled), a loss in one that sits at the 128-register limit (pair), see
 // profiles/ring_fft_diet_ab.txt.
-template <int R1, int LR, bool NYQ1 = false, bool EARLY = false, class Sync = NoSync>
+// TAP: the source of the taps (TAP_LDS: `imgb` is the padded LDS image's base; TAP_L1: the particle's image in global memory, less
+// nx + 1 floats)
+template <int R1, int LR, bool NYQ1 = false, bool EARLY = false, int TAP = TAP_LDS, class Sync = NoSync>
 __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, float *bufs, const float2 *tw_s,
                                          const float2 *qt_s, const float *ctr, float *part, const int4 *inst_s,
                                          const float *instw_s, int inst0, int count, int zero, int sbuf, int nlive = 4,
@@ -470,6 +534,7 @@ __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, fl
     const float rad = (float)in.w, wt = instw_s[inst0 + subc];
     const float cx = ctr[2 * slot], cy = ctr[2 * slot + 1];
     const float2 *qt = qt_s + in.z;
+    const bool probe = NR <= 128 && RA_DBG(g, 16384);      // profiling builds: bilinear_probe
     // Normalize_ring partial sums: plain sums of the lane's samples and their squares, two at a time (packed f32),
     // weighted once per ring at the end
     v2f av2 = {0.f, 0.f}, sq2 = {0.f, 0.f};
@@ -523,13 +588,18 @@ __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, fl
                     m.y = ((qd + 1) & 2) ? -m.y : m.y;
                     o = m + ctr2;
                 }
-                const float s = bilinear_pad(imgb, g.pst, o.x, o.y);
+                const float s = ring_tap_sample<TAP>(g, imgb, o.x, o.y, probe, lane);
                 if (u == 0) val.x = s; else val.y = s;
             }
             av2 += val;
             sq2 += val * val;
             v[a] = make_float2(val.x, val.y);
-            if ((NYQ1 && (QCT ? 4 * b + q : b) >= R1 / 2) || ((QCT ? q : b) & 1)) __builtin_amdgcn_sched_barrier(0);   // at most 4 samples' taps in flight (fused kernel: 2 once half of the samples are held in registers)
+            if constexpr (TAP == TAP_L1) {
+                // taps through the L1 come back later than LDS ones: 8 samples' taps in flight (one position step).  Against 4 | 2
+                // as below the headline step differs by 0.1 ms, inside the run-to-run spread; all 16 in flight lose the whole gain
+                // (profiles/tap_source_ab.txt, section 4)
+                if (QCT ? q == 3 : (b & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+            } else if ((NYQ1 && (QCT ? 4 * b + q : b) >= R1 / 2) || ((QCT ? q : b) & 1)) __builtin_amdgcn_sched_barrier(0);   // at most 4 samples' taps in flight (fused kernel: 2 once half of the samples are held in registers)
         }
     }
     }
@@ -696,7 +766,7 @@ __device__ __forceinline__ void ring_job(const DevGeom &g, const float *imgb, fl
 // short rings of a pass fit the 64 lanes of one wave and every wave of the workgroup gets exactly one job -- as three jobs
 // (one per length) the two shortest cost a second round of ~3 k cycles each on the wave timeline.  The instance table holds
 // one entry per LANE: in.x = slot | ring << 8 | log2 n << 16 | lane-in-ring << 20.  Same arithmetic as ring_job<4, LR>.
-template <bool NYQ1, class Sync = NoSync>
+template <bool NYQ1, int TAP = TAP_LDS, class Sync = NoSync>
 __device__ __forceinline__ void ring_job_mix(const DevGeom &g, const float *imgb, float *bufs, const float2 *tw_s,
                                              const float2 *qt_s, const float *ctr, float *part, const int4 *inst_s,
                                              const float *instw_s, int inst0, int count, int zero, int sbuf, int nlive = 4,
@@ -712,6 +782,7 @@ __device__ __forceinline__ void ring_job_mix(const DevGeom &g, const float *imgb
     const float rad = (float)in.w, wt = instw_s[inst0 + lanec];
     const v2f ctr2 = {ctr[2 * slot], ctr[2 * slot + 1]};
     const float2 *qt = qt_s + in.z;
+    const bool probe = RA_DBG(g, 16384);                   // profiling builds: bilinear_probe
     v2f av2 = {0.f, 0.f}, sq2 = {0.f, 0.f};
     float2 v[4];
     if (active) {
@@ -731,7 +802,7 @@ __device__ __forceinline__ void ring_job_mix(const DevGeom &g, const float *imgb
                 m.y = ((qd + 1) & 2) ? -m.y : m.y;
                 o = m + ctr2;
             }
-            const float sv = bilinear_pad(imgb, g.pst, o.x, o.y);
+            const float sv = ring_tap_sample<TAP>(g, imgb, o.x, o.y, probe, lane);
             if (u == 0) val.x = sv; else val.y = sv;
         }
         av2 += val;

@@ -4,7 +4,10 @@
 // (resident_expected) alike.  Whether a family's LDS plan then fits is decided where its tables are (ralign_engine.hip).
 #pragma once
 
+#include <algorithm>
+#include <cmath>
 #include <cstdlib>
+#include <vector>
 
 #include "../../include/ralign.h"
 #include "ralign_geom.h"
@@ -107,6 +110,41 @@ inline bool tcrop_class(const Geometry &g, const ra_config &cfg, const PlanReque
 {
     return generic && g.maxrin == 256 && g.nring <= 64 && g.numr[2] >= 8 && cfg.nref <= 127 && !rq.generic_forced() &&
            rq.allow_tcrop && rq.sw.tcrop && rq.sw.fused;
+}
+
+// Tap source of search_fused_kernel's short rings (its TAPL1): rings of at most 64 or 128 samples may read their taps from the
+// particle's image in global memory, which has no zero border -- a tap outside the image would read the neighbouring particle, or
+// past the allocation behind the last one.  A ring of radius r qualifies when no tap of any sample can leave the image for any
+// search offset and any state the window rule admits: particle_window resets (RA_MODE_MREF) or clamps (RA_MODE_REFFREE) the state to
+// |d| <= mashi = cn - win_ring - 2, an offset adds at most ceil(range), a sample at most r, and the right / lower taps of the
+// interpolation are x + 1 / y + 1 (the zero-weight tap one past a sample that lands on a pixel counts).  One-based, as integers:
+//   cn - mashi - ceil(xr) - r >= 1   and   cn + mashi + ceil(xr) + r + 1 <= nx,   and the same in y with yr.
+// mashi: l1_tap_mashi -- the wider of the two modes' windows, since ra_engine_switch_mode changes the mode of a standing plan (at
+// ring step 1 both are cn - last_ring - 2).
+// The rule is all or nothing per engine: the largest setting T of {128, 64} up to `cap` whose rings of at most T samples ALL
+// qualify, else 0.  numr: (radius, offset, length) per ring.
+constexpr int kTapL1Cap = 128;      // the largest setting the dispatch instantiates (select_fused)
+inline int l1_tap_mashi(const std::vector<int> &numr, int nring, int nx, int last_ring)
+{
+    const int cn = nx / 2 + 1;
+    return std::max(std::abs(cn - last_ring - 2), std::abs(cn - numr[3 * (nring - 1)] - 2));
+}
+inline bool l1_tap_ring_ok(int nx, int mashi, float xrng, float yrng, int r)
+{
+    const int cn = nx / 2 + 1, ax = mashi + (int)std::ceil(xrng), ay = mashi + (int)std::ceil(yrng);
+    return cn - ax - r >= 1 && cn + ax + r + 1 <= nx && cn - ay - r >= 1 && cn + ay + r + 1 <= nx;
+}
+inline int l1_tap_rings(const std::vector<int> &numr, int nring, int nx, int last_ring, float xrng, float yrng, int cap = kTapL1Cap)
+{
+    const int mashi = l1_tap_mashi(numr, nring, nx, last_ring);
+    for (int T : {128, 64}) {
+        if (T > cap) continue;
+        bool ok = true;
+        for (int i = 0; i < nring && ok; i++)
+            if (numr[3 * i + 2] <= T && !l1_tap_ring_ok(nx, mashi, xrng, yrng, numr[3 * i])) ok = false;
+        if (ok) return T;
+    }
+    return 0;
 }
 
 // ring quads of the B stream of the particle-resident kernels, summed over the groups of 16 bins (rf_layout_b lays them out so):

@@ -180,6 +180,14 @@ int  ra_search_offsets_per_pass(const ra_engine *e);
 int  ra_search_skips_offsets(const ra_engine *e);
 /* 1 when the particle-resident path is search_tiled_kernel (reference tiles: 15 and more references), 0 otherwise */
 int  ra_search_tiled(const ra_engine *e);
+/* search_fused_kernel: rings of at most this many samples (64 | 128) read their bilinear taps from the particle's image in global
+ * memory, through the vector L1, instead of the LDS image; 0: every tap from LDS (a geometry or window in which a tap of such a
+ * ring could leave the image, and every other kernel).  Follows ra_reset_shifts */
+int  ra_search_l1_tap_rings(const ra_engine *e);
+/* the rule behind it, without an engine or a device: 128 | 64 when no tap of any sample of the rings of at most that many samples
+ * can leave an nx x nx image for any search offset of the window and any shift state the window rule admits, else 0 -- whatever
+ * kernel an engine would run and however many references it has (an engine also asks for 3 to 10 references) */
+int  ra_l1_tap_rule(int nx, int first_ring, int last_ring, int ring_skip, float xrng, float yrng);
 /* change the search window without re-allocating (reset_shifts analogue); the number of
  * offsets may not grow beyond what ra_create sized */
 int  ra_reset_shifts(ra_engine *e, float xrng, float yrng, float step);
