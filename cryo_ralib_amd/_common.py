@@ -59,6 +59,11 @@ def as_input(X, backend, error, numpy_on_device=True, numpy_dtype=None):
     return X if numpy_dtype is None else np.asarray(X, numpy_dtype)
 
 
+def host_finite(A, step=1 << 16):
+    """whether the numpy array A [n][...] holds finite values only, read a block of rows at a time"""
+    return all(bool(np.all(np.isfinite(A[s:s + step]))) for s in range(0, A.shape[0], step))
+
+
 def check_finite(X, backend, error):
     ok = bool(X.isfinite().all().item()) if backend == "device" else bool(np.all(np.isfinite(X)))
     if not ok:

@@ -1,5 +1,5 @@
 // DBSCAN of X [n][d] (scikit-learn 1.7 DBSCAN(eps, min_samples, metric="euclidean")).  The column lists are
-// ralign_kmeans.h's member lists padded by ralign_validity.h's kernels; the pair tiling is val_silhouette_kernel's, in double.
+// km_column_lists' (ralign_embed.hip: ralign_kmeans.h's member lists padded by ralign_validity.h's kernels); the pair tiling is val_silhouette_kernel's, in double.
 //
 //   D2(i, j) = sum_t (x_it - x_jt)^2 in double from differences, the features in order, one fma per feature.  x_i - x_j and
 //   x_j - x_i differ in sign alone and the chain's order is the same, so D2(i, j) == D2(j, i) bit for bit and D2(i, i) == 0.

@@ -15,29 +15,42 @@
 
 using namespace ralign;
 
-// ---- t-SNE (ralign_tsne.h)
+// ---- t-SNE (ralign_tsne.h; the neighbour lists: ralign_knn.h)
 
-extern "C" int ra_tsne_knn(const float *d_x, int n, int d, int k, int *d_idx, double *d_dist2, void *hip_stream)
+// the neighbour lists of q [nq][d] among x [m][d] (ralign_knn.h): the plan (C survivors, list capacity, dynamic LDS), the norms
+// and the kernel.  self: q == x and nq == m, row i leaves itself out, and the norms are computed once
+static int tsne_knn_run(const char *what, bool self, const float *d_q, int nq, const float *d_x, int m, int d, int k, int *d_idx,
+                        double *d_dist2, hipStream_t stream)
 {
-    hipStream_t stream = (hipStream_t)hip_stream;
-    if (n < 2 || n > TSNE_MAX_N || d < 1 || d > TSNE_MAX_D || k < 1 || k > std::min(n - 1, TSNE_MAX_K))
-        return arg_error("ra_tsne_knn: need 2 <= n <= 262144, 1 <= d <= 2048 and 1 <= k <= min(n - 1, 301)");
-    if (!d_x || !d_idx || !d_dist2) return arg_error("ra_tsne_knn: null argument");
     TsneKnnArgs a;
-    a.x = d_x; a.n = n; a.d = d; a.k = k;
-    a.C = std::min(n - 1, k + TSNE_KNN_MARGIN);
+    a.q = d_q; a.x = d_x; a.nq = nq; a.m = m; a.d = d; a.k = k;
+    a.C = std::min(self ? m - 1 : m, k + TSNE_KNN_MARGIN);
     a.cap = a.C + TSNE_KNN_SLACK;
     a.idx = d_idx; a.dist2 = d_dist2;
     const size_t lds = (size_t)16 * a.C * sizeof(double) + (size_t)16 * TSNE_KNN_TILE * sizeof(float) + (size_t)16 * a.cap * 8;
-    if (const int rc = RA_LDS(nullptr, tsne_knn_kernel, lds)) return rc;
+    if (const int rc = self ? RA_LDS(nullptr, tsne_knn_kernel, lds) : RA_LDS(nullptr, tsne_knn_query_kernel, lds)) return rc;
     StreamScratch scratch(stream);
-    float *d_nrm = scratch.get<float>(n);
-    if (!d_nrm) return hip_error("ra_tsne_knn", scratch.status());
-    a.nrm = d_nrm;
-    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_x, n, d, d_nrm);
+    float *d_nrm = scratch.get<float>(self ? (size_t)m : (size_t)nq + m);
+    if (!d_nrm) return hip_error(what, scratch.status());
+    a.qnrm = d_nrm; a.xnrm = self ? d_nrm : d_nrm + nq;
+    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, d_q, nq, d, d_nrm);
     hipError_t he = hipGetLastError();
-    RA_LAUNCH(he, tsne_knn_kernel, dim3((n + 15) / 16), dim3(TSNE_KNN_THREADS), lds, stream, a);
-    return he == hipSuccess ? RA_OK : hip_error("ra_tsne_knn", he);
+    const dim3 grid((nq + 15) / 16), block(TSNE_KNN_THREADS);
+    if (self) {
+        RA_LAUNCH(he, tsne_knn_kernel, grid, block, lds, stream, a);
+    } else {
+        RA_LAUNCH(he, tsne_sqnorm_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, d_x, m, d, d_nrm + nq);
+        RA_LAUNCH(he, tsne_knn_query_kernel, grid, block, lds, stream, a);
+    }
+    return he == hipSuccess ? RA_OK : hip_error(what, he);
+}
+
+extern "C" int ra_tsne_knn(const float *d_x, int n, int d, int k, int *d_idx, double *d_dist2, void *hip_stream)
+{
+    if (n < 2 || n > TSNE_MAX_N || d < 1 || d > TSNE_MAX_D || k < 1 || k > std::min(n - 1, TSNE_MAX_K))
+        return arg_error("ra_tsne_knn: need 2 <= n <= 262144, 1 <= d <= 2048 and 1 <= k <= min(n - 1, 301)");
+    if (!d_x || !d_idx || !d_dist2) return arg_error("ra_tsne_knn: null argument");
+    return tsne_knn_run("ra_tsne_knn", true, d_x, n, d_x, n, d, k, d_idx, d_dist2, (hipStream_t)hip_stream);
 }
 
 extern "C" int ra_tsne_affinity(const double *d_dist2, int n, int k, float perplexity, double *d_pcond, void *hip_stream)
@@ -118,26 +131,10 @@ extern "C" int ra_tsne_error(const float *d_y, int n, const int *d_indptr, const
 extern "C" int ra_tsne_knn_query(const float *d_q, int nq, const float *d_x, int m, int d, int k, int *d_idx, double *d_dist2,
                                  void *hip_stream)
 {
-    hipStream_t stream = (hipStream_t)hip_stream;
     if (nq < 1 || nq > TSNE_MAX_NQ || m < 1 || m > TSNE_MAX_N || d < 1 || d > TSNE_MAX_D || k < 1 || k > std::min(m, TSNE_MAX_K))
         return arg_error("ra_tsne_knn_query: need 1 <= nq <= 4194304, 1 <= m <= 262144, 1 <= d <= 2048 and 1 <= k <= min(m, 301)");
     if (!d_q || !d_x || !d_idx || !d_dist2) return arg_error("ra_tsne_knn_query: null argument");
-    TsneKnnQueryArgs a;
-    a.q = d_q; a.x = d_x; a.nq = nq; a.m = m; a.d = d; a.k = k;
-    a.C = std::min(m, k + TSNE_KNN_MARGIN);
-    a.cap = a.C + TSNE_KNN_SLACK;
-    a.idx = d_idx; a.dist2 = d_dist2;
-    const size_t lds = (size_t)16 * a.C * sizeof(double) + (size_t)16 * TSNE_KNN_TILE * sizeof(float) + (size_t)16 * a.cap * 8;
-    if (const int rc = RA_LDS(nullptr, tsne_knn_query_kernel, lds)) return rc;
-    StreamScratch scratch(stream);
-    float *d_nrm = scratch.get<float>((size_t)nq + m);
-    if (!d_nrm) return hip_error("ra_tsne_knn_query", scratch.status());
-    a.qnrm = d_nrm; a.xnrm = d_nrm + nq;
-    hipLaunchKernelGGL(tsne_sqnorm_kernel, dim3((nq + 255) / 256), dim3(256), 0, stream, d_q, nq, d, d_nrm);
-    hipError_t he = hipGetLastError();
-    RA_LAUNCH(he, tsne_sqnorm_kernel, dim3((m + 255) / 256), dim3(256), 0, stream, d_x, m, d, d_nrm + nq);
-    RA_LAUNCH(he, tsne_knn_query_kernel, dim3((nq + 15) / 16), dim3(TSNE_KNN_THREADS), lds, stream, a);
-    return he == hipSuccess ? RA_OK : hip_error("ra_tsne_knn_query", he);
+    return tsne_knn_run("ra_tsne_knn_query", false, d_q, nq, d_x, m, d, k, d_idx, d_dist2, (hipStream_t)hip_stream);
 }
 
 extern "C" int ra_tsne_affinity_rows(const double *d_dist2, int rows, int k, float perplexity, double *d_pcond, void *hip_stream)
@@ -218,6 +215,18 @@ static hipError_t km_member_lists(const int *labels, int n, int k, int L, const 
     RA_LAUNCH(he, km_offsets_kernel, dim3(k), dim3(256), 0, stream, bcnt, nb, k, cnt);
     RA_LAUNCH(he, km_starts_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, L, start, M.run0());
     RA_LAUNCH(he, km_scatter_kernel, dim3(nb), dim3(KM_BLOCK), 0, stream, labels, n, k, (const int *)bcnt, (const int *)start, M.mem());
+    return he;
+}
+
+// the padded column lists of the labels (val_pstart_kernel pads to VAL_TC = DBS_TC): cols is -1 wherever no member lands
+static hipError_t km_column_lists(const int *labels, int n, int k, const KmColumns &Cl, hipStream_t stream)
+{
+    const KmLists &M = Cl.M;
+    hipError_t he = hipMemsetAsync(Cl.cols(), 0xff, (size_t)Cl.cap * 4, stream);
+    if (he == hipSuccess) he = km_member_lists(labels, n, k, km_run_len(n), M, stream);
+    RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)M.cnt(), k, Cl.pstart());
+    RA_LAUNCH(he, val_cols_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const int *)M.mem(), (const int *)M.start(),
+              (const int *)M.cnt(), (const int *)Cl.pstart(), n, k, Cl.cap, Cl.cols());
     return he;
 }
 
@@ -376,20 +385,13 @@ extern "C" int ra_kmeans_silhouette(const float *d_x, int n, int d, const int *d
         return arg_error("ra_kmeans_silhouette: need 3 <= n <= 262144, 1 <= d <= 2048 and 2 <= k <= 256");
     if (!d_x || !d_labels || !d_out || !d_nearest) return arg_error("ra_kmeans_silhouette: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int cap = n + k * VAL_TC;
     KmScratch S;
-    const KmLists M(S, n, k, KM_BLOCK);
-    const size_t o_pstart = S.take((size_t)(k + 1) * 4), o_cols = S.take((size_t)cap * 4);
+    const KmColumns Cl(S, n, k, KM_BLOCK, VAL_TC);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_kmeans_silhouette", scratch.status());
-    int *cnt = M.cnt(), *start = M.start(), *mem = M.mem(), *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols);
-    hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);          // every column invalid (-1) until a member lands on it
-    if (he == hipSuccess) he = km_member_lists(d_labels, n, k, km_run_len(n), M, stream);
-    RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, k, pstart);
-    RA_LAUNCH(he, val_cols_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt,
-              (const int *)pstart, n, k, cap, cols);
+    hipError_t he = km_column_lists(d_labels, n, k, Cl, stream);
     ValSilArgs a;
-    a.x = d_x; a.labels = d_labels; a.cols = cols; a.count = cnt; a.pstart = pstart; a.n = n; a.d = d; a.k = k;
+    a.x = d_x; a.labels = d_labels; a.cols = Cl.cols(); a.count = Cl.M.cnt(); a.pstart = Cl.pstart(); a.n = n; a.d = d; a.k = k;
     a.out = d_out; a.nearest = d_nearest;
     RA_LAUNCH(he, val_silhouette_kernel, dim3((n + VAL_TR - 1) / VAL_TR), dim3(256), 0, stream, a);
     return he == hipSuccess ? RA_OK : hip_error("ra_kmeans_silhouette", he);
@@ -452,25 +454,19 @@ extern "C" int ra_dbscan_step(const float *d_x, int n, int d, double eps, const 
     if (!d_x || !d_count || !d_label || !d_label_out || !d_changed || d_label_out == d_label)
         return arg_error("ra_dbscan_step: null argument, or d_label_out == d_label");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int nt = (n + 255) / 256, cap = n + 2 * DBS_TC;
+    const int nt = (n + 255) / 256;
     KmScratch S;
-    const KmLists M(S, n, 2, KM_BLOCK);
-    const size_t o_flag = S.take((size_t)n * 4), o_pstart = S.take(3 * 4), o_cols = S.take((size_t)cap * 4);
-    const size_t o_m = S.take((size_t)n * 4), o_p = S.take((size_t)n * 4);
+    const KmColumns Cl(S, n, 2, KM_BLOCK, DBS_TC);
+    const size_t o_flag = S.take((size_t)n * 4), o_m = S.take((size_t)n * 4), o_p = S.take((size_t)n * 4);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_dbscan_step", scratch.status());
-    int *flag = S.at<int>(o_flag), *cnt = M.cnt(), *start = M.start(), *mem = M.mem();
-    int *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols), *m = S.at<int>(o_m), *P = S.at<int>(o_p);
-    // the core points in index order: the member list of "cluster" 0 of the flags, padded to the column tile with -1
-    hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);
-    if (he == hipSuccess) he = hipMemsetAsync(d_changed, 0, sizeof(int), stream);
+    int *flag = S.at<int>(o_flag), *m = S.at<int>(o_m), *P = S.at<int>(o_p);
+    // the core points in index order: the column list of "cluster" 0 of the flags
+    hipError_t he = hipMemsetAsync(d_changed, 0, sizeof(int), stream);
     RA_LAUNCH(he, dbs_flag_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, flag);
-    if (he == hipSuccess) he = km_member_lists(flag, n, 2, km_run_len(n), M, stream);
-    RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, 2, pstart);
-    RA_LAUNCH(he, val_cols_kernel, dim3(nt), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt, (const int *)pstart,
-              n, 2, cap, cols);
-    RA_LAUNCH(he, dbs_min_kernel, dim3((n + DBS_TR - 1) / DBS_TR), dim3(256), 0, stream, d_x, n, d, eps * eps, (const int *)cols,
-              (const int *)pstart, d_label, m);
+    if (he == hipSuccess) he = km_column_lists(flag, n, 2, Cl, stream);
+    RA_LAUNCH(he, dbs_min_kernel, dim3((n + DBS_TR - 1) / DBS_TR), dim3(256), 0, stream, d_x, n, d, eps * eps, (const int *)Cl.cols(),
+              (const int *)Cl.pstart(), d_label, m);
     if (he == hipSuccess) he = hipMemcpyAsync(P, d_label, (size_t)n * 4, hipMemcpyDeviceToDevice, stream);
     RA_LAUNCH(he, dbs_hook_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, d_label, (const int *)m, P);
     RA_LAUNCH(he, dbs_compress_kernel, dim3(nt), dim3(256), 0, stream, d_count, n, min_samples, d_label, (const int *)m, (const int *)P,
@@ -551,23 +547,18 @@ extern "C" int ra_ward_nearest(const double *d_c, const int *d_size, int n, int 
     if (n_rows < 1 || n_rows > WARD_MAX_N) return arg_error("ra_ward_nearest: need 1 <= n_rows <= 262144");
     if (!d_c || !d_size || !d_rows || !d_nn || !d_w2) return arg_error("ra_ward_nearest: null argument");
     hipStream_t stream = (hipStream_t)hip_stream;
-    const int nt = (n + 255) / 256, cap = n + 2 * DBS_TC;
     KmScratch S;
-    const KmLists M(S, n, 2, KM_BLOCK);
-    const size_t o_flag = S.take((size_t)n * 4), o_pstart = S.take(3 * 4), o_cols = S.take((size_t)cap * 4);
+    const KmColumns Cl(S, n, 2, KM_BLOCK, DBS_TC);
+    const size_t o_flag = S.take((size_t)n * 4);
     StreamScratch scratch(stream);
     if (!(S.base = scratch.get<unsigned char>(S.off))) return hip_error("ra_ward_nearest", scratch.status());
-    int *flag = S.at<int>(o_flag), *cnt = M.cnt(), *start = M.start(), *mem = M.mem();
-    int *pstart = S.at<int>(o_pstart), *cols = S.at<int>(o_cols);
-    // the live slots in slot order: the member list of "cluster" 0 of the flags (size >= 1), padded to the column tile with -1
-    hipError_t he = hipMemsetAsync(cols, 0xff, (size_t)cap * 4, stream);
-    RA_LAUNCH(he, dbs_flag_kernel, dim3(nt), dim3(256), 0, stream, d_size, n, 1, flag);
-    if (he == hipSuccess) he = km_member_lists(flag, n, 2, km_run_len(n), M, stream);
-    RA_LAUNCH(he, val_pstart_kernel, dim3(1), dim3(64), 0, stream, (const int *)cnt, 2, pstart);
-    RA_LAUNCH(he, val_cols_kernel, dim3(nt), dim3(256), 0, stream, (const int *)mem, (const int *)start, (const int *)cnt, (const int *)pstart,
-              n, 2, cap, cols);
+    int *flag = S.at<int>(o_flag);
+    // the live slots in slot order: the column list of "cluster" 0 of the flags (size >= 1)
+    hipLaunchKernelGGL(dbs_flag_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, d_size, n, 1, flag);
+    hipError_t he = hipGetLastError();
+    if (he == hipSuccess) he = km_column_lists(flag, n, 2, Cl, stream);
     RA_LAUNCH(he, ward_row_kernel, dim3((n_rows + WARD_TR - 1) / WARD_TR), dim3(256), 0, stream, d_c, d_size, n, d, d_rows, n_rows,
-              (const int *)cols, (const int *)pstart, d_nn, d_w2);
+              (const int *)Cl.cols(), (const int *)Cl.pstart(), d_nn, d_w2);
     return he == hipSuccess ? RA_OK : hip_error("ra_ward_nearest", he);
 }
 

@@ -28,4 +28,16 @@ struct KmLists {
     int *mem() const { return S.at<int>(o_mem); }
 };
 
+// the member lists and, on top of them, the padded column lists (km_column_lists): pstart [k + 1] and cols [cap], every label's
+// members in index order in a range padded to a multiple of the column tile tc with -1; cap = n + k tc bounds any padding
+struct KmColumns {
+    KmLists M;
+    int cap;
+    size_t o_pstart, o_cols;
+    KmColumns(KmScratch &s, int n, int k, int block, int tc)
+        : M(s, n, k, block), cap(n + k * tc), o_pstart(s.take((size_t)(k + 1) * 4)), o_cols(s.take((size_t)cap * 4)) {}
+    int *pstart() const { return M.S.at<int>(o_pstart); }
+    int *cols() const { return M.S.at<int>(o_cols); }
+};
+
 } // namespace ralign

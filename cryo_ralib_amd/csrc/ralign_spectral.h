@@ -97,6 +97,7 @@ __global__ __launch_bounds__(256) void spec_spmv_kernel(const int *__restrict__ 
 }
 
 // bad[0] = 1 unless indptr[0] == 0, every row has 0 <= p0 <= p1 with at most n entries and every column is in 0 .. n - 1
+// (umap_check_kernel asks for another condition, an indptr that ascends to nnz: the two stay apart)
 __global__ __launch_bounds__(256) void spec_check_kernel(const int *__restrict__ indptr, const int *__restrict__ indices, int n,
                                                          int *__restrict__ bad)
 {

@@ -1,9 +1,6 @@
 // t-SNE of factors X [n][d] (scikit-learn 1.7 TSNE, method="barnes_hut", angle=0: sparse kNN affinities, exact repulsion).
 //
-//   tsne_sqnorm_kernel      |x_i|^2 per row (double sum, rounded once), for the Gram distances of the kNN.
-//   tsne_knn_kernel         exact kNN: Gram distance tiles |x_i|^2 + |x_j|^2 - 2 x_i.x_j on v_mfma_f32_16x16x4_f32, a streaming
-//                           per-row top-C selection in LDS (C = min(n - 1, k + TSNE_KNN_MARGIN)), then the C survivors re-ranked
-//                           by squared distances computed in double from x_i - x_j; writes the k best by (distance, index).
+//   tsne_sqnorm_kernel, tsne_knn_kernel, tsne_knn_query_kernel   the exact neighbour lists: ralign_knn.h.
 //   tsne_affinity_kernel    sklearn's _binary_search_perplexity on the k neighbours of a row (one wave per row, double).
 //   tsne_repulsion_kernel   all-pairs partials over one block of rows x one segment of columns: sum_j w_ij^2 (y_i - y_j) per row
 //                           and sum_{j != i} w_ij over the block, w = 1 / (1 + d^2).  The self pair (w = 1) is left out of the
@@ -11,11 +8,10 @@
 //   tsne_update_kernel      Z from the block partials, the row's repulsion from its segment partials, the sparse attraction over
 //                           its CSR row, the gradient, then sklearn's gains / momentum update (or the gradient alone).
 //   tsne_stats_kernel       KL error and squared gradient norm from the update's per-workgroup partials.
-//   tsne_knn_query_kernel, tsne_place_kernel   out-of-sample placement of new points into a fixed embedding (at the end).
+//   tsne_place_kernel       out-of-sample placement of new points into a fixed embedding (at the end).
 //
 // Determinism: no atomics on floating-point data. Every sum has an order fixed by n alone: the segment length, the row blocks
-// and the reduction trees depend on n only, never on the device or on how the grid is scheduled. The kNN list's append order
-// varies (an LDS integer counter), but only its set is used: every cut is by the total order (distance, index).
+// and the reduction trees depend on n only, never on the device or on how the grid is scheduled.
 // Indices read from data (CSR columns, row pointers) are clamped before they address anything.
 #pragma once
 
@@ -23,15 +19,9 @@
 
 #include <type_traits>
 
-namespace ralign {
+#include "ralign_knn.h"
 
-#define TSNE_KNN_THREADS 256        // 4 waves; the workgroup owns 16 query rows, a wave 16 candidate columns of each tile
-#define TSNE_KNN_TILE 64            // candidate columns per tile
-#define TSNE_KNN_MARGIN 32          // survivors kept beyond k for the double re-rank
-#define TSNE_KNN_SLACK 256          // list capacity beyond C: a compaction every >= 192 accepted candidates
-#define TSNE_MAX_K 301              // k = int(3 perplexity + 1) at perplexity 100
-#define TSNE_MAX_N 262144
-#define TSNE_MAX_D 2048
+namespace ralign {
 
 #define TSNE_REP_THREADS 256
 #define TSNE_REP_R 4                                   // rows per lane
@@ -47,17 +37,6 @@ __host__ __device__ inline int tsne_segment(int n)
     return TSNE_REP_ROWS * (per > 0 ? per : 1);
 }
 
-__device__ __forceinline__ const float *x_row_or_null(const float *x, int i, int n, int d)
-{
-    return i < n ? x + (size_t)i * d : nullptr;
-}
-
-__device__ __forceinline__ float tsne_not_nan(float v) { return v != v ? __builtin_inff() : v; }
-
-__device__ __forceinline__ bool tsne_key_less(float da, int ia, float db, int ib) { return da < db || (da == db && ia < ib); }
-
-__device__ __forceinline__ bool tsne_key_less(double da, int ia, double db, int ib) { return da < db || (da == db && ia < ib); }
-
 // fixed-order sum of v over the workgroup (blockDim.x = NT, a power of two); every thread gets the result
 template <int NT>
 __device__ __forceinline__ double tsne_block_sum(double v, double *red)
@@ -72,152 +51,6 @@ __device__ __forceinline__ double tsne_block_sum(double v, double *red)
     const double r = red[0];
     __syncthreads();
     return r;
-}
-
-__global__ __launch_bounds__(256) void tsne_sqnorm_kernel(const float *__restrict__ x, int n, int d, float *__restrict__ nrm)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float *xi = x + (size_t)i * d;
-    double s = 0.0;
-    for (int t = 0; t < d; t++) s += (double)xi[t] * (double)xi[t];
-    nrm[i] = (float)s;
-}
-
-struct TsneKnnArgs {
-    const float *x, *nrm;
-    int n, d, k, C, cap;            // C survivors per row, cap list capacity (C + TSNE_KNN_SLACK)
-    int *idx;                       // [n][k]
-    double *dist2;                  // [n][k]
-};
-
-// LDS: tile [16][64] float, list distances [16][cap] float, list indices [16][cap] int, exact distances [16][C] double
-__global__ __launch_bounds__(TSNE_KNN_THREADS) void tsne_knn_kernel(TsneKnnArgs a)
-{
-    extern __shared__ __align__(16) unsigned char tsne_smem[];
-    double *ex = (double *)tsne_smem;
-    float *tile = (float *)(ex + 16 * a.C);
-    float *ld = tile + 16 * TSNE_KNN_TILE;
-    int *li = (int *)(ld + 16 * a.cap);
-    __shared__ int cnt[16], full[16], thr_i[16];
-    __shared__ float thr_d[16];
-
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
-    const int i0 = blockIdx.x * 16;
-    const int row = tid >> 4, sub = tid & 15, gi = i0 + row;   // selection: 16 lanes per query row
-    if (tid < 16) { cnt[tid] = 0; full[tid] = 0; thr_d[tid] = __builtin_inff(); thr_i[tid] = 0; }
-    __syncthreads();
-
-    // keep the C smallest (distance, index) of the rows whose list holds more than `limit`; workgroup-uniform
-    auto compact = [&](int limit) {
-        const int c = cnt[row];
-        const bool act = gi < a.n && c > limit;
-        float *rd = ld + row * a.cap;
-        int *ri = li + row * a.cap;
-        if (act) {
-            for (int e = sub; e < c; e += 16) {
-                const float de = rd[e];
-                const int ie = ri[e];
-                int rank = 0;
-                for (int f = 0; f < c; f++) rank += tsne_key_less(rd[f], ri[f], de, ie) ? 1 : 0;
-                if (rank == a.C - 1) { thr_d[row] = de; thr_i[row] = ie; }
-            }
-        }
-        __syncthreads();
-        if (act) {
-            const float td = thr_d[row];
-            const int ti = thr_i[row];
-            int base = 0;
-            // in-place stream compaction, 16 entries at a time: all lanes of the row read their entry before any write, and
-            // every write lands below the next chunk
-            for (int c0 = 0; c0 < c; c0 += 16) {
-                const int e = c0 + sub;
-                float dv = 0.f;
-                int iv = 0;
-                bool keep = false;
-                if (e < c) { dv = rd[e]; iv = ri[e]; keep = !tsne_key_less(td, ti, dv, iv); }
-                const unsigned long long b = __ballot(keep);
-                const unsigned grp = (unsigned)(b >> (lane & 48)) & 0xffffu;
-                const int pre = __popc(grp & ((1u << sub) - 1u));
-                if (keep) { rd[base + pre] = dv; ri[base + pre] = iv; }
-                base += __popc(grp);
-            }
-            if (sub == 0) { cnt[row] = base; full[row] = 1; }
-        }
-        __syncthreads();
-    };
-
-    const int qi = i0 + lr;
-    const float *xq = x_row_or_null(a.x, qi, a.n, a.d);
-    for (int j0 = 0; j0 < a.n; j0 += TSNE_KNN_TILE) {
-        // Gram tile: rows i0 .. i0 + 15 x columns j0 + 16 wave .. + 15
-        const int cj = j0 + wave * 16 + lr;
-        const float *xc = x_row_or_null(a.x, cj, a.n, a.d);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int k0 = 0; k0 < a.d; k0 += 4) {
-            const int kk = k0 + lk;
-            const float av = (xq && kk < a.d) ? xq[kk] : 0.f;
-            const float bv = (xc && kk < a.d) ? xc[kk] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-        }
-        const float nc = cj < a.n ? a.nrm[cj] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int orow = lk * 4 + r;
-            const float nq = i0 + orow < a.n ? a.nrm[i0 + orow] : 0.f;
-            tile[orow * TSNE_KNN_TILE + wave * 16 + lr] = tsne_not_nan(nq + nc - 2.f * acc[r]);
-        }
-        __syncthreads();
-        if (gi < a.n) {
-            const bool fl = full[row] != 0;
-            const float td = thr_d[row];
-#pragma unroll
-            for (int m = 0; m < TSNE_KNN_TILE / 16; m++) {
-                const int col = sub + 16 * m, j = j0 + col;
-                if (j >= a.n || j == gi) continue;
-                const float dv = tile[row * TSNE_KNN_TILE + col];
-                // columns arrive in increasing index order, so a distance equal to the cut loses to the kept entry
-                if (!fl || dv < td) {
-                    const int pos = atomicAdd(&cnt[row], 1);
-                    ld[row * a.cap + pos] = dv;
-                    li[row * a.cap + pos] = j;
-                }
-            }
-        }
-        __syncthreads();
-        bool over = false;
-#pragma unroll
-        for (int r = 0; r < 16; r++) over |= cnt[r] > a.cap - TSNE_KNN_TILE;
-        if (over) compact(a.cap - TSNE_KNN_TILE);
-    }
-    compact(a.C);
-
-    // re-rank the survivors by the exact squared distance (double, from x_i - x_j)
-    const int c = gi < a.n ? cnt[row] : 0;
-    const float *xi = a.x + (size_t)min(gi, a.n - 1) * a.d;
-    double *rx = ex + row * a.C;
-    const int *ri = li + row * a.cap;
-    for (int e = sub; e < c; e += 16) {
-        const float *xj = a.x + (size_t)ri[e] * a.d;
-        double s = 0.0;
-        for (int t = 0; t < a.d; t++) {
-            const double df = (double)xi[t] - (double)xj[t];
-            s += df * df;
-        }
-        rx[e] = s != s ? __builtin_inf() : s;
-    }
-    __syncthreads();
-    for (int e = sub; e < c; e += 16) {
-        const double de = rx[e];
-        const int ie = ri[e];
-        int rank = 0;
-        for (int f = 0; f < c; f++) rank += tsne_key_less(rx[f], ri[f], de, ie) ? 1 : 0;
-        if (rank < a.k) {
-            a.idx[(size_t)gi * a.k + rank] = ie;
-            a.dist2[(size_t)gi * a.k + rank] = de;
-        }
-    }
 }
 
 // one wave per row: sklearn _binary_search_perplexity (_utils.pyx) with the row's k squared distances rounded to float, as
@@ -418,8 +251,7 @@ __global__ __launch_bounds__(256) void tsne_stats_kernel(const double *__restric
 
 // ---- out-of-sample placement: new points against a fixed embedding
 //
-//   tsne_knn_query_kernel   tsne_knn_kernel with separate query rows q [nq][d] and base rows x [m][d] and no self exclusion:
-//                           C = min(m, k + TSNE_KNN_MARGIN) survivors of the float32 Gram screen, re-ranked in double.
+//   tsne_knn_query_kernel   the neighbour lists of the new rows among the fitted rows: ralign_knn.h.
 //   tsne_place_kernel       a wave owns TSNE_PLACE_R new points and keeps their y, update and gains in registers over all
 //                           iterations; its 64 lanes share the fitted points (lane l takes columns l, l + 64, ... of each staged
 //                           chunk) and the neighbour list (entries l, l + 64, ...).  Per chunk a lane sums at most
@@ -429,144 +261,10 @@ __global__ __launch_bounds__(256) void tsne_stats_kernel(const double *__restric
 // Order: a point's sums depend on m and k only (the chunk, the lane stride and the butterfly are constants); the four points of a
 // wave run the same instructions on separate registers, so neither n, the point's slot nor the grid enters any value.
 
-#define TSNE_MAX_NQ 4194304
 #define TSNE_PLACE_THREADS 256
 #define TSNE_PLACE_R 4                                                 // points per wave
 #define TSNE_PLACE_ROWS (TSNE_PLACE_R * TSNE_PLACE_THREADS / 64)       // points per workgroup
 #define TSNE_PLACE_CHUNK 2048                                          // fitted points staged in LDS at a time
-
-struct TsneKnnQueryArgs {
-    const float *q, *qnrm, *x, *xnrm;
-    int nq, m, d, k, C, cap;        // C survivors per row, cap list capacity (C + TSNE_KNN_SLACK)
-    int *idx;                       // [nq][k]
-    double *dist2;                  // [nq][k]
-};
-
-// LDS as tsne_knn_kernel: tile [16][64] float, list distances [16][cap] float, list indices [16][cap] int, exact [16][C] double
-__global__ __launch_bounds__(TSNE_KNN_THREADS) void tsne_knn_query_kernel(TsneKnnQueryArgs a)
-{
-    extern __shared__ __align__(16) unsigned char tsne_smem[];
-    double *ex = (double *)tsne_smem;
-    float *tile = (float *)(ex + 16 * a.C);
-    float *ld = tile + 16 * TSNE_KNN_TILE;
-    int *li = (int *)(ld + 16 * a.cap);
-    __shared__ int cnt[16], full[16], thr_i[16];
-    __shared__ float thr_d[16];
-
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, lr = lane & 15, lk = lane >> 4;
-    const int i0 = blockIdx.x * 16;
-    const int row = tid >> 4, sub = tid & 15, gi = i0 + row;   // selection: 16 lanes per query row
-    if (tid < 16) { cnt[tid] = 0; full[tid] = 0; thr_d[tid] = __builtin_inff(); thr_i[tid] = 0; }
-    __syncthreads();
-
-    // keep the C smallest (distance, index) of the rows whose list holds more than `limit`; workgroup-uniform
-    auto compact = [&](int limit) {
-        const int c = cnt[row];
-        const bool act = gi < a.nq && c > limit;
-        float *rd = ld + row * a.cap;
-        int *ri = li + row * a.cap;
-        if (act) {
-            for (int e = sub; e < c; e += 16) {
-                const float de = rd[e];
-                const int ie = ri[e];
-                int rank = 0;
-                for (int f = 0; f < c; f++) rank += tsne_key_less(rd[f], ri[f], de, ie) ? 1 : 0;
-                if (rank == a.C - 1) { thr_d[row] = de; thr_i[row] = ie; }
-            }
-        }
-        __syncthreads();
-        if (act) {
-            const float td = thr_d[row];
-            const int ti = thr_i[row];
-            int base = 0;
-            for (int c0 = 0; c0 < c; c0 += 16) {
-                const int e = c0 + sub;
-                float dv = 0.f;
-                int iv = 0;
-                bool keep = false;
-                if (e < c) { dv = rd[e]; iv = ri[e]; keep = !tsne_key_less(td, ti, dv, iv); }
-                const unsigned long long b = __ballot(keep);
-                const unsigned grp = (unsigned)(b >> (lane & 48)) & 0xffffu;
-                const int pre = __popc(grp & ((1u << sub) - 1u));
-                if (keep) { rd[base + pre] = dv; ri[base + pre] = iv; }
-                base += __popc(grp);
-            }
-            if (sub == 0) { cnt[row] = base; full[row] = 1; }
-        }
-        __syncthreads();
-    };
-
-    const int qi = i0 + lr;
-    const float *xq = x_row_or_null(a.q, qi, a.nq, a.d);
-    for (int j0 = 0; j0 < a.m; j0 += TSNE_KNN_TILE) {
-        const int cj = j0 + wave * 16 + lr;
-        const float *xc = x_row_or_null(a.x, cj, a.m, a.d);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 4
-        for (int k0 = 0; k0 < a.d; k0 += 4) {
-            const int kk = k0 + lk;
-            const float av = (xq && kk < a.d) ? xq[kk] : 0.f;
-            const float bv = (xc && kk < a.d) ? xc[kk] : 0.f;
-            acc = __builtin_amdgcn_mfma_f32_16x16x4f32(av, bv, acc, 0, 0, 0);
-        }
-        const float nc = cj < a.m ? a.xnrm[cj] : 0.f;
-#pragma unroll
-        for (int r = 0; r < 4; r++) {
-            const int orow = lk * 4 + r;
-            const float nq = i0 + orow < a.nq ? a.qnrm[i0 + orow] : 0.f;
-            tile[orow * TSNE_KNN_TILE + wave * 16 + lr] = tsne_not_nan(nq + nc - 2.f * acc[r]);
-        }
-        __syncthreads();
-        if (gi < a.nq) {
-            const bool fl = full[row] != 0;
-            const float td = thr_d[row];
-#pragma unroll
-            for (int t = 0; t < TSNE_KNN_TILE / 16; t++) {
-                const int col = sub + 16 * t, j = j0 + col;
-                if (j >= a.m) continue;
-                const float dv = tile[row * TSNE_KNN_TILE + col];
-                // columns arrive in increasing index order, so a distance equal to the cut loses to the kept entry
-                if (!fl || dv < td) {
-                    const int pos = atomicAdd(&cnt[row], 1);
-                    ld[row * a.cap + pos] = dv;
-                    li[row * a.cap + pos] = j;
-                }
-            }
-        }
-        __syncthreads();
-        bool over = false;
-#pragma unroll
-        for (int r = 0; r < 16; r++) over |= cnt[r] > a.cap - TSNE_KNN_TILE;
-        if (over) compact(a.cap - TSNE_KNN_TILE);
-    }
-    compact(a.C);
-
-    // re-rank the survivors by the exact squared distance (double, from q_i - x_j, the features in order)
-    const int c = gi < a.nq ? cnt[row] : 0;
-    const float *xi = a.q + (size_t)min(gi, a.nq - 1) * a.d;
-    double *rx = ex + row * a.C;
-    const int *ri = li + row * a.cap;
-    for (int e = sub; e < c; e += 16) {
-        const float *xj = a.x + (size_t)ri[e] * a.d;
-        double s = 0.0;
-        for (int t = 0; t < a.d; t++) {
-            const double df = (double)xi[t] - (double)xj[t];
-            s += df * df;
-        }
-        rx[e] = s != s ? __builtin_inf() : s;
-    }
-    __syncthreads();
-    for (int e = sub; e < c; e += 16) {
-        const double de = rx[e];
-        const int ie = ri[e];
-        int rank = 0;
-        for (int f = 0; f < c; f++) rank += tsne_key_less(rx[f], ri[f], de, ie) ? 1 : 0;
-        if (rank < a.k) {
-            a.idx[(size_t)gi * a.k + rank] = ie;
-            a.dist2[(size_t)gi * a.k + rank] = de;
-        }
-    }
-}
 
 struct TsnePlaceArgs {
     float2 *y;                      // [n]: read; written after the iterations if n_iter > 0

@@ -106,7 +106,8 @@ __global__ __launch_bounds__(256) void umap_smooth_kernel(const double *__restri
     }
 }
 
-// bad[0] = 1 unless indptr ascends from 0 to nnz and every column is in 0 .. n - 1
+// bad[0] = 1 unless indptr ascends from 0 to nnz and every column is in 0 .. n - 1 (spec_check_kernel asks for another condition,
+// rows of at most n entries: the two stay apart)
 __global__ __launch_bounds__(256) void umap_check_kernel(const int *__restrict__ indptr, const int *__restrict__ indices, int n, int nnz,
                                                          int *__restrict__ bad)
 {

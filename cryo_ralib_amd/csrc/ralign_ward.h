@@ -18,8 +18,8 @@
 //   ward_size_kernel   (a launch of its own) one thread per pair: s_a <- s_a + s_b, s_b <- 0.
 //                      Both skip a pair outside 0 <= a < b < n or with a dead member; the pairs of one call are disjoint.
 //
-// The live column list is the member list of "cluster" 0 of dbs_flag_kernel(size, min_samples = 1), padded by val_pstart_kernel /
-// val_cols_kernel, as DBSCAN's core columns are.
+// The live column list is the member list of "cluster" 0 of dbs_flag_kernel(size, min_samples = 1), padded by km_column_lists
+// (ralign_embed.hip), as DBSCAN's core columns are.
 //
 // Determinism: no floating-point atomics and no floating-point sum across threads (a pair's chain lives in one thread); the
 // minimum is that of a set, so the order of the shuffles cannot change it.  No workgroup waits for another: ordering comes from

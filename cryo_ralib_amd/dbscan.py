@@ -48,7 +48,7 @@ import sys
 
 import numpy as np
 
-from . import _common
+from . import _common, _graph
 from ._common import Launcher, d2_rows, is_int, is_real, ptr, row_chunks
 
 MAX_N, MAX_D, MAX_KNN = 262144, 2048, 301
@@ -88,7 +88,8 @@ def check_domain(n, d, eps, min_samples):
 # ---- CPU checker (float64 numpy)
 
 def _components(n, ea, eb):
-    """label [n] = the lowest index of the connected component under the edges (ea, eb): minimum, hook, compress, as the device"""
+    """label [n] = the lowest index of the connected component under the edges (ea, eb): minimum, hook, compress, as the device.
+    Apart from spectral.components_numpy: this one takes an edge list, hooks every point as well as its label, and counts rounds."""
     lab = np.arange(n, dtype=np.int64)
     rounds = 0
     while True:
@@ -99,12 +100,7 @@ def _components(n, ea, eb):
         P = lab.copy()
         sel = m < lab
         np.minimum.at(P, lab[sel], m[sel])
-        P = np.minimum(P, m)
-        while True:
-            Q = P[P]
-            if np.array_equal(Q, P):
-                break
-            P = Q
+        P = _graph.jump(np.minimum(P, m))
         if np.array_equal(P, lab):
             return lab, rounds
         lab = P
@@ -213,10 +209,7 @@ def kdistances(X, min_samples, backend="device"):
     L = Launcher(X)
     torch = L.torch
     with torch.cuda.device(X.device):
-        idx = torch.empty((n, k), dtype=torch.int32, device=X.device)
-        d2 = torch.empty((n, k), dtype=torch.float64, device=X.device)
-        L.call("ra_tsne_knn", ptr(X), n, d, k, ptr(idx), ptr(d2))
-        return torch.sqrt(d2[:, k - 1]).cpu().numpy()
+        return torch.sqrt(_graph.knn(L, X, k)[1][:, k - 1]).cpu().numpy()
 
 
 # ---- command line

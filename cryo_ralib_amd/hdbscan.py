@@ -73,7 +73,7 @@ import time
 
 import numpy as np
 
-from . import _common
+from . import _common, _graph
 from ._common import Launcher, d2_rows, is_int, ptr, row_chunks
 
 MAX_N, MAX_D, MAX_MIN_SAMPLES = 262144, 2048, 302
@@ -243,15 +243,6 @@ def _mst_device(X, min_samples):
 
 # ---- rules 6 - 9, shared by both backends
 
-def _jump(up):
-    """the fixed point of x -> up[x] for every x, by pointer doubling"""
-    while True:
-        nxt = up[up]
-        if np.array_equal(nxt, up):
-            return up
-        up = nxt
-
-
 def _dendrogram(n, lo, hi):
     """the binary single-linkage dendrogram of the sorted tree edges: node n + e joins the two nodes that hold lo[e] and hi[e].
     Returns parent [2 n - 1] (the root its own parent) and size [2 n - 1].  The one pass that is a Python loop: a union-find
@@ -291,7 +282,7 @@ def tree_from_mst(n, lo, hi, w2, min_cluster_size, method="eom"):
     # rule 6: a node whose parent has the same height is part of its parent's level node; rep = the top of that chain
     ident = np.arange(N, dtype=np.int64)
     same = (ident >= n) & (parent != ident) & (height[parent] == height) & (parent >= n)
-    rep = _jump(np.where(same, parent, ident))
+    rep = _graph.jump(np.where(same, parent, ident))
     is_level = rep == ident                                         # points, and the top binary node of every level node
     lp = rep[parent]                                                # level parent of a level node (the root: itself)
     big = is_level & (size >= mcs)
@@ -300,7 +291,7 @@ def tree_from_mst(n, lo, hi, w2, min_cluster_size, method="eom"):
     nbig = np.bincount(lp[kids], weights=big[kids].astype(np.float64), minlength=N).astype(np.int64)
     # a big level node heads a cluster if it is the root or one of two or more big children; otherwise it continues its parent's
     heads = big & ((ident == root) | (nbig[lp] >= 2))
-    head = _jump(np.where(big & ~heads, lp, ident))                 # for a big level node: the node that heads its cluster
+    head = _graph.jump(np.where(big & ~heads, lp, ident))          # for a big level node: the node that heads its cluster
     head_nodes = np.nonzero(heads)[0][::-1]                         # the root first; a parent cluster before its children
     ncl = len(head_nodes)
     cid = np.full(N, -1, np.int64)
@@ -315,7 +306,7 @@ def tree_from_mst(n, lo, hi, w2, min_cluster_size, method="eom"):
     cl_parent = np.full(ncl, -1, np.int64)
     cl_parent[1:] = c_parent
     # point rows: a point leaves with the topmost level ancestor-or-self below min_cluster_size, at that node's level parent
-    top = _jump(np.where(is_level & ~big[lp] & (ident != root), lp, ident))
+    top = _graph.jump(np.where(is_level & ~big[lp] & (ident != root), lp, ident))
     pts = np.arange(n, dtype=np.int64)
     leave = lp[top[pts]]
     p_parent, p_lambda = cid[head[leave]], lam_node[leave]

@@ -43,7 +43,7 @@ import sys
 
 import numpy as np
 
-from . import _common
+from . import _common, _graph
 from ._common import Launcher, d2_rows, is_int, ptr, row_chunks
 
 MAX_N, MAX_D, MAX_K, MAX_ROWS = 262144, 2048, 301, 4194304
@@ -130,7 +130,8 @@ def _sorted_rows(A, s0, s1):
 
 
 def knn_numpy(B, k):
-    """N_B [n][k] int64 of rule 3"""
+    """N_B [n][k] int64 of rule 3, by rule 2's difference chains, the row itself left out (tsne.knn_numpy screens by a Gram matrix
+    first and tsne.knn_query_numpy leaves nothing out: they stay apart)"""
     B = np.asarray(B, np.float64)
     n = B.shape[0]
     idx = np.empty((n, k), np.int64)
@@ -157,15 +158,6 @@ def ranks_numpy(A, idx):
 
 
 # ---- device
-
-def _knn_device(L, B, k):
-    n, d = (int(s) for s in B.shape)
-    torch = L.torch
-    idx = torch.empty((n, k), dtype=torch.int32, device=L.dev)
-    d2 = torch.empty((n, k), dtype=torch.float64, device=L.dev)
-    L.call("ra_tsne_knn", ptr(B), n, d, k, ptr(idx), ptr(d2))
-    return idx
-
 
 def _ranks_device(L, A, idx, want_ranks=True, want_pen=True):
     """(rank int32 [n][k] or None, pen int64 [n] or None) of ra_embed_ranks, on the device"""
@@ -229,7 +221,7 @@ def _one_direction(rank_space, list_space, k, backend, details):
     else:
         L = Launcher(rank_space)
         with L.torch.cuda.device(L.dev):
-            idx = _knn_device(L, list_space, k)
+            idx = _graph.knn(L, list_space, k)[0]
             ranks, pen = _ranks_device(L, rank_space, idx, want_ranks=details)
             pen = pen.cpu().numpy()
             if details:
@@ -294,8 +286,8 @@ def embedding_quality(X, Y, n_neighbors=10, sample_size=None, random_state=None,
     else:
         L = Launcher(X)
         with L.torch.cuda.device(L.dev):
-            ranks, pen_t = _ranks_device(L, X, _knn_device(L, Y, k))
-            _, pen_c = _ranks_device(L, Y, _knn_device(L, X, k), want_ranks=False)
+            ranks, pen_t = _ranks_device(L, X, _graph.knn(L, Y, k)[0])
+            _, pen_c = _ranks_device(L, Y, _graph.knn(L, X, k)[0], want_ranks=False)
             qnx, lcmc, k_best = _coranking_device(L.torch, ranks)
             pen_t, pen_c = pen_t.cpu().numpy(), pen_c.cpu().numpy()
     T, tp = scores_from_penalties(pen_t, n, k)

@@ -24,7 +24,7 @@ The contract, rule by rule.  Everything after the neighbour lists is float64.
   2. Weights.  Directed w_ij for j in N(i).  affinity="connectivity" (sklearn's): w_ij = 1.  affinity="gaussian" (self-tuning):
      w_ij = exp(-D2_ij / (sigma_i sigma_j)), sigma_i = sqrt(D2 to the local_scale-th neighbour of i), 1 <= local_scale <=
      n_neighbors - 1; a row with sigma_i = 0 (duplicates) raises, naming the first such row.  a_ij = (w_ij [j in N(i)] + w_ji [i in
-     N(j)]) / 2, a_ii = 0: a CSR with the columns of a row ascending, built by tsne.py's stable-sort pattern (no scatter), so
+     N(j)]) / 2, a_ii = 0: a CSR with the columns of a row ascending, built by _graph.py's stable sort (no scatter), so
      a_ij == a_ji bit for bit.
   3. Components.  The connected components of a are numbered by lowest member: component [n] int32.  on_disconnected="largest"
      (default) embeds the largest component (ties: the lower number); its rows keep their order and are compacted to n_sub rows;
@@ -72,7 +72,7 @@ import warnings
 
 import numpy as np
 
-from . import _common
+from . import _common, _graph
 from ._common import Launcher, is_int, is_real, ptr
 
 MAX_N, MAX_D = 262144, 2048
@@ -160,49 +160,27 @@ def _weights_numpy(idx, d2, affinity, local_scale):
 
 
 def _symmetrize_numpy(idx, w):
-    n, k = idx.shape
-    rows = np.repeat(np.arange(n, dtype=np.int64), k)
-    cols = idx.reshape(-1).astype(np.int64)
-    keys = np.concatenate([rows * n + cols, cols * n + rows])
-    vals = np.concatenate([w.reshape(-1), w.reshape(-1)])
-    order = np.argsort(keys, kind="stable")
-    keys, vals = keys[order], vals[order]
-    uk, start, counts = np.unique(keys, return_index=True, return_counts=True)
-    second = vals[np.minimum(start + 1, len(vals) - 1)]
-    a = 0.5 * (vals[start] + np.where(counts == 2, second, 0.0))
-    indptr = np.searchsorted(uk // n, np.arange(n + 1, dtype=np.int64))
-    return indptr.astype(np.int32), (uk % n).astype(np.int32), a
-
-
-def _row_ids(indptr):
-    return np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+    indptr, indices, a, b = _graph.symmetrize_numpy(idx, w)
+    return indptr.astype(np.int32), indices.astype(np.int32), 0.5 * (a + b)
 
 
 def _row_sums_numpy(indptr, a):
     """sum_j a_ij with a row's entries added in row order (bincount adds in index order)"""
-    return np.bincount(_row_ids(indptr), weights=a, minlength=len(indptr) - 1)
+    return np.bincount(_graph.row_ids_numpy(indptr), weights=a, minlength=len(indptr) - 1)
 
 
 def _density_numpy(indptr, indices, a, alpha):
     if alpha == 0:
         return a
     q = _row_sums_numpy(indptr, a) ** alpha
-    return a / (q[_row_ids(indptr)] * q[indices])
-
-
-def _jump(up):
-    while True:
-        nxt = up[up]
-        if np.array_equal(nxt, up):
-            return up
-        up = nxt
+    return a / (q[_graph.row_ids_numpy(indptr)] * q[indices])
 
 
 def components_numpy(indptr, indices):
     """int64 [n]: the lowest member of every row's connected component, by the device's rounds (minimum-label hooking, pointer
-    compression)"""
+    compression).  Apart from dbscan._components, which hooks over an edge list and counts its rounds."""
     n = len(indptr) - 1
-    rows, cols = _row_ids(indptr), np.asarray(indices, np.int64)
+    rows, cols = _graph.row_ids_numpy(indptr), np.asarray(indices, np.int64)
     label = np.arange(n, dtype=np.int64)
     while True:
         m = label.copy()
@@ -211,7 +189,7 @@ def components_numpy(indptr, indices):
         hook = np.nonzero(m < label)[0]
         np.minimum.at(P, label[hook], m[hook])
         np.minimum.at(P, hook, m[hook])
-        new = _jump(P)
+        new = _graph.jump(P)
         if np.array_equal(new, label):
             return label
         label = new
@@ -234,7 +212,7 @@ def check_graph(indptr, indices, a):
           "indptr ascends from 0 to nnz = len(indices) = len(a) < 2^31")
     _need(len(indices) > 0, "the graph has no edges")
     _need(indices.min() >= 0 and indices.max() < n, "a column index is outside 0 .. n - 1")
-    rows = _row_ids(indptr)
+    rows = _graph.row_ids_numpy(indptr)
     keys = rows * n + indices.astype(np.int64)
     _need(np.all(np.diff(keys) > 0), "the columns of a row ascend strictly")
     _need(not np.any(rows == indices), "the diagonal is not stored (a_ii = 0)")
@@ -249,14 +227,8 @@ def check_graph(indptr, indices, a):
 # ---- the same on the device
 
 class _Device(Launcher):
-    """rules 1 - 5 on the current stream of X's device: ra_tsne_knn, torch plumbing, ra_spectral_components and ra_spectral_spmv"""
-
-    def knn(self, X, k):
-        n, d = (int(s) for s in X.shape)
-        idx = self.torch.empty((n, k), dtype=self.torch.int32, device=self.dev)
-        d2 = self.torch.empty((n, k), dtype=self.torch.float64, device=self.dev)
-        self.call("ra_tsne_knn", ptr(X), n, d, k, ptr(idx), ptr(d2))
-        return idx, d2
+    """rules 2 - 5 on the current stream of X's device: torch plumbing, ra_spectral_components and ra_spectral_spmv (rule 1's lists
+    are _graph.knn's)"""
 
     def weights(self, idx, d2, affinity, local_scale):
         torch = self.torch
@@ -269,25 +241,8 @@ class _Device(Launcher):
         return torch.exp(-d2 / (sigma[:, None] * sigma[idx.long()]))
 
     def symmetrize(self, idx, w):
-        """tsne.py's pattern: a stable sort of the keys i n + j, then the (at most two) entries of each key added"""
-        torch = self.torch
-        n, k = (int(s) for s in idx.shape)
-        rows = torch.arange(n, device=self.dev, dtype=torch.int64).repeat_interleave(k)
-        cols = idx.reshape(-1).to(torch.int64)
-        keys = torch.cat([rows * n + cols, cols * n + rows])
-        vals = torch.cat([w.reshape(-1), w.reshape(-1)])
-        keys, order = torch.sort(keys, stable=True)
-        vals = vals[order]
-        uk, counts = torch.unique_consecutive(keys, return_counts=True)
-        start = torch.cumsum(counts, 0) - counts
-        second = vals[torch.clamp(start + 1, max=vals.numel() - 1)]
-        a = 0.5 * (vals[start] + torch.where(counts == 2, second, torch.zeros_like(second)))
-        indptr = torch.searchsorted(uk // n, torch.arange(n + 1, device=self.dev, dtype=torch.int64))
-        return indptr.to(torch.int32), (uk % n).to(torch.int32), a
-
-    def row_ids(self, indptr):
-        n = int(indptr.numel()) - 1
-        return self.torch.arange(n, device=self.dev, dtype=self.torch.int64).repeat_interleave((indptr[1:] - indptr[:-1]).long())
+        indptr, indices, a, b = _graph.symmetrize_torch(idx, w)
+        return indptr.to(self.torch.int32), indices.to(self.torch.int32), 0.5 * (a + b)
 
     def spmv(self, indptr, indices, val, x):
         y = self.torch.empty_like(x)
@@ -302,7 +257,7 @@ class _Device(Launcher):
         if alpha == 0:
             return a
         q = self.row_sums(indptr, indices, a) ** alpha
-        return a / (q[self.row_ids(indptr)] * q[indices.long()])
+        return a / (q[_graph.row_ids_torch(indptr)] * q[indices.long()])
 
     def components(self, indptr, indices):
         torch = self.torch
@@ -319,7 +274,7 @@ class _Device(Launcher):
 def _graph_device(X, n_neighbors, affinity, local_scale, alpha):
     D = _Device(X)
     with D.torch.cuda.device(D.dev):
-        idx, d2 = D.knn(X, n_neighbors - 1)
+        idx, d2 = _graph.knn(D, X, n_neighbors - 1)
         indptr, indices, a = D.symmetrize(idx, D.weights(idx, d2, affinity, local_scale))
         a = D.density(indptr, indices, a, alpha)
         root = D.components(indptr, indices)
@@ -359,7 +314,7 @@ class _NumpyOperator:
 
     def __init__(self, indptr, indices, a):
         self.indptr, self.indices, self.n = indptr, indices.astype(np.int64), len(indptr) - 1
-        self.rows = _row_ids(indptr)
+        self.rows = _graph.row_ids_numpy(indptr)
         self.deg = _row_sums_numpy(indptr, a)
         _need(bool(np.all(self.deg > 0)), "a row of the embedded component has degree 0 (weights that underflow)")
         self.s = 1.0 / np.sqrt(self.deg)
@@ -404,7 +359,7 @@ class _DeviceOperator:
         _need(bool(np.all(self.deg > 0)), "a row of the embedded component has degree 0 (weights that underflow)")
         s = 1.0 / D.torch.sqrt(deg)
         self.s = s.cpu().numpy()
-        self.val = ((s[D.row_ids(indptr)] * a) * s[indices.long()]).contiguous()
+        self.val = ((s[_graph.row_ids_torch(indptr)] * a) * s[indices.long()]).contiguous()
 
     def start(self, q0, v0, m_max):
         torch, D = self.D.torch, self.D
@@ -526,7 +481,7 @@ def _sub_numpy(indptr, indices, a, rows, n):
         return indptr, indices, a
     new = np.full(n, -1, np.int64)
     new[rows] = np.arange(len(rows))
-    keep = new[_row_ids(indptr)] >= 0
+    keep = new[_graph.row_ids_numpy(indptr)] >= 0
     cnt = np.diff(indptr)[rows]
     return np.concatenate([[0], np.cumsum(cnt)]).astype(np.int32), new[indices[keep]].astype(np.int32), a[keep]
 
@@ -538,7 +493,7 @@ def _sub_device(D, indptr, indices, a, rows, n):
     new = torch.full((n,), -1, dtype=torch.int64, device=D.dev)
     r = torch.from_numpy(rows).to(D.dev)
     new[r] = torch.arange(len(rows), dtype=torch.int64, device=D.dev)
-    keep = new[D.row_ids(indptr)] >= 0
+    keep = new[_graph.row_ids_torch(indptr)] >= 0
     cnt = (indptr[1:] - indptr[:-1]).long()[r]
     sub = torch.cat([torch.zeros(1, dtype=torch.int64, device=D.dev), torch.cumsum(cnt, 0)])
     return sub.to(torch.int32), new[indices.long()[keep]].to(torch.int32), a[keep].contiguous()

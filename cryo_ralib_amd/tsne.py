@@ -65,7 +65,7 @@ import sys
 
 import numpy as np
 
-from . import _common
+from . import _common, _graph
 from ._common import Launcher, ptr
 from .sdr import fix_signs
 
@@ -137,7 +137,8 @@ def _scale_pca(F):
 # ---- CPU checker (float64 numpy)
 
 def knn_numpy(X, k):
-    """(idx [n][k] int64, dist2 [n][k] float64): float64 brute force, itself excluded, ordered by (squared distance, index)"""
+    """(idx [n][k] int64, dist2 [n][k] float64): float64 brute force, itself excluded, ordered by (squared distance, index).  A Gram
+    screen plus a re-rank, as the kernel: apart from knn_query_numpy and quality.knn_numpy, which form difference chains only."""
     X = np.asarray(X, np.float64)
     n = X.shape[0]
     nrm = np.einsum("ij,ij->i", X, X)
@@ -191,23 +192,10 @@ def binary_search_perplexity(dist2, perplexity):
     return P
 
 
-def _symmetrize_numpy(idx, pcond, n):
-    k = idx.shape[1]
-    rows = np.repeat(np.arange(n, dtype=np.int64), k)
-    cols = idx.reshape(-1).astype(np.int64)
-    keys = np.concatenate([rows * n + cols, cols * n + rows])
-    vals = np.concatenate([pcond.reshape(-1), pcond.reshape(-1)])
-    o = np.argsort(keys, kind="stable")
-    keys, vals = keys[o], vals[o]
-    uk, start, counts = np.unique(keys, return_index=True, return_counts=True)
-    v = vals[start] + np.where(counts == 2, vals[np.minimum(start + 1, len(vals) - 1)], 0.0)
-    v = v / max(float(np.sum(v)), MACHINE_EPSILON)
-    indptr = np.searchsorted(uk // n, np.arange(n + 1)).astype(np.int64)
-    return indptr, (uk % n).astype(np.int64), v
-
-
-def _csr_rows(indptr):
-    return np.repeat(np.arange(len(indptr) - 1), np.diff(indptr))
+def _symmetrize_numpy(idx, pcond):
+    indptr, indices, a, b = _graph.symmetrize_numpy(idx, pcond)
+    v = a + b
+    return indptr, indices, v / max(float(np.sum(v)), MACHINE_EPSILON)
 
 
 def gradient_numpy(Y, csr, exaggeration=1.0):
@@ -226,7 +214,7 @@ def gradient_numpy(Y, csr, exaggeration=1.0):
         Z += float(np.sum(w))
         rep[s:e] = np.einsum("ij,ijk->ik", w * w, D)
     Z = max(Z, MACHINE_EPSILON)
-    rows = _csr_rows(indptr)
+    rows = _graph.row_ids_numpy(indptr)
     D = Y[rows] - Y[indices]
     w = 1.0 / (1.0 + np.sum(D * D, axis=1))
     pe = exaggeration * np.asarray(P, np.float64)
@@ -264,19 +252,8 @@ class _NumpyState:
 
 # ---- device
 
-class _Device:
-    """thin launcher of the ra_tsne_* entries on the current stream of X's device"""
-
-    def __init__(self, dev):
-        L = Launcher(dev)
-        self.torch, self.api, self.lib, self.dev, self.stream, self.call = L.torch, L.api, L.lib, L.dev, L.stream, L.call
-
-    def knn(self, X, k):
-        n, d = (int(s) for s in X.shape)
-        idx = self.torch.empty((n, k), dtype=self.torch.int32, device=self.dev)
-        d2 = self.torch.empty((n, k), dtype=self.torch.float64, device=self.dev)
-        self.call("ra_tsne_knn", ptr(X), n, d, k, ptr(idx), ptr(d2))
-        return idx, d2
+class _Device(Launcher):
+    """thin launcher of the ra_tsne_* entries on the current stream of a device; the lists come from _graph.knn / knn_query"""
 
     def affinity(self, d2, perplexity):
         n, k = (int(s) for s in d2.shape)
@@ -285,23 +262,12 @@ class _Device:
         return pc
 
     def symmetrize(self, idx, pc):
-        """CSR of (P_c + P_c^T) / max(sum, eps) on the device: a stable sort of the keys i n + j, then the (at most two) entries of
-        each key added; deterministic (no scatter)"""
+        """CSR of (P_c + P_c^T) / max(sum, eps) on the device"""
         torch = self.torch
-        n, k = (int(s) for s in idx.shape)
-        rows = torch.arange(n, device=self.dev, dtype=torch.int64).repeat_interleave(k)
-        cols = idx.reshape(-1).to(torch.int64)
-        keys = torch.cat([rows * n + cols, cols * n + rows])
-        vals = torch.cat([pc.reshape(-1), pc.reshape(-1)])
-        keys, order = torch.sort(keys, stable=True)
-        vals = vals[order]
-        uk, counts = torch.unique_consecutive(keys, return_counts=True)
-        start = torch.cumsum(counts, 0) - counts
-        second = vals[torch.clamp(start + 1, max=vals.numel() - 1)]
-        v = vals[start] + torch.where(counts == 2, second, torch.zeros_like(second))
+        indptr, indices, a, b = _graph.symmetrize_torch(idx, pc)
+        v = a + b
         v = v / torch.clamp(v.sum(), min=MACHINE_EPSILON)
-        indptr = torch.searchsorted(uk // n, torch.arange(n + 1, device=self.dev, dtype=torch.int64))
-        return indptr.to(torch.int32), (uk % n).to(torch.int32), v
+        return indptr.to(torch.int32), indices.to(torch.int32), v
 
     def gradient(self, y, indptr, indices, p32, exaggeration):
         n = int(y.shape[0])
@@ -309,13 +275,6 @@ class _Device:
         st = self.torch.empty(2, dtype=self.torch.float64, device=self.dev)
         self.call("ra_tsne_error", ptr(y), n, ptr(indptr), ptr(indices), ptr(p32), int(p32.numel()), float(exaggeration), ptr(g), ptr(st))
         return float(st[0].item()), g
-
-    def knn_query(self, Q, X, k):
-        nq, d = (int(s) for s in Q.shape)
-        idx = self.torch.empty((nq, k), dtype=self.torch.int32, device=self.dev)
-        d2 = self.torch.empty((nq, k), dtype=self.torch.float64, device=self.dev)
-        self.call("ra_tsne_knn_query", ptr(Q), nq, ptr(X), int(X.shape[0]), d, k, ptr(idx), ptr(d2))
-        return idx, d2
 
     def affinity_rows(self, d2, perplexity):
         rows, k = (int(s) for s in d2.shape)
@@ -413,11 +372,11 @@ def affinities(X, perplexity=30.0, backend="device"):
     k = n_neighbors(n, perplexity)
     if backend == "numpy":
         idx, d2 = knn_numpy(X, k)
-        return _symmetrize_numpy(idx, binary_search_perplexity(d2, perplexity), n)
+        return _symmetrize_numpy(idx, binary_search_perplexity(d2, perplexity))
     import torch
     with torch.cuda.device(X.device):
         D = _Device(X.device)
-        idx, d2 = D.knn(X, k)
+        idx, d2 = _graph.knn(D, X, k)
         indptr, indices, P = D.symmetrize(idx, D.affinity(d2, perplexity))
         return indptr.cpu().numpy().astype(np.int64), indices.cpu().numpy().astype(np.int64), P.cpu().numpy()
 
@@ -432,7 +391,7 @@ def knn(X, k, backend="device"):
         return knn_numpy(X, k)
     import torch
     with torch.cuda.device(X.device):
-        idx, d2 = _Device(X.device).knn(X, k)
+        idx, d2 = _graph.knn(Launcher(X), X, k)
         return idx.cpu().numpy().astype(np.int64), d2.cpu().numpy()
 
 
@@ -497,14 +456,14 @@ def tsne(X, perplexity=30.0, early_exaggeration=12.0, learning_rate="auto", max_
     k = n_neighbors(n, perplexity)
     if backend == "numpy":
         idx, d2 = knn_numpy(X, k)
-        csr = _symmetrize_numpy(idx, binary_search_perplexity(d2, perplexity), n)
+        csr = _symmetrize_numpy(idx, binary_search_perplexity(d2, perplexity))
         state = _NumpyState(Y0, csr)
         err, it, errors = _optimise(state, max_iter, early_exaggeration, lr, n_iter_without_progress, min_grad_norm)
         return TsneResult(state.embedding(), err, it, errors)
     import torch
     with torch.cuda.device(X.device):
         D = _Device(X.device)
-        idx, d2 = D.knn(X, k)
+        idx, d2 = _graph.knn(D, X, k)
         indptr, indices, P = D.symmetrize(idx, D.affinity(d2, perplexity))
         state = _DeviceState(D, torch.from_numpy(Y0).to(X.device), indptr, indices, P.to(torch.float32))
         err, it, errors = _optimise(state, max_iter, early_exaggeration, lr, n_iter_without_progress, min_grad_norm)
@@ -598,7 +557,8 @@ def check_transform_domain(n, m, d, perplexity=30.0, learning_rate=0.1, momentum
 
 
 def knn_query_numpy(Q, X, k):
-    """rule 1 in float64: (idx [nq][k] int64, dist2 [nq][k]) of the k rows of X nearest each row of Q, by (distance, index)"""
+    """rule 1 in float64: (idx [nq][k] int64, dist2 [nq][k]) of the k rows of X nearest each row of Q, by (distance, index).
+    Difference chains, nothing left out: apart from quality.knn_numpy, which leaves the row itself out and returns no distances."""
     Q, X = np.asarray(Q, np.float64), np.asarray(X, np.float64)
     nq, m = Q.shape[0], X.shape[0]
     idx = np.empty((nq, k), np.int64)
@@ -699,10 +659,6 @@ def _initial_placement_device(torch, init, Y_fit, idx, p32):
     return acc.float().contiguous()
 
 
-def _host_finite(A, step=1 << 16):
-    return all(bool(np.all(np.isfinite(A[s:s + step]))) for s in range(0, A.shape[0], step))
-
-
 def knn_query(Q, X, k, backend="device"):
     """rule 1: (idx [nq][k], dist2 [nq][k] float64) of the k rows of X [m][d] nearest every row of Q [nq][d], as numpy arrays"""
     Q = _common.as_input(Q, backend, TsneError)
@@ -715,7 +671,7 @@ def knn_query(Q, X, k, backend="device"):
         return knn_query_numpy(np.asarray(Q, np.float32), np.asarray(X, np.float32), k)
     import torch
     with torch.cuda.device(X.device):
-        idx, d2 = _Device(X.device).knn_query(Q, X, k)
+        idx, d2 = _graph.knn_query(Launcher(X), Q, X, k)
         return idx.cpu().numpy().astype(np.int64), d2.cpu().numpy()
 
 
@@ -744,7 +700,7 @@ def transform(X_new, X_fit, Y_fit, perplexity=30.0, learning_rate=0.1, momentum=
     init = _check_init(init, n)
     _common.check_finite(Xf, backend, TsneError)
     _common.check_finite(Yf, backend, TsneError)
-    if not (_host_finite(Xn) if host_new else bool(Xn.isfinite().all().item())):
+    if not (_common.host_finite(Xn) if host_new else bool(Xn.isfinite().all().item())):
         raise TsneError("X holds NaN or infinite values")
     k = n_neighbors_query(m, perplexity)
     emb, kl = np.empty((n, 2), np.float32), np.empty(n, np.float64)
@@ -765,7 +721,7 @@ def transform(X_new, X_fit, Y_fit, perplexity=30.0, learning_rate=0.1, momentum=
                 emb[s:e] = y.astype(np.float32)
             else:
                 xb = torch.from_numpy(np.ascontiguousarray(Xn[s:e], np.float32)).to(D.dev) if host_new else Xn[s:e]
-                idx, d2 = D.knn_query(xb, Xf, k)
+                idx, d2 = _graph.knn_query(D, xb, Xf, k)
                 p = D.affinity_rows(d2, perplexity).to(torch.float32)
                 y = _initial_placement_device(torch, y0, Yf, idx, p)
                 if details:
@@ -804,7 +760,7 @@ def affinities_query(X_new, X_fit, perplexity=30.0, batch=65536, backend="device
             p_all[s:s + batch] = binary_search_perplexity(d2, perplexity)
         else:
             with torch.cuda.device(Xf.device):
-                idx, d2 = D.knn_query(torch.from_numpy(xb).to(D.dev), Xf, k)
+                idx, d2 = _graph.knn_query(D, torch.from_numpy(xb).to(D.dev), Xf, k)
                 idx_all[s:s + batch] = idx.cpu().numpy()
                 p_all[s:s + batch] = D.affinity_rows(d2, perplexity).to(torch.float32).cpu().numpy()
     return idx_all, p_all

@@ -33,7 +33,7 @@ The contract, rule by rule.  Positions are float32; everything else is float64.
      (The device adds psum's terms lane by lane and then across the lanes, ralign_umap.h: psum may differ from list order by the
      roundings of k additions; the mean is added in list order there too.)
   3. Fuzzy union.  s_ij = w_ij + w_ji - w_ij w_ji, a missing direction counting 0: a CSR with the columns of a row ascending, built
-     by spectral.py's stable-sort pattern.  Both operations commute, so s_ij == s_ji bit for bit.
+     by _graph.py's stable sort.  Both operations commute, so s_ij == s_ji bit for bit.
   4. Curve.  (a, b) = scipy.optimize.curve_fit of 1 / (1 + a x^(2b)) to x = linspace(0, 3 spread, 300), y = 1 for x < min_dist, else
      exp(-(x - min_dist) / spread) (find_ab_params), on the host.  The defaults give a = 1.5769434603, b = 0.8950608779.  a and b may
      be passed instead.
@@ -81,7 +81,7 @@ import warnings
 
 import numpy as np
 
-from . import _common
+from . import _common, _graph
 from ._common import Launcher, is_int, is_real, ptr
 
 MAX_N, MAX_D = 262144, 2048
@@ -238,23 +238,8 @@ def smooth_knn_numpy(dist2, n_neighbors):
 
 
 def _union_numpy(idx, w):
-    n, k = idx.shape
-    rows = np.repeat(np.arange(n, dtype=np.int64), k)
-    cols = idx.reshape(-1).astype(np.int64)
-    keys = np.concatenate([rows * n + cols, cols * n + rows])
-    vals = np.concatenate([w.reshape(-1), w.reshape(-1)])
-    order = np.argsort(keys, kind="stable")
-    keys, vals = keys[order], vals[order]
-    uk, start, counts = np.unique(keys, return_index=True, return_counts=True)
-    first = vals[start]
-    second = np.where(counts == 2, vals[np.minimum(start + 1, len(vals) - 1)], 0.0)
-    s = first + second - first * second
-    indptr = np.searchsorted(uk // n, np.arange(n + 1, dtype=np.int64))
-    return indptr.astype(np.int32), (uk % n).astype(np.int32), s
-
-
-def _row_ids(indptr):
-    return np.repeat(np.arange(len(indptr) - 1, dtype=np.int64), np.diff(indptr))
+    indptr, indices, first, second = _graph.symmetrize_numpy(idx, w)
+    return indptr.astype(np.int32), indices.astype(np.int32), first + second - first * second
 
 
 # ---- rules 5 and 6 in numpy: the checker
@@ -340,7 +325,7 @@ def epoch_numpy(Y, indptr, indices, rate, a, b, t, n_epochs, gamma=1.0, negative
     n = Y64.shape[0]
     indptr, indices = np.asarray(indptr, np.int64), np.asarray(indices, np.int64)
     p = np.nonzero(fires(np.asarray(rate, np.float64), t))[0]
-    i = _row_ids(indptr)[p]
+    i = _graph.row_ids_numpy(indptr)[p]
     j = indices[p]
     terms = np.empty((len(p), 1 + negative_sample_rate, 2))
     terms[:, 0] = _attract(Y64[i], Y64[j], a, b, 2.0)
@@ -383,12 +368,7 @@ def start_numpy(Y_fit, idx, w):
 # ---- the same on the device
 
 class _Device(Launcher):
-    """rules 1 - 3, 6 and 8 on the current stream of X's device"""
-
-    def __init__(self, where):
-        Launcher.__init__(self, where)
-        from . import tsne
-        self.lists = tsne._Device(self.dev)
+    """rules 2, 3, 6 and 8 on the current stream of X's device (rule 1's lists are _graph.knn's and knn_query's)"""
 
     def smooth_knn(self, d2, n_neighbors):
         torch = self.torch
@@ -400,23 +380,8 @@ class _Device(Launcher):
         return rho, sigma, w
 
     def union(self, idx, w):
-        """spectral._Device.symmetrize's pattern with rule 3's combine"""
-        torch = self.torch
-        n, k = (int(s) for s in idx.shape)
-        rows = torch.arange(n, device=self.dev, dtype=torch.int64).repeat_interleave(k)
-        cols = idx.reshape(-1).to(torch.int64)
-        keys = torch.cat([rows * n + cols, cols * n + rows])
-        vals = torch.cat([w.reshape(-1), w.reshape(-1)])
-        keys, order = torch.sort(keys, stable=True)
-        vals = vals[order]
-        uk, counts = torch.unique_consecutive(keys, return_counts=True)
-        start = torch.cumsum(counts, 0) - counts
-        first = vals[start]
-        second = vals[torch.clamp(start + 1, max=vals.numel() - 1)]
-        second = torch.where(counts == 2, second, torch.zeros_like(second))
-        s = first + second - first * second
-        indptr = torch.searchsorted(uk // n, torch.arange(n + 1, device=self.dev, dtype=torch.int64))
-        return indptr.to(torch.int32), (uk % n).to(torch.int32), s
+        indptr, indices, first, second = _graph.symmetrize_torch(idx, w)
+        return indptr.to(self.torch.int32), indices.to(self.torch.int32), first + second - first * second
 
     def epochs(self, y, indptr, indices, rate, a, b, gamma, neg, lr, n_epochs, epoch0, count, seed):
         """`count` epochs from epoch0 on the float32 tensor y [n][2]; returns the tensor that holds the result"""
@@ -446,7 +411,7 @@ class _Device(Launcher):
 def _graph_device(X, n_neighbors):
     D = _Device(X)
     with D.torch.cuda.device(D.dev):
-        idx, d2 = D.lists.knn(X, n_neighbors - 1)
+        idx, d2 = _graph.knn(D, X, n_neighbors - 1)
         rho, sigma, w = D.smooth_knn(d2, n_neighbors)
         indptr, indices, s = D.union(idx, w)
     return D, indptr, indices, s, rho, sigma
@@ -624,10 +589,6 @@ def check_transform_domain(n, m, d, n_neighbors=15, batch=65536):
     _need(1 <= batch <= MAX_BATCH, "need 1 <= batch <= %d, got %d" % (MAX_BATCH, batch))
 
 
-def _host_finite(A, step=1 << 16):
-    return all(bool(np.all(np.isfinite(A[s:s + step]))) for s in range(0, A.shape[0], step))
-
-
 def transform(X_new, X_fit, Y_fit, n_neighbors=15, min_dist=0.1, spread=1.0, n_epochs=100, learning_rate=1.0, negative_sample_rate=5,
               repulsion_strength=1.0, random_state=42, a=None, b=None, batch=65536, backend="device", details=False):
     """Place X_new [n][d] into the embedding Y_fit [m][2] of X_fit [m][d] (rule 8): the embedding [n][2] float32, or with details
@@ -649,7 +610,7 @@ def transform(X_new, X_fit, Y_fit, n_neighbors=15, min_dist=0.1, spread=1.0, n_e
     check_transform_domain(n, m, d, n_neighbors, batch)
     _common.check_finite(Xf, backend, UmapError)
     _common.check_finite(Yf, backend, UmapError)
-    _need(_host_finite(Xn) if host_new else bool(Xn.isfinite().all().item()), "X holds NaN or infinite values")
+    _need(_common.host_finite(Xn) if host_new else bool(Xn.isfinite().all().item()), "X holds NaN or infinite values")
     if a is None:
         a, b = find_ab(spread, min_dist)
     k = min(m, n_neighbors)
@@ -670,7 +631,7 @@ def transform(X_new, X_fit, Y_fit, n_neighbors=15, min_dist=0.1, spread=1.0, n_e
                 start[s:e] = y0
             else:
                 xb = torch.from_numpy(np.ascontiguousarray(Xn[s:e], np.float32)).to(D.dev) if host_new else Xn[s:e]
-                idx, d2 = D.lists.knn_query(xb, Xf, k)
+                idx, d2 = _graph.knn_query(D, xb, Xf, k)
                 w = D.smooth_knn(d2, n_neighbors)[2]
                 y = D.start(Yf, idx, w)
                 start[s:e] = y.cpu().numpy()

@@ -65,7 +65,7 @@ import sys
 
 import numpy as np
 
-from . import _common
+from . import _common, _graph
 from ._common import Launcher, is_int, is_real, ptr, row_chunks
 
 MAX_N, MAX_D = 262144, 2048
@@ -326,15 +326,6 @@ def greedy_numpy(X):
 
 # ---- rule 6
 
-def _jump(up):
-    """the fixed point of x -> up[x] for every x, by pointer doubling"""
-    while True:
-        nxt = up[up]
-        if np.array_equal(nxt, up):
-            return up
-        up = nxt
-
-
 def n_clusters_at(tree, distance_threshold):
     """sklearn's rule: the merges with height >= t are undone"""
     return int(np.count_nonzero(tree.heights >= distance_threshold)) + 1
@@ -349,7 +340,7 @@ def cut(tree, n_clusters=None, distance_threshold=None):
     m = tree.n - k
     up = np.arange(tree.n, dtype=np.int64)
     up[tree.merges[:m, 1]] = tree.merges[:m, 0]
-    root = _jump(up)
+    root = _graph.jump(up)
     return np.searchsorted(np.unique(root), root).astype(np.int32)
 
 

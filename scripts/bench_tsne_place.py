@@ -24,7 +24,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "scripts"))
-from cryo_ralib_amd import tsne  # noqa: E402
+from cryo_ralib_amd import _graph, tsne  # noqa: E402
 from cryo_ralib_amd._common import ptr  # noqa: E402
 from bench_tsne import make_factors  # noqa: E402
 
@@ -83,8 +83,8 @@ def run_row(name, n, xf, yf, dev, args):
     with torch.cuda.device(dev):
         D = tsne._Device(dev)
         x = torch.from_numpy(X).to(dev)
-        (row["knn_query_ms"],) = alternate([lambda: D.knn_query(x, xf, k)], dev, args.reps, args.warmup)
-        idx, d2 = D.knn_query(x, xf, k)
+        (row["knn_query_ms"],) = alternate([lambda: _graph.knn_query(D, x, xf, k)], dev, args.reps, args.warmup)
+        idx, d2 = _graph.knn_query(D, x, xf, k)
         (row["affinity_ms"],) = alternate([lambda: D.affinity_rows(d2, PERPLEXITY)], dev, args.reps, args.warmup)
         p = D.affinity_rows(d2, PERPLEXITY).to(torch.float32)
         y0 = tsne._initial_placement_device(torch, "weighted", yf, idx, p)
@@ -103,7 +103,7 @@ def run_row(name, n, xf, yf, dev, args):
             names.append("torch_ms")
         if name == "50k":
             # the fit's own step on the same fitted rows, from its own affinities
-            fi, fd2 = D.knn(xf, tsne.n_neighbors(m, PERPLEXITY))
+            fi, fd2 = _graph.knn(D, xf, tsne.n_neighbors(m, PERPLEXITY))
             indptr, indices, P = D.symmetrize(fi, D.affinity(fd2, PERPLEXITY))
             st = tsne._DeviceState(D, yf.clone(), indptr, indices, P.to(torch.float32))
             st.reset()

@@ -30,7 +30,7 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
-from cryo_ralib_amd import tsne, umap  # noqa: E402
+from cryo_ralib_amd import _graph, tsne, umap  # noqa: E402
 from bench_dbscan import ROWS, make_factors, make_row, timed  # noqa: E402
 
 N_NEIGHBORS, N_EPOCHS, NEG, SEED, BATCH = 15, 200, 5, 42, 65536
@@ -91,7 +91,7 @@ def bench_place(Xf, Yf, a, b, dev, n_new):
 
     def batch(s, keep):
         xb = torch.from_numpy(X_new[s:s + BATCH]).to(dev)
-        (idx, d2), t1 = timed(lambda: D.lists.knn_query(xb, xf, N_NEIGHBORS), dev)
+        (idx, d2), t1 = timed(lambda: _graph.knn_query(D, xb, xf, N_NEIGHBORS), dev)
         w, t2 = timed(lambda: D.smooth_knn(d2, N_NEIGHBORS)[2], dev)
         y, t3 = timed(lambda: D.start(yf, idx, w), dev)
         rate = (w / w.max(dim=1).values[:, None]).contiguous()

@@ -1,9 +1,9 @@
-// Checks the offset arithmetic of KmScratch / KmLists (cryo_ralib_amd/csrc/ralign_scratch.h) on the host, without a device:
+// Checks the offset arithmetic of KmScratch / KmLists / KmColumns (cryo_ralib_amd/csrc/ralign_scratch.h) on the host, without a device:
 //
 //     g++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -Icryo_ralib_amd/csrc \
 //         scripts/dev/km_scratch_check.cpp -o km_scratch_check && ./km_scratch_check
 //
-// For a handful of (n, k, d) it carves the scratch of the four entries that hold member lists the way ralign_embed.hip does,
+// For a handful of (n, k, d) it carves the scratch of the five entries that hold member lists the way ralign_embed.hip does,
 // backs it with a real allocation of exactly S.off bytes and writes every piece end to end (so the sanitizer sees any piece that
 // leaves the allocation), and asserts that every offset is 256-aligned, that no two pieces overlap and that the total is the sum
 // of the pieces, each rounded up to 256 bytes.
@@ -67,6 +67,19 @@ static std::vector<Piece> lists(const KmLists &M, int n, int k)
     return p;
 }
 
+// the pieces of the padded column lists: the member lists, pstart [k + 1] and cols [n + k tc]
+static std::vector<Piece> columns(const KmColumns &Cl, int n, int k, int tc)
+{
+    std::vector<Piece> p = lists(Cl.M, n, k);
+    p.push_back({Cl.o_pstart, (size_t)(k + 1) * 4});
+    p.push_back({Cl.o_cols, ((size_t)n + (size_t)k * tc) * 4});
+    if (Cl.cap != n + k * tc) {
+        std::printf("FAILED cap n = %d k = %d\n", n, k);
+        ++failures;
+    }
+    return p;
+}
+
 static void one(int n, int k, int d)
 {
     const int L = run_len(n), rmax = (n + L - 1) / L + k;
@@ -82,10 +95,8 @@ static void one(int n, int k, int d)
     }
     {   // ra_kmeans_silhouette
         KmScratch S;
-        const KmLists M(S, n, k, KM_BLOCK);
-        std::vector<Piece> p = lists(M, n, k);
-        for (size_t b : {(size_t)(k + 1) * 4, ((size_t)n + (size_t)k * VAL_TC) * 4}) p.push_back({S.take(b), b});
-        check("silhouette", n, k, d, S, p);
+        const KmColumns Cl(S, n, k, KM_BLOCK, VAL_TC);
+        check("silhouette", n, k, d, S, columns(Cl, n, k, VAL_TC));
     }
     {   // ra_kmeans_dispersion
         KmScratch S;
@@ -94,12 +105,19 @@ static void one(int n, int k, int d)
         for (size_t b : {(size_t)rmax * d * 8, (size_t)k * d * 8, (size_t)k * 8, (size_t)n * 8}) p.push_back({S.take(b), b});
         check("dispersion", n, k, d, S, p);
     }
-    {   // ra_dbscan_step: the lists of two "clusters" (core or not)
+    {   // ra_dbscan_step: the column lists of two "clusters" (core or not), the flags, m and P
         KmScratch S;
-        const KmLists M(S, n, 2, KM_BLOCK);
-        std::vector<Piece> p = lists(M, n, 2);
-        for (size_t b : {(size_t)n * 4, (size_t)3 * 4, ((size_t)n + 2 * DBS_TC) * 4, (size_t)n * 4, (size_t)n * 4}) p.push_back({S.take(b), b});
+        const KmColumns Cl(S, n, 2, KM_BLOCK, DBS_TC);
+        std::vector<Piece> p = columns(Cl, n, 2, DBS_TC);
+        for (size_t b : {(size_t)n * 4, (size_t)n * 4, (size_t)n * 4}) p.push_back({S.take(b), b});
         check("dbscan_step", n, 2, d, S, p);
+    }
+    {   // ra_ward_nearest: the column lists of two "clusters" (live or dead) and the flags
+        KmScratch S;
+        const KmColumns Cl(S, n, 2, KM_BLOCK, DBS_TC);
+        std::vector<Piece> p = columns(Cl, n, 2, DBS_TC);
+        p.push_back({S.take((size_t)n * 4), (size_t)n * 4});
+        check("ward_nearest", n, 2, d, S, p);
     }
 }
 
@@ -115,6 +133,6 @@ int main()
                 one(n, k, d);
                 ++cases;
             }
-    std::printf("%d shapes x 4 entries, %d failures\n", cases, failures);
+    std::printf("%d shapes x 5 entries, %d failures\n", cases, failures);
     return failures ? 1 : 0;
 }

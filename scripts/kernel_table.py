@@ -3,6 +3,9 @@ second library, the comparison of the two (a refactor must leave every row as it
 
     python3 scripts/kernel_table.py NEW.so [OLD.so] > profiles/kernel_table.md
 
+Kernels are matched by their unqualified names (template arguments kept, parameter types dropped): a kernel whose argument
+struct was renamed has another mangled name and is still the same kernel.
+
 The code objects come out of the library with `llvm-objdump --offloading` (one per translation unit), the rows from
 `llvm-readelf --notes` (amdhsa.kernels) and the sizes from the kernel symbols (`llvm-readelf --symbols`)."""
 import glob
@@ -17,8 +20,19 @@ FIELDS = [".vgpr_count", ".agpr_count", ".sgpr_count", ".group_segment_fixed_siz
           ".max_flat_workgroup_size"]
 
 
+def unqualified(symbols):
+    """{mangled: name without return type, namespaces and parameter list}, by c++filt"""
+    plain = subprocess.check_output(["c++filt", "-p"] + symbols, text=True).split("\n")
+    out = {}
+    for m, d in zip(symbols, plain):
+        d = re.sub(r"^void ", "", d)
+        head = d.split("<")[0]
+        out[m] = head.split("::")[-1] + d[len(head):]
+    return out
+
+
 def kernels(lib):
-    """{kernel symbol: (vgpr, agpr, sgpr, lds, scratch, max workgroup, code bytes)} over every gfx950 code object of the library"""
+    """{kernel name: (vgpr, agpr, sgpr, lds, scratch, max workgroup, code bytes)} over every gfx950 code object of the library"""
     rows = {}
     with tempfile.TemporaryDirectory() as tmp:
         so = os.path.join(tmp, "lib.so")
@@ -33,7 +47,9 @@ def kernels(lib):
                 name = val[".name"]
                 assert name not in rows, "kernel %s in two code objects" % name
                 rows[name] = tuple(int(val.get(f, "0")) for f in FIELDS) + (size[name],)
-    return rows
+    short = unqualified(sorted(rows))
+    assert len(set(short.values())) == len(rows), "two kernels share an unqualified name"
+    return {short[name]: row for name, row in rows.items()}
 
 
 def main():

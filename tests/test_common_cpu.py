@@ -252,8 +252,11 @@ def sources():
     return sorted(glob.glob(os.path.join(PKG, "*.py")))
 
 
+SHARED = ("_common", "_graph")          # the modules every feature module may import from
+
+
 def test_no_module_imports_a_private_name_from_a_sibling():
-    """`from .x import _name` and `from . import _x` are allowed only for _common"""
+    """`from .x import _name` and `from . import _x` are allowed only for the shared modules"""
     bad = []
     for path in sources():
         for node in ast.walk(ast.parse(open(path).read(), path)):
@@ -261,17 +264,18 @@ def test_no_module_imports_a_private_name_from_a_sibling():
                 continue
             source = (node.module or "").split(".")[-1]
             for a in node.names:
-                if a.name.startswith("_") and not a.name.startswith("__") and a.name != "_common" and source != "_common":
+                if a.name.startswith("_") and not a.name.startswith("__") and a.name not in SHARED and source not in SHARED:
                     bad.append("%s: from %s import %s" % (os.path.basename(path), "." * node.level + (node.module or ""), a.name))
     assert not bad, bad
 
 
 def test_the_shared_helpers_are_defined_once():
-    """no module-level copy outside _common.py (Engine._ptr, a method that checks dtypes, is not one)"""
-    names = {"_ptr", "_as_input", "_check_finite", "_is_int", "_is_real", "ptr", "as_input", "check_finite", "is_int", "is_real"}
+    """no module-level copy outside _common.py and _graph.py (Engine._ptr, a method that checks dtypes, is not one)"""
+    names = {"_ptr", "_as_input", "_check_finite", "_is_int", "_is_real", "ptr", "as_input", "check_finite", "is_int", "is_real",
+             "_host_finite", "host_finite", "_jump", "jump", "_row_ids", "_csr_rows", "row_ids_numpy", "row_ids_torch"}
     bad = []
     for path in sources():
-        if os.path.basename(path) == "_common.py":
+        if os.path.basename(path)[:-3] in SHARED:
             continue
         for node in ast.parse(open(path).read(), path).body:
             if isinstance(node, (ast.FunctionDef, ast.AsyncFunctionDef)) and node.name in names:
@@ -279,7 +283,8 @@ def test_the_shared_helpers_are_defined_once():
     assert not bad, bad
     defined = {n.name for n in ast.parse(open(os.path.join(PKG, "_common.py")).read()).body if isinstance(n, ast.FunctionDef)}
     assert {"ptr", "as_input", "check_finite", "is_int", "is_real", "check_random_state", "read_input", "read_truth", "read_params",
-            "add_cluster_arguments", "check_averages_arguments", "require_gpu", "to_device", "truth_scores", "write_averages"} <= defined
+            "add_cluster_arguments", "check_averages_arguments", "require_gpu", "to_device", "truth_scores", "write_averages",
+            "host_finite"} <= defined
 
 
 def test_common_imports_no_feature_module_at_module_level():

@@ -29,7 +29,7 @@ pytestmark = pytest.mark.gpu
 torch = pytest.importorskip("torch")
 
 import umap_cases as uc  # noqa: E402
-from cryo_ralib_amd import api, umap  # noqa: E402
+from cryo_ralib_amd import _graph, api, umap  # noqa: E402
 
 RA_ERR_ARG = -1
 
@@ -294,7 +294,7 @@ def test_device_graph(blob, fits, dev):
     assert np.array_equal(indptr, got.graph[0]) and np.array_equal(indices, got.graph[1])
     keep = sk.margin >= uc.MARGIN
     assert np.mean(~keep) <= uc.MAX_LEFT_OUT
-    both = keep[umap._row_ids(indptr.astype(np.int64))] & keep[indices]
+    both = keep[_graph.row_ids_numpy(indptr.astype(np.int64))] & keep[indices]
     tol = 4 * (14 + 2) * uc.U
     rel = np.abs(got.graph[2] - s)[both] / s[both]
     print("s against rules 2 - 3 on the device's lists: worst %.3g of the bound; against the checker's own graph: worst relative %.3g"
@@ -302,10 +302,10 @@ def test_device_graph(blob, fits, dev):
     assert np.all(rel <= tol)
     assert np.all(np.abs(got.rho - sk.rho) <= np.spacing(sk.rho))
     same = np.all(tsne.knn_numpy(blob[0], 14)[1] == d2, axis=1) & keep
-    same2 = same[umap._row_ids(indptr.astype(np.int64))] & same[indices]
+    same2 = same[_graph.row_ids_numpy(indptr.astype(np.int64))] & same[indices]
     print("rows with bitwise equal distances from the two kNNs: %.3f; entries between two such rows: %.3f" % (same.mean(), same2.mean()))
     assert np.all(np.abs(got.graph[2] - ref.graph[2])[same2] <= tol * ref.graph[2][same2])
-    rows = umap._row_ids(got.graph[0].astype(np.int64))
+    rows = _graph.row_ids_numpy(got.graph[0].astype(np.int64))
     S = np.zeros((1500, 1500))
     S[rows, got.graph[1]] = got.graph[2]
     assert np.array_equal(S, S.T)

@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import umap_cases as uc
-from cryo_ralib_amd import tsne, umap
+from cryo_ralib_amd import _graph, tsne, umap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MASK = (1 << 64) - 1
@@ -110,7 +110,7 @@ def test_fuzzy_union_is_symmetric_and_matches_dense():
     W = np.zeros((n, n))
     W[np.repeat(np.arange(n), 9), idx.reshape(-1)] = umap.smooth_knn_numpy(d2, 10).w.reshape(-1)
     S = np.zeros((n, n))
-    rows = umap._row_ids(indptr.astype(np.int64))
+    rows = _graph.row_ids_numpy(indptr.astype(np.int64))
     S[rows, indices] = s
     assert np.array_equal(S, S.T)                                       # bit for bit
     assert np.all(s >= 0) and np.all(s <= 1)
@@ -244,7 +244,7 @@ def test_epoch_edges_case_matches_scalar_restatement(epoch_cases):
 def test_builder_epoch_conditions(epoch_cases):
     for name, case in epoch_cases.items():
         Y = case.Y.astype(np.float64)
-        rows = umap._row_ids(case.indptr.astype(np.int64))
+        rows = _graph.row_ids_numpy(case.indptr.astype(np.int64))
         cols = case.indices.astype(np.int64)
         q_att = np.sum((Y[rows] - Y[cols]) ** 2, axis=1)
         assert not np.any((q_att > 0) & (q_att < uc.Q_MIN)), name

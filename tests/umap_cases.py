@@ -2,7 +2,7 @@
 tests, with the conditions the GPU file relies on (asserted in the CPU file)."""
 import numpy as np
 
-from cryo_ralib_amd import umap
+from cryo_ralib_amd import _graph, umap
 
 U = 2.0 ** -53
 SK_ROWS = 4                 # rows per workgroup of umap_smooth_kernel
@@ -98,7 +98,7 @@ class EpochCase:
     def terms(self, t):
         """the number of terms vertex i adds in epoch t, [n]"""
         f = umap.fires(self.rate, t)
-        return np.bincount(umap._row_ids(self.indptr.astype(np.int64))[f], minlength=self.n) * (1 + self.neg)
+        return np.bincount(_graph.row_ids_numpy(self.indptr.astype(np.int64))[f], minlength=self.n) * (1 + self.neg)
 
 
 def epoch_lengths():
