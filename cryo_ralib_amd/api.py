@@ -56,7 +56,15 @@ class RaOptions(ctypes.Structure):
 RESULT_DTYPE = np.dtype([("alpha", np.float32), ("sx", np.float32), ("sy", np.float32), ("mirror", np.int32),
                          ("ref_id", np.int32), ("peak", np.float32), ("angle_bin", np.int32),
                          ("shift_idx", np.int32)])
-
+# candidate record of the search kernels (CandT, 40 bytes): peak, jtot word (bits 0-12 jtot | 13-20 runner-up reference + 1 | 21 its
+# mirror flag | 22-31 its jtot), reference | mirror << 16, the 7 CCF samples around the peak
+CAND_DTYPE = np.dtype([("val", np.float32), ("jtot", np.int32), ("refmir", np.int32), ("t7", np.float32, (7,))])
+# record of the refine list (RefineRec, 120 bytes): the winner and up to 7 alternates (offset, reference tile, reference | mirror << 16)
+REFINE_ALTS = 7
+REFINE_DTYPE = np.dtype([("p", np.int32), ("ref", np.int32), ("mirror", np.int32), ("jtot", np.int32), ("bs", np.int32),
+                         ("brt", np.int32), ("sxi", np.float32), ("syi", np.float32), ("nalt", np.int32),
+                         ("alt", np.dtype([("bs", np.int32), ("rt", np.int32), ("refmir", np.int32)]), (REFINE_ALTS,))])
+assert CAND_DTYPE.itemsize == 40 and REFINE_DTYPE.itemsize == 120 and REFINE_DTYPE.fields["alt"][1] == 36
 
 
 class RaLdsRow(ctypes.Structure):
@@ -75,7 +83,7 @@ EXPORTED_SYMBOLS = [
     "ref_free_alignment_2D_filter_references", "ra_isac_get_references", "ra_legacy_bytes",
     "ra_last_error", "ra_create", "ra_destroy", "ra_set_stream", "ra_num_shifts", "ra_maxrin", "ra_lcirc", "ra_search_path", "ra_search_tiled", "ra_search_l1_tap_rings", "ra_l1_tap_rule", "ra_search_offsets_per_pass", "ra_set_nomirror", "ra_set_mask",
     "ra_reset_shifts", "ra_set_references", "ra_get_prepared_references", "ra_align", "ra_state_from_params", "ra_set_refine", "ra_set_class_references", "ra_align_classes",
-    "ra_debug_spectra", "ra_transform_accumulate", "ra_update_references", "ra_normalize_particles", "ra_sync", "ra_kernel_time",
+    "ra_debug_spectra", "ra_debug_exact_references", "ra_debug_finalize", "ra_debug_refine", "ra_transform_accumulate", "ra_update_references", "ra_normalize_particles", "ra_sync", "ra_kernel_time",
     "ra_fsc_len", "ra_class_fsc", "ra_last_class_fsc", "ra_fit_tanh", "ra_class_averages", "ra_filter_references",
     "ra_state_from_params_dev", "ra_class_fsc_fit", "ra_filter_references_dev", "ra_last_refine_count", "ra_lds_report",
     "ra_create_ex", "ra_set_normalize_ring", "ra_get_options", "ra_search_skips_offsets", "ra_phase_flip",
@@ -149,6 +157,10 @@ def load_library(path=None):
     L.ra_normalize_particles.argtypes = [vp, vp, ctypes.c_int]
     L.ra_sync.argtypes = [vp]
     L.ra_debug_spectra.argtypes = [vp, vp, ctypes.c_int, vp, vp]
+    L.ra_debug_exact_references.argtypes = [vp, vp, vp]
+    L.ra_debug_finalize.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, ctypes.c_int, ctypes.c_int, ctypes.c_float, vp, vp, vp,
+                                    ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    L.ra_debug_refine.argtypes = [vp, vp, ctypes.c_int, vp, ctypes.c_int, vp, vp, vp]
     L.ra_kernel_time.argtypes = [vp, ctypes.c_int, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int),
                                  ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)]
     L.ra_fsc_len.argtypes = [vp]
@@ -815,6 +827,44 @@ class Engine:
                                          self._ptr(state, self.torch.float32), out.ctypes.data_as(ctypes.c_void_p)),
                "ra_debug_spectra")
         return out
+
+    def debug_exact_references(self):
+        """(exact reference spectra [nref][lcirc], copy table [nref][2] = (first copy, next copy or -1)) of the sub-bin refinement
+        (ra_debug_exact_references)"""
+        refx = np.zeros((self.nref, self.lcirc), np.float32)
+        dup = np.zeros((self.nref, 2), np.int32)
+        _check(self.lib.ra_debug_exact_references(self.handle, refx.ctypes.data_as(ctypes.c_void_p), dup.ctypes.data_as(ctypes.c_void_p)),
+               "ra_debug_exact_references")
+        return refx, dup
+
+    def debug_finalize(self, cand, nrtile, state, kernel, live, refine_thr, with_list=True):
+        """finalize_kernel (kernel 0) or finalize_wave_kernel (1) over hand-built records (ra_debug_finalize): cand CAND_DTYPE, dense
+        [n][ent_stride][nrtile] or (live) the in-window offsets' records only; state float32 [n][2].  Returns (results RESULT_DTYPE [n],
+        new state [n][2], refine list REFINE_DTYPE [count] in append order -- empty without a list)"""
+        cand = np.ascontiguousarray(cand, CAND_DTYPE)
+        state = np.ascontiguousarray(state, np.float32)
+        n = state.shape[0]
+        assert state.shape == (n, 2) and cand.size % int(nrtile) == 0
+        res = np.zeros(n, RESULT_DTYPE)
+        st = np.zeros((n, 2), np.float32)
+        rl = np.zeros(n, REFINE_DTYPE)
+        cnt = ctypes.c_int(0)
+        _check(self.lib.ra_debug_finalize(self.handle, cand.ctypes.data_as(ctypes.c_void_p), int(nrtile), n,
+                                          state.ctypes.data_as(ctypes.c_void_p), int(kernel), int(bool(live)), float(refine_thr),
+                                          res.ctypes.data_as(ctypes.c_void_p), st.ctypes.data_as(ctypes.c_void_p),
+                                          rl.ctypes.data_as(ctypes.c_void_p) if with_list else None, n, ctypes.byref(cnt)),
+               "ra_debug_finalize")
+        return res, st, rl[:cnt.value].copy()
+
+    def debug_refine(self, particles, rlist, state, result, cls=None):
+        """refine_winner_kernel over the hand-built list rlist (REFINE_DTYPE) against the engine's exact references, in place on the
+        CUDA tensors state [n][2] and result [n][8] (ra_debug_refine); cls: int32 CUDA tensor [n], class-resident mode"""
+        rlist = np.ascontiguousarray(rlist, REFINE_DTYPE)
+        n = particles.shape[0]
+        assert particles.shape[1:] == (self.nx, self.nx) and state.shape == (n, 2) and result.shape == (n, 8)
+        _check(self.lib.ra_debug_refine(self.handle, self._ptr(particles, self.torch.float32), n, rlist.ctypes.data_as(ctypes.c_void_p),
+                                        int(rlist.size), self._ptr(state, self.torch.float32), self._ptr(result, self.torch.int32),
+                                        self._ptr(cls, self.torch.int32)), "ra_debug_refine")
 
     # -- reference update on the device (SURVEY.md section 8 row f-1)
     def class_fsc(self, sums, counts, min_count=4, masked=False):

@@ -2463,3 +2463,140 @@ extern "C" int ra_rot_shift2d(const float *d_in, int n, int nx, const ra_result 
     // the kernel and grid ra_transform_accumulate picks for the same box without sums
     return launch_transform(stream, nullptr, nx, d_in, n, 0, d_params, d_out, nullptr, nullptr);
 }
+
+// ---- diagnostics of the decision stage (include/ralign.h): the engine's finalize and replay kernels on hand-built records.
+// Buffers of their own, the engine's DevGeom by value: nothing a search uses is written.
+
+// the record layouts the numpy dtypes of api.py restate (CAND_DTYPE, REFINE_DTYPE)
+static_assert(sizeof(CandT) == 40 && offsetof(CandT, t7) == 12, "CandT: update CAND_DTYPE (api.py)");
+static_assert(sizeof(RefineRec) == 120 && offsetof(RefineRec, alt) == 36 && sizeof(RefineAlt) == 12, "RefineRec: update REFINE_DTYPE (api.py)");
+#define RA_DEBUG_MAX_N 32768          // live_scan_kernel's bound
+
+namespace {
+// device buffers of one diagnostic call, freed when it returns
+struct DebugBufs {
+    std::vector<void *> ptrs;
+    ~DebugBufs() { for (void *p : ptrs) (void)hipFree(p); }
+    template <class T> hipError_t get(T **p, size_t count)
+    {
+        const hipError_t he = hipMalloc((void **)p, std::max<size_t>(count, 1) * sizeof(T));
+        if (he == hipSuccess) ptrs.push_back(*p);
+        return he;
+    }
+};
+bool debug_refine_ready(const ra_engine *e)
+{
+    if (e->refine_ok && e->refs_ready && e->refine_thr != 0.f && e->d_refx && e->dg.ref_dup) return true;
+    g_last_error = "the decision diagnostics need the sub-bin refinement (ra_set_refine != 0) and ra_set_references";
+    return false;
+}
+}  // namespace
+
+extern "C" int ra_debug_exact_references(ra_engine *e, float *h_refx, int *h_dup)
+{
+    if (!e) { g_last_error = "null argument"; return RA_ERR_ARG; }
+    if (!debug_refine_ready(e)) return RA_ERR_STATE;
+    RA_HIP(hipStreamSynchronize(e->stream));
+    if (h_refx) RA_HIP(hipMemcpy(h_refx, e->d_refx, (size_t)e->cfg.nref * e->geo.lcirc * sizeof(float), hipMemcpyDeviceToHost));
+    if (h_dup) RA_HIP(hipMemcpy(h_dup, e->d_refdup, (size_t)2 * e->cfg.nref * sizeof(int), hipMemcpyDeviceToHost));
+    return RA_OK;
+}
+
+extern "C" int ra_debug_finalize(ra_engine *e, const void *h_cand, int nrtile, int n, const float *h_state, int kernel, int live,
+                                 float refine_thr, ra_result *h_res, float *h_state_out, void *h_rlist, int rlist_cap, int *h_count)
+{
+    if (!e || !h_cand || !h_state || !h_res || !h_state_out || !h_count || n < 1 || n > RA_DEBUG_MAX_N || nrtile < 1 || nrtile > 4096 ||
+        (kernel != 0 && kernel != 1) || (live != 0 && live != 1) || (h_rlist && rlist_cap < n)) {
+        g_last_error = "ra_debug_finalize: bad argument";
+        return RA_ERR_ARG;
+    }
+    if (!debug_refine_ready(e)) return RA_ERR_STATE;
+    DevGeom dg = e->dg;
+    DebugBufs bufs;
+    float *d_st = nullptr;
+    ra_result *d_res = nullptr;
+    int *d_base = nullptr, *d_total = nullptr, *d_cnt = nullptr;
+    CandT *d_cand = nullptr;
+    RefineRec *d_rl = nullptr;
+    RA_HIP(bufs.get(&d_st, (size_t)2 * n));
+    RA_HIP(bufs.get(&d_res, (size_t)n));
+    RA_HIP(bufs.get(&d_cnt, 1));
+    RA_HIP(bufs.get(&d_base, (size_t)n + 8));
+    RA_HIP(bufs.get(&d_total, 4));
+    if (h_rlist) RA_HIP(bufs.get(&d_rl, (size_t)n));
+    RA_HIP(hipMemcpyAsync(d_st, h_state, (size_t)2 * n * sizeof(float), hipMemcpyHostToDevice, e->stream));
+    RA_HIP(hipMemsetAsync(d_cnt, 0, sizeof(int), e->stream));
+    RA_HIP(hipMemsetAsync(d_res, 0, (size_t)n * sizeof(ra_result), e->stream));
+    if (d_rl) RA_HIP(hipMemsetAsync(d_rl, 0, (size_t)n * sizeof(RefineRec), e->stream));          // (alt[nalt ..] is not written: zeros, the same bytes every time)
+    size_t entries = (size_t)n * dg.ent_stride;
+    dg.ent_base = nullptr; dg.ent_total = nullptr;
+    if (live) {          // the entry ranges as the size-generic path lays them out before its kernels
+        hipLaunchKernelGGL(live_scan_kernel, dim3(1), dim3(1024), 0, e->stream, dg, (const float *)d_st, n, d_base, d_total);
+        RA_HIP(hipGetLastError());
+        int total = 0;
+        RA_HIP(hipMemcpyAsync(&total, d_total, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+        RA_HIP(hipStreamSynchronize(e->stream));
+        if (total < 0 || (size_t)total > (size_t)n * e->geo.nshift) { g_last_error = "ra_debug_finalize: live_scan_kernel left an impossible total"; return RA_ERR_HIP; }
+        entries = (size_t)total;
+        dg.ent_base = d_base; dg.ent_total = d_total;
+    }
+    RA_HIP(bufs.get(&d_cand, entries * nrtile + 8));
+    RA_HIP(hipMemsetAsync(d_cand, 0, (entries * nrtile + 8) * sizeof(CandT), e->stream));
+    if (entries) RA_HIP(hipMemcpyAsync(d_cand, h_cand, entries * nrtile * sizeof(CandT), hipMemcpyHostToDevice, e->stream));
+    if (kernel == 1)
+        hipLaunchKernelGGL(finalize_wave_kernel, dim3(n), dim3(64), 0, e->stream, dg, (const CandT *)d_cand, nrtile, n, d_st, d_res, d_rl, d_cnt, refine_thr, 0);
+    else
+        hipLaunchKernelGGL(finalize_kernel, dim3((n + 127) / 128), dim3(128), 0, e->stream, dg, (const CandT *)d_cand, nrtile, n, d_st, d_res,
+                           (const float *)e->d_cs, d_rl, d_cnt, refine_thr, 0);
+    RA_HIP(hipGetLastError());
+    int count = 0;
+    RA_HIP(hipMemcpyAsync(&count, d_cnt, sizeof(int), hipMemcpyDeviceToHost, e->stream));
+    RA_HIP(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(ra_result), hipMemcpyDeviceToHost, e->stream));
+    RA_HIP(hipMemcpyAsync(h_state_out, d_st, (size_t)2 * n * sizeof(float), hipMemcpyDeviceToHost, e->stream));
+    RA_HIP(hipStreamSynchronize(e->stream));
+    if (count < 0 || count > n) { g_last_error = "ra_debug_finalize: the refine list has an impossible count"; return RA_ERR_HIP; }
+    if (h_rlist && count) RA_HIP(hipMemcpy(h_rlist, d_rl, (size_t)count * sizeof(RefineRec), hipMemcpyDeviceToHost));
+    *h_count = count;
+    return RA_OK;
+}
+
+extern "C" int ra_debug_refine(ra_engine *e, const float *d_particles, int n, const void *h_rlist, int count, float *d_state,
+                               ra_result *d_result, const int *d_cls)
+{
+    if (!e || !d_particles || !h_rlist || !d_state || !d_result || n < 1 || count < 1 || count > RA_DEBUG_MAX_N) {
+        g_last_error = "ra_debug_refine: bad argument";
+        return RA_ERR_ARG;
+    }
+    if (!debug_refine_ready(e)) return RA_ERR_STATE;
+    const int nref = e->cfg.nref, nshift = e->geo.nshift;
+    const RefineRec *recs = static_cast<const RefineRec *>(h_rlist);
+    for (int i = 0; i < count; i++) {          // every index the kernel follows stays inside the engine's tables
+        const RefineRec &r = recs[i];
+        bool ok = r.p >= 0 && r.p < n && r.ref >= 0 && r.ref < nref && r.bs >= 0 && r.bs < nshift && r.nalt >= 0 && r.nalt <= RA_TIE_ALTS &&
+                  (r.mirror == 0 || r.mirror == 1);
+        for (int a = 0; ok && a < r.nalt; a++)
+            ok = r.alt[a].bs >= 0 && r.alt[a].bs < nshift && (r.alt[a].refmir & 0xffff) < nref && (r.alt[a].refmir >> 16 == 0 || r.alt[a].refmir >> 16 == 1);
+        if (!ok) { g_last_error = "ra_debug_refine: a record points outside the engine's tables"; return RA_ERR_ARG; }
+    }
+    if (d_cls) {
+        std::vector<int> cls((size_t)n);
+        RA_HIP(hipStreamSynchronize(e->stream));
+        RA_HIP(hipMemcpy(cls.data(), d_cls, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+        for (int c : cls)
+            if (c < 0 || c >= nref) { g_last_error = "ra_debug_refine: a class outside the engine's references"; return RA_ERR_ARG; }
+    }
+    DebugBufs bufs;
+    RefineRec *d_rl = nullptr;
+    int *d_cnt = nullptr;
+    RA_HIP(bufs.get(&d_rl, (size_t)count));
+    RA_HIP(bufs.get(&d_cnt, 1));
+    RA_HIP(hipMemcpyAsync(d_rl, h_rlist, (size_t)count * sizeof(RefineRec), hipMemcpyHostToDevice, e->stream));
+    RA_HIP(hipMemcpyAsync(d_cnt, &count, sizeof(int), hipMemcpyHostToDevice, e->stream));
+    const auto k = e->refine_gm ? refine_winner_kernel<true> : refine_winner_kernel<false>;
+    hipLaunchKernelGGL(k, dim3(std::min(count, e->refine_grid)), dim3(RA_EXACT_THREADS), e->lds_refine, e->stream, e->dg, (const int *)e->d_numr,
+                       (const float *)e->d_twx, (const int *)e->d_twxoff, d_particles, (const float *)e->d_refx, (const RefineRec *)d_rl,
+                       (const int *)d_cnt, d_result, d_cls, d_state, e->d_rscratch);
+    RA_HIP(hipGetLastError());
+    RA_HIP(hipStreamSynchronize(e->stream));
+    return RA_OK;
+}

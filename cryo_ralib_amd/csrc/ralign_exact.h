@@ -40,7 +40,7 @@ namespace ralign {
 // GM: the ring buffers live in global memory (boxes whose rings exceed the LDS: 271 KB per offset at 256 x 256 / ou = 120); the
 // workgroup's threads then hand data to each other through the CU's vector cache.
 #define RA_EXACT_THREADS 256
-#define RA_TIE_EXP 64            // entries of the replayed scan: candidates x copies of their references (more: the first 64)
+#define RA_TIE_EXP 64            // entries of the replayed scan: candidates x copies of their references (more: the scan walks the copy chains instead, refine_winner_kernel)
 #define RA_EXACT_TABLE_BYTES(maxrin) ((size_t)24 * (maxrin))      // refine_winner_kernel: [maxrin] double2 twiddles + [maxrin] double samples
 // static LDS of refine_winner_kernel -- red, redi, cand_inf, cand_b, cand_win, ex_key, ex_ci, ex_mir, ex_ref, ex_bs: 1276 bytes --
 // rounded up to 64: the room the host rules leave beside the kernel's dynamic LDS (1280 bytes, the code object's figure).
@@ -432,11 +432,13 @@ __global__ __launch_bounds__(RA_EXACT_THREADS) void refine_winner_kernel(DevGeom
         __syncthreads();
         if (lane == 0) {
             int nex = 0;
+            bool fits = true;          // the whole expansion is in the list
             for (int ci = 0; ci < ncand; ci++) {
                 const int r0 = cand_inf[ci][0];
                 const long long hi = (long long)cand_inf[ci][3] << 32;
                 if (g.ref_dup && !cls) {
-                    for (int r2 = g.ref_dup[2 * r0]; r2 >= 0 && nex < RA_TIE_EXP; r2 = g.ref_dup[2 * r2 + 1]) {
+                    for (int r2 = g.ref_dup[2 * r0]; r2 >= 0; r2 = g.ref_dup[2 * r2 + 1]) {
+                        if (nex == RA_TIE_EXP) { fits = false; break; }
                         ex_key[nex] = hi | (unsigned)r2; ex_ci[nex] = (unsigned char)ci; ex_mir[nex] = (unsigned char)cand_inf[ci][1]; nex++;
                     }
                 } else if (nex < RA_TIE_EXP) {
@@ -445,29 +447,55 @@ __global__ __launch_bounds__(RA_EXACT_THREADS) void refine_winner_kernel(DevGeom
             }
             const bool float_peak = g.mode == RA_MODE_MREF;
             double peak = -1.0e23;
-            int cur = -1;
-            unsigned long long used = 0;
-            for (int step = 0; step < nex; step++) {
-                int c = -1;          // the next (offset, reference) in scan order
-                for (int k = 0; k < nex; k++)
-                    if (!((used >> k) & 1) && (c < 0 || ex_key[k] < ex_key[c])) c = k;
-                if (c < 0) break;
-                int cs = -1, cm = -1;          // its straight and mirrored entries (the first of each, duplicates are dropped)
-                for (int k = 0; k < nex; k++)
-                    if (!((used >> k) & 1) && ex_key[k] == ex_key[c]) {
-                        used |= 1ull << k;
-                        if (ex_mir[k]) { if (cm < 0) cm = k; } else { if (cs < 0) cs = k; }
-                    }
-                const double qn = cs >= 0 ? cand_b[ex_ci[cs]][3] : -1.0e300, qm = cm >= 0 ? cand_b[ex_ci[cm]][3] : -1.0e300;
+            int wci = 0;                                   // the scan's winner: its candidate and its (offset, reference)
+            long long wkey = ex_key[0];                    // (no peak a number: the first entry)
+            // one (offset, reference) of the scan: its straight and mirrored candidates cs, cm (-1: none)
+            auto visit = [&](long long key, int cs, int cm) {
+                const double qn = cs >= 0 ? cand_b[cs][3] : -1.0e300, qm = cm >= 0 ? cand_b[cm][3] : -1.0e300;
                 if (qn >= peak || qm >= peak) {
-                    cur = qn >= qm ? cs : cm;
+                    wci = qn >= qm ? cs : cm; wkey = key;
                     const double v = qn >= qm ? qn : qm;
                     peak = float_peak ? (double)(float)v : v;
                 }
+            };
+            if (fits) {
+                unsigned long long used = 0;
+                for (int step = 0; step < nex; step++) {
+                    int c = -1;          // the next (offset, reference) in scan order
+                    for (int k = 0; k < nex; k++)
+                        if (!((used >> k) & 1) && (c < 0 || ex_key[k] < ex_key[c])) c = k;
+                    if (c < 0) break;
+                    int cs = -1, cm = -1;          // its straight and mirrored entries (the first of each, duplicates are dropped)
+                    for (int k = 0; k < nex; k++)
+                        if (!((used >> k) & 1) && ex_key[k] == ex_key[c]) {
+                            used |= 1ull << k;
+                            if (ex_mir[k]) { if (cm < 0) cm = ex_ci[k]; } else { if (cs < 0) cs = ex_ci[k]; }
+                        }
+                    visit(ex_key[c], cs, cm);
+                }
+            } else {
+                // more entries than the list holds (8 candidates whose references have 9 copies each: 72): the same scan without the
+                // list.  The copies of a reference are chained in ascending order (ref_dup), so every candidate keeps ONE cursor --
+                // the key of the copy it stands at, in ex_key[ci], -1 behind its last copy -- and the scan takes the smallest key of
+                // all cursors, then moves the cursors that stood there.
+                for (int ci = 0; ci < ncand; ci++) ex_key[ci] = ((long long)cand_inf[ci][3] << 32) | (unsigned)g.ref_dup[2 * cand_inf[ci][0]];
+                for (;;) {
+                    long long key = -1;
+                    for (int ci = 0; ci < ncand; ci++)
+                        if (ex_key[ci] >= 0 && (key < 0 || ex_key[ci] < key)) key = ex_key[ci];
+                    if (key < 0) break;
+                    const int nxt = g.ref_dup[2 * (int)(key & 0xffffffffll) + 1];
+                    int cs = -1, cm = -1;
+                    for (int ci = 0; ci < ncand; ci++)
+                        if (ex_key[ci] == key) {
+                            if (cand_inf[ci][1]) { if (cm < 0) cm = ci; } else { if (cs < 0) cs = ci; }
+                            ex_key[ci] = nxt >= 0 ? ((key >> 32) << 32) | (unsigned)nxt : -1ll;
+                        }
+                    visit(key, cs, cm);
+                }
             }
-            if (cur < 0) cur = 0;
-            cand_win = ex_ci[cur];
-            ex_ref = (int)(ex_key[cur] & 0xffffffffll); ex_bs = (int)(ex_key[cur] >> 32);
+            cand_win = wci;
+            ex_ref = (int)(wkey & 0xffffffffll); ex_bs = (int)(wkey >> 32);
         }
         __syncthreads();
         const int wsel = cand_win;

@@ -275,6 +275,28 @@ int  ra_normalize_particles(ra_engine *e, float *d_particles, int n);
  * spectra of every search offset in EMAN2 packing, h_out [n][num_shifts][lcirc] (what
  * Polar2Dm -> Normalize_ring -> Frngs leave in `cimage` inside Util.multiref_polar_ali_2d) */
 int  ra_debug_spectra(ra_engine *e, const float *d_particles, int n, const float *d_state, float *h_out);
+/* diagnostics of the decision stage (finalize and the exact replay; tests/test_gpu_decision.py).  They launch the engine's own
+ * kernels with its geometry, tables and stream on buffers of their own, change nothing a search uses, and need the sub-bin
+ * refinement (ra_set_refine != 0, ra_set_references called): RA_ERR_STATE otherwise, RA_ERR_ARG for a bad argument; either
+ * way nothing is launched or written.  The record layouts (40-byte candidate record, 120-byte refine record) are
+ * CAND_DTYPE / REFINE_DTYPE of cryo_ralib_amd/api.py.
+ * ra_debug_exact_references: the exact reference spectra h_refx [nref][lcirc] (Polar2Dm -> Frngs -> Applyws in the CPU path's
+ * arithmetic) and the copy table h_dup [nref][2] = (first copy, next copy or -1); either may be NULL. */
+int  ra_debug_exact_references(ra_engine *e, float *h_refx, int *h_dup);
+/* ra_debug_finalize: finalize_kernel (kernel = 0) or finalize_wave_kernel (1) over hand-built candidate records of n <= 32768
+ * particles with the states h_state [n][2].  live = 0: h_cand [n][ent_stride][nrtile] (ent_stride: the engine's entries per
+ * particle, num_shifts rounded up to 4 -- or num_shifts itself on the size-generic path); live = 1: the records of the in-window
+ * offsets only, [ent_base[n]][nrtile], laid out by live_scan_kernel on h_state.  refine_thr as ra_set_refine's threshold.
+ * Out: h_res [n] results, h_state_out [n][2], and -- h_rlist != NULL, rlist_cap >= n -- the refine list (in the order of the
+ * atomic appends) with *h_count entries; h_rlist = NULL: the kernels run without a list and *h_count = 0. */
+int  ra_debug_finalize(ra_engine *e, const void *h_cand, int nrtile, int n, const float *h_state, int kernel, int live,
+                       float refine_thr, ra_result *h_res, float *h_state_out, void *h_rlist, int rlist_cap, int *h_count);
+/* ra_debug_refine: refine_winner_kernel (ring buffers in LDS or in global scratch, as the engine runs it) over the hand-built
+ * list h_rlist [count] (count <= 32768, every index inside the engine's tables) against the engine's exact references;
+ * d_particles [n][nx][nx], d_state [n][2], d_result [n] as the search leaves them, d_cls [n] (class-resident mode: particle p
+ * against reference d_cls[p], copies ignored) or NULL.  Synchronises. */
+int  ra_debug_refine(ra_engine *e, const float *d_particles, int n, const void *h_rlist, int count, float *d_state,
+                     ra_result *d_result, const int *d_cls);
 /* ---- reference update of one iteration on the device (what the reference's main node does on the
  * CPU, test_mref_gpu_align.py:517-564 / test_reffree_gpu_align.py:374-429, default user function) */
 /* length of an FSC curve: nx/2 + 1 */
